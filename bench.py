@@ -18,7 +18,9 @@ launches with.  Inputs are resident in HBM before the timed region.
           same flow is timed on a 1024x1024x64 frame (BASELINE.json configs[3]) and reported as `config4_1024`.
           --scaling weak: every rank renders its own full frame (a band of an N-times larger image) + the same all-gather.
 
-One JSON line is printed by rank 0; see DESIGN.md for the accounting behind `roofline`.
+One JSON line is printed by rank 0; see DESIGN.md for the accounting behind `roofline`.  `ms_per_step` is the wall time of one
+timed step (--steps of them, after --warmup untimed ones).  --dump-outputs DIR writes the maps the last timed step returned
+(dump_outputs); the inputs depend on the arguments alone (--seed), so two builds can be compared output for output.
 """
 import argparse
 import importlib
@@ -86,6 +88,10 @@ def parse():
     ap.add_argument("--no-extras", action="store_true", help="skip the measurements reported beside the headline")
     ap.add_argument("--cpu-seconds", type=float, default=16.0, help="target CPU time of the cpu_baseline samples (half per CPU program)")
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the maps the last timed step returned as DIR/<name>.npy (float32; integer maps as "
+                         "float64), at most 64 MB in all: arrays that do not fit are cut to the same fixed, seeded sample of rows; the NaN disparity of a "
+                         "ray that meets nothing (acc 0) is written as 0")
     ap.add_argument("--split-f16", action="store_true",
                     help="dense layers on f16 MFMA with fp32 operands split into hi+lo (GPNERF_FLAG_SPLIT_F16)")
     ap.add_argument("--fold", action="store_true",
@@ -104,6 +110,8 @@ def parse():
                          "4x8 with --occ-cull: the rays of a compact block terminate / are culled together far more often than those "
                          "of a 32-pixel row")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.patch is None:
         args.patch = "8x4" if args.early_term else ("4x8" if args.occ_cull else "32x8")
     return args
@@ -145,6 +153,49 @@ def time_launches(fn, steps, warmup):
         b.record()
     torch.cuda.synchronize()
     return float(np.mean([a.elapsed_time(b) for a, b in ev])), out
+
+
+DUMP_BYTES = 60_000_000            # --dump-outputs: the arrays of one dump together stay below this (64 MB with room for the headers)
+DUMP_SEED = 2024                   # ... and the rows kept of the arrays that would not fit whole come from PCG64(DUMP_SEED)
+
+
+def dump_outputs(out, path, budget=DUMP_BYTES, seed=DUMP_SEED):
+    """--dump-outputs: every tensor of `out` (one step's maps, one row per ray) as path/<name>.npy, float32 as computed (other
+    dtypes as float64, exactly).  When the whole set exceeds `budget` bytes, the widest arrays (per-sample weights / z_vals first)
+    are cut, until the whole ones take at most half the budget, to one shared, sorted sample of rows drawn from PCG64(seed): the
+    rows depend on the ray count alone, so runs with the same arguments write the same rows.  Returns what was written.
+    disp_map is 1 / max(1e-10, depth / acc) with the reference's NaN for a ray whose weights are all zero (BaseRender.py:102, 0 / 0,
+    which torch.max passes on): such a ray meets nothing, its depth is unbounded, and the dump writes its disparity as 0.  Only
+    those entries (NaN where acc_map == 0) are rewritten; any other non-finite value is written as computed."""
+    import torch
+    arrs = {}
+    for k, v in out.items():
+        if torch.is_tensor(v):
+            a = v.detach().cpu().numpy()
+            arrs[k] = a if a.dtype == np.float32 else a.astype(np.float64)
+    n = {a.shape[0] for a in arrs.values()}
+    assert len(n) == 1, {k: a.shape for k, a in arrs.items()}
+    n = n.pop()
+    empty = None
+    if "disp_map" in arrs and "acc_map" in arrs:
+        empty = np.isnan(arrs["disp_map"]) & (arrs["acc_map"] == 0)
+        arrs["disp_map"] = np.where(empty, arrs["disp_map"].dtype.type(0), arrs["disp_map"])
+    whole = sorted(arrs, key=lambda k: arrs[k].nbytes)
+    cut, rows = [], None
+    if sum(a.nbytes for a in arrs.values()) > budget:
+        while sum(arrs[k].nbytes for k in whole) > budget // 2:
+            cut.append(whole.pop())
+        m = (budget - sum(arrs[k].nbytes for k in whole)) // sum(arrs[k].nbytes // n for k in cut)
+        rows = np.sort(np.random.Generator(np.random.PCG64(seed)).choice(n, size=m, replace=False))
+        for k in cut:
+            arrs[k] = arrs[k][rows]
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrs.items():
+        np.save(os.path.join(path, k + ".npy"), np.ascontiguousarray(a))
+    return {"dir": os.path.abspath(path), "arrays": {k: list(a.shape) for k, a in sorted(arrs.items())}, "rays": int(n),
+            "row_sample": None if rows is None else {"arrays": sorted(cut), "rows": int(rows.size), "seed": seed},
+            "bytes": int(sum(a.nbytes for a in arrs.values())),
+            "disp_of_empty_rays_as_0": None if empty is None else int(empty.sum())}
 
 
 def device_identity(dev):
@@ -327,6 +378,8 @@ def main():
     # and sit in the profiler's average of this kernel)
     step_stats = fm.render_fused(wl.frame, flow.rays, S, want=flow.want + ("step_stats",), ray_order=flow.order, fold=flow.fold, **kw)["step_stats"].cpu().numpy()
     dt, kernel_ms, out = flow.timed(args.steps, args.warmup)
+    # what the last timed step returned, on the host before anything else runs on the device
+    dumped = dump_outputs(out, args.dump_outputs) if (args.dump_outputs and rank == 0) else None
     # who ran where: every rank's device identity and its own event times, gathered once, after the timed region
     report = dict(device_identity(dev), rank=rank, local_rank=local_rank, kernel_ms=kernel_ms, exchange_ms=getattr(flow, "exchange_ms", None),
                   rays=int(flow.n_local))
@@ -451,6 +504,8 @@ def main():
         # sanity on the product's own output (not a parity check; tests/ do that)
         assert bool(torch.isfinite(out["rgb_map"]).all()), "non-finite rgb"
         line["maps_finite"] = bool(torch.isfinite(out["rgb_map"]).all() and torch.isfinite(out["depth_map"]).all())
+        if dumped is not None:
+            line["dump_outputs"] = dumped
         print(json.dumps(line), flush=True)
     if world > 1:
         dist.destroy_process_group()

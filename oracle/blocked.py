@@ -3,10 +3,13 @@
 Test / bench infrastructure only (see the C file's header): the product never imports this.  The library is compiled with
 -march=native, so it is built on the host it runs on, under a name that carries a hash of that host's CPU flags (a build
 made in the container is not loaded on the GPU box's host)."""
+import atexit
 import ctypes as C
 import hashlib
 import os
+import shutil
 import subprocess
+import tempfile
 
 import numpy as np
 
@@ -47,10 +50,16 @@ _lib = None
 
 
 def lib():
+    """The library for this host: __graft_entry__.build() compiles it next to the source.  A host without one compiles it there
+    on first use or, where this directory is read-only, into a private temporary directory of the process."""
     global _lib
     if _lib is None:
         path = os.path.join(HERE, f"libgpnerf_cpu_blocked.{_host_tag()}.so")
         if not os.path.exists(path):
+            if not os.access(HERE, os.W_OK):
+                tmp = tempfile.mkdtemp(prefix="gpnerf_cpu_blocked_")
+                atexit.register(shutil.rmtree, tmp, True)
+                path = os.path.join(tmp, os.path.basename(path))
             subprocess.check_call(["gcc", "-O3", "-march=native", "-ffp-contract=off", "-fopenmp", "-fPIC", "-shared", "-std=gnu11", "-Wall",
                                    "-o", path, SRC, "-lm"])
         _lib = C.CDLL(path)

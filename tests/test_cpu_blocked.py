@@ -31,3 +31,24 @@ def test_blocked_twin_ragged_blocks(oracle, syn):
         ref = oracle.render(sc, S)
         for k in ("rgb_map", "depth_map", "acc_map", "weights"):
             assert_close(got[k], ref[k], 5e-5 if k == "depth_map" else 1e-5, f"{k} S={S} n={n}")
+
+
+def test_blocked_twin_loads_from_a_read_only_tree(monkeypatch, tmp_path, oracle, syn):
+    """A host without a library built for it, in a checkout it may not write to (the benchmark's cpu_baseline run by another
+    user than the build): the twin compiles into a private temporary directory, writes nothing next to its source, and renders
+    as the oracle does."""
+    import os
+    from oracle import blocked
+    ro = tmp_path / "oracle"
+    ro.mkdir()
+    access = os.access
+    monkeypatch.setattr(blocked, "HERE", str(ro))
+    monkeypatch.setattr(blocked, "_lib", None)
+    monkeypatch.setattr(os, "access", lambda p, mode, **kw: False if (os.fspath(p) == str(ro) and mode & os.W_OK) else access(p, mode, **kw))
+    assert blocked.max_threads() >= 1
+    assert os.listdir(ro) == []
+    sc = syn.make_scene(H=16, W=16, seed=7, fill="full", pose="random", aabb_half=(0.12, 0.16, 0.05), bias_std=0.1)
+    got = blocked.render(blocked.Frame(sc), oracle.rays_of(sc), 16)
+    ref = oracle.render(sc, 16)
+    for k in ("rgb_map", "depth_map", "acc_map", "weights"):
+        assert_close(got[k], ref[k], 5e-5 if k == "depth_map" else 1e-5, k)
