@@ -2638,6 +2638,89 @@ head_forward_kernel(const float* __restrict__ blob, const float* __restrict__ vo
 }
 
 // ---------------------------------------------------------------------------------------------
+// the inference renderer's density lattice (libs/renders/demo_render.py:249-311,366-371; use_rgbhead=False)
+// ---------------------------------------------------------------------------------------------
+// One lane per lattice point, 32 points per wavefront (the two lane halves split the K dimension of every dense layer, as in the
+// sample loop).  A tile is a brick of LAT_BY x LAT_BZ points of one x-slice of the PADDED cube, so that neighbouring lanes sample
+// neighbouring texels and voxels (shared L2 lines); the tiles of the padding and the tiles whose 32 points are all culled only
+// store zeros -- no gather, no matrix work.  The kept points run the reference-order form's device code (the fused kernel's
+// FORM_F32 step without its colour branch): grid_sample of the occupancy (the cull), the four volume levels (multiply-then-add
+// taps), the sigma feature layer, Projector.compute of the three views, mean / variance and the density branch.
+constexpr int LAT_BY = 4, LAT_BZ = 8, LAT_WAVES = 8;
+struct LatticeArgs {          // the kernel's only argument, read through the kernarg segment (as render_fused_kernel's)
+    FrameK fr;
+    const float* axis[3];     // lattice coordinates (x, y, z), device
+    int n[3];                 // lattice size
+    int pad;                  // zero border of the cube on every side
+    int neg;                  // Projector(neg_ray)
+    long n_tiles;
+    int bricks_y, bricks_z;   // of the padded cube
+    float* cube;              // [n0 + 2 pad][n1 + 2 pad][n2 + 2 pad]
+    unsigned long long* n_kept;
+};
+typedef const __attribute__((address_space(4))) LatticeArgs* lattice_ptr;
+
+__global__ void __launch_bounds__(LAT_WAVES * 64, LAT_WAVES / 4) density_lattice_kernel(const LatticeArgs) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    lattice_ptr ka = (lattice_ptr)__builtin_amdgcn_kernarg_segment_ptr();
+    {
+        const f32x4* src = reinterpret_cast<const f32x4*>(ka->fr.head_blob_ref);
+        f32x4* dst = reinterpret_cast<f32x4*>(lds);
+        for (int i = threadIdx.x; i < gpl::BLOB_FLOATS / 4; i += LAT_WAVES * 64) dst[i] = src[i];
+    }
+    __syncthreads();
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, n = lane & 31, half = lane >> 5;
+    for (long tile = (long)blockIdx.x * LAT_WAVES + wave; tile < ka->n_tiles; tile += (long)gridDim.x * LAT_WAVES) {
+        lattice_ptr kt = (lattice_ptr)__builtin_amdgcn_kernarg_segment_ptr();     // re-read per tile (see render_tile)
+        asm volatile("" : "+s"(kt));
+        const __attribute__((address_space(4))) FrameK& fr = kt->fr;
+        const int pad = kt->pad, n0 = kt->n[0], n1 = kt->n[1], n2 = kt->n[2];
+        const int PY = n1 + 2 * pad, PZ = n2 + 2 * pad;
+        const int bz = (int)(tile % kt->bricks_z);
+        const long r = tile / kt->bricks_z;
+        const int by = (int)(r % kt->bricks_y), x = (int)(r / kt->bricks_y);
+        const int y = by * LAT_BY + (n / LAT_BZ), z = bz * LAT_BZ + (n % LAT_BZ);
+        const bool in_cube = y < PY && z < PZ;
+        const int i = x - pad, j = y - pad, k = z - pad;
+        const bool inside = in_cube && (unsigned)i < (unsigned)n0 && (unsigned)j < (unsigned)n1 && (unsigned)k < (unsigned)n2;
+        float px = 0.f, py = 0.f, pz = 0.f, gx = 0.f, gy = 0.f, gz = 0.f;
+        bool keep = false;
+        if (inside) {
+            px = kt->axis[0][i]; py = kt->axis[1][j]; pz = kt->axis[2][k];
+            grid_coords(fr, px, py, pz, gx, gy, gz);                   // pts_to_can_pts + the demo's get_grid_coords (/ 0.005)
+            keep = sample_occupancy(fr.occ, fr.vol_dhw[0][0], fr.vol_dhw[0][1], fr.vol_dhw[0][2], gx, gy, gz) > 0.f;   // :270-281
+        }
+        float alpha = 0.f;
+        const unsigned long long kept = __ballot(keep) & 0xffffffffull;
+        if (kept) {
+            // SparseConvNet.forward sampling (:113-122) and the sigma feature layer: test_forward (trainhead.py:61-76)
+            float fv[64], sf[32];
+#pragma unroll
+            for (int l = 0; l < GPNERF_LEVELS; ++l)
+                gather_volume<true>(fr.vol[l], fr.vol_dhw[l][0], fr.vol_dhw[l][1], fr.vol_dhw[l][2], gx, gy, gz, half, fv + 16 * l);
+            unsigned bits = 0u;
+#pragma unroll
+            for (int t = 0; t < 64; t += 2) bits |= __builtin_bit_cast(unsigned, fv[t]) | __builtin_bit_cast(unsigned, fv[t + 1]);
+            if (__all((bits << 1) == 0u)) geo_bias_ref(lds, lane, sf);      // all volume features zero: ELU(bias), same bits
+            else {
+                float fk[64];
+#pragma unroll
+                for (int l = 0; l < GPNERF_LEVELS; ++l) interleave16(fv + 16 * l, fk + 16 * l);
+                geo_eval_ref(lds, lane, fk, sf);
+            }
+            // Projector.compute (BaseRender.py:326-363), fused_mean_variance, rgbhead.out_geometry_fc + masked_fill
+            float xv[NV][18], vrgb[NV][3], mv[36], sigma;
+            const float nvalid = gather_views<FORM_F32>(fr, px, py, pz, kt->neg != 0, half, xv, vrgb);
+            mean_var_ref(xv, mv);
+            mlp_density_ref(lds, lane, sf, mv, nvalid, sigma);
+            alpha = keep ? 1.f - expf(-sigma) : 0.f;                    // sigma2alpha (demo_render.py:315-316)
+        }
+        if (half == 0 && in_cube) kt->cube[((long)x * PY + y) * PZ + z] = alpha;
+        if (lane == 0 && kt->n_kept && kept) atomicAdd(kt->n_kept, (unsigned long long)__popcll(kept));
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
 // stage entry points: the same device functions as the fused kernel, one stage per launch
 // ---------------------------------------------------------------------------------------------
 // get_sampling_points + pts_to_can_pts + get_grid_coords (BaseRender.py:35-73): one lane per sample
@@ -3302,7 +3385,9 @@ int device_ready(int* cus) {
                    hipFuncSetAttribute(reinterpret_cast<const void*>(&head_forward_kernel<FUSED_WAVES, 1>),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes) == hipSuccess &&
                    hipFuncSetAttribute(reinterpret_cast<const void*>(&head_forward_kernel<FUSED_WAVES, 2>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes) == hipSuccess;
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes) == hipSuccess &&
+                   hipFuncSetAttribute(reinterpret_cast<const void*>(&density_lattice_kernel),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sizeof(float) * gpl::BLOB_FLOATS)) == hipSuccess;
         }
         (void)hipGetLastError();
     }
@@ -4142,6 +4227,37 @@ int gpnerf_build_occupancy(const GpnerfFrame* f, float* occ, void* stream) {
     if (!to_framek(f, k, true, false)) return GPNERF_E_ARG;
     const long n = (long)k.vol_dhw[0][0] * k.vol_dhw[0][1] * k.vol_dhw[0][2];
     hipLaunchKernelGGL(occupancy_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, S_(stream), k, occ);
+    return launch_status();
+}
+
+int gpnerf_density_lattice(const GpnerfFrame* f, const float* axis_x, const float* axis_y, const float* axis_z, const int32_t* dims,
+                           int32_t pad, int32_t neg_ray, float* cube, int64_t* n_kept, void* stream) {
+    if (!f || !axis_x || !axis_y || !axis_z || !dims || !cube || pad < 0 || !f->occ || !f->head_blob_ref) return GPNERF_E_ARG;
+    if (dims[0] < 1 || dims[1] < 1 || dims[2] < 1) return GPNERF_E_ARG;
+    const int64_t PX = (int64_t)dims[0] + 2 * (int64_t)pad, PY = (int64_t)dims[1] + 2 * (int64_t)pad, PZ = (int64_t)dims[2] + 2 * (int64_t)pad;
+    if (PX >= ((int64_t)1 << 24) || PY >= ((int64_t)1 << 24) || PZ >= ((int64_t)1 << 24) || PX * PY * PZ >= ((int64_t)1 << 40))
+        return GPNERF_E_ARG;
+    FrameK k;
+    if (!to_framek(f, k, true, true)) return GPNERF_E_ARG;
+    k.voxel[0] = k.voxel[1] = k.voxel[2] = 0.005f;     // demo_render.py:91 `xyz / 0.005`, as under GPNERF_FLAG_OCC_CULL
+    int n_cus = 0;
+    if (device_ready(&n_cus) != GPNERF_OK) return GPNERF_E_DEVICE;
+    LatticeArgs a;
+    a.fr = k;
+    a.axis[0] = axis_x; a.axis[1] = axis_y; a.axis[2] = axis_z;
+    for (int i = 0; i < 3; ++i) a.n[i] = dims[i];
+    a.pad = pad;
+    a.neg = neg_ray != 0;
+    a.bricks_y = (int)((PY + LAT_BY - 1) / LAT_BY);
+    a.bricks_z = (int)((PZ + LAT_BZ - 1) / LAT_BZ);
+    a.n_tiles = (long)PX * a.bricks_y * a.bricks_z;
+    a.cube = cube;
+    a.n_kept = reinterpret_cast<unsigned long long*>(n_kept);
+    if (n_kept && !zero_async(n_kept, sizeof(int64_t), stream)) return GPNERF_E_LAUNCH;
+    // one workgroup per CU (the head image fills most of its LDS), persistent over the tiles
+    const long wgs = (a.n_tiles + LAT_WAVES - 1) / LAT_WAVES;
+    const unsigned grid = (unsigned)(wgs < n_cus ? wgs : n_cus);
+    hipLaunchKernelGGL(density_lattice_kernel, dim3(grid), dim3(LAT_WAVES * 64), sizeof(float) * gpl::BLOB_FLOATS, S_(stream), a);
     return launch_status();
 }
 

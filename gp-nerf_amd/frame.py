@@ -621,3 +621,109 @@ def patch_order_of(idx, W, patch_w=4, patch_h=8):
     y, x = idx // W, idx % W
     key = ((y // patch_h) * ((W + patch_w - 1) // patch_w) + x // patch_w) * (patch_w * patch_h) + (y % patch_h) * patch_w + x % patch_w
     return idx[torch.argsort(key)].to(torch.int32)
+
+
+# ---- geometry mode of the inference renderer (demo_render.py:166-175,249-311,366-376: use_rgbhead False) ---------------------------
+MESH_PAD = 10                 # np.pad(cube, 10) (:370)
+
+
+def lattice_axis(lo, hi, step):
+    """torch.range(lo, hi + step, step) as demo_render.py:249-263 calls it, on the host: lo, hi float32 scalars (can_bounds entries),
+    step the float64 voxel size.  end = float32(hi) + float32(step), rounded to float32 (a float32 0-d tensor plus a Python/numpy
+    scalar); size = floor((end - lo) / step) + 1 and value i = lo + i * step, both in float64, the values rounded to float32."""
+    lo, step = np.float64(np.float32(lo)), np.float64(step)
+    end = np.float64(np.float32(np.float32(hi) + np.float32(step)))
+    n = int(np.floor((end - lo) / step)) + 1
+    return (lo + np.arange(max(n, 0), dtype=np.float64) * step).astype(np.float32)
+
+
+def mesh_box(frame, voxel_size, bounds_min, Rh, Th, threshold=0.1, host=None):
+    """can_bounds (demo_render.py:166-175) of a frame with its occupancy volume: min / max over the world points of the level-1 voxels
+    whose occupancy is above `threshold`, z widened by 0.05 (float32 arithmetic), as host float32 [2,3] -- the box's six values are
+    this call's one device-to-host read (they size the lattice).  gpnerf_select_pixels computes them; its pixel marks (of a one-pixel
+    image) are not used.  host: fetch_host(voxel_size, bounds_min, Rh, Th) done earlier, or None."""
+    lib = L.lib()
+    if not frame.c.occ:
+        frame.build_occupancy()
+    occ = frame.occ
+    dev = occ.device
+    host = host if host is not None else fetch_host(voxel_size, bounds_min, Rh, Th)
+    vox, bmin, rh, th = [np.ascontiguousarray(np.asarray(a, dtype=np.float32).ravel()) for a in host]
+    eye_pose = np.ascontiguousarray(np.eye(3, 4, dtype=np.float32).ravel())
+    eye_k = np.ascontiguousarray(np.eye(3, dtype=np.float32).ravel())
+    sel = torch.empty((1,), device=dev, dtype=torch.uint8)
+    mm = torch.empty((6,), device=dev, dtype=torch.int32)
+    D1, H1, W1 = occ.shape
+    p = lambda a: a.ctypes.data_as(L.FP)
+    L.check(lib.gpnerf_select_pixels(occ.data_ptr(), D1, H1, W1, float(threshold), p(vox), p(bmin), p(rh), p(th), p(eye_pose), p(eye_k),
+                                     1, 1, sel.data_ptr(), mm.data_ptr(), _stream_ptr(dev)), "gpnerf_select_pixels")
+    bits = mm.cpu().numpy()
+    bits = np.where(bits >= 0, bits, bits ^ 0x7FFFFFFF).astype(np.int32)
+    box = bits.view(np.float32).reshape(2, 3).copy()
+    if not np.all(box[0] <= box[1]):
+        raise L.GpnerfError(f"mesh extraction: no level-1 voxel has occupancy above {threshold} (the reference's min over no points fails too)")
+    box[0, 2] = np.float32(box[0, 2] - np.float32(0.05))
+    box[1, 2] = np.float32(box[1, 2] + np.float32(0.05))
+    return box
+
+
+def lattice_axes(box, voxel_size):
+    """The three lattice axes of demo_render.py:249-263 (float32 host arrays)."""
+    vs = np.asarray(voxel_size, dtype=np.float64).ravel()
+    return [lattice_axis(box[0, a], box[1, a], vs[a]) for a in range(3)]
+
+
+def density_lattice(frame, axes, neg_ray=False, pad=MESH_PAD):
+    """gpnerf_density_lattice: the padded alpha cube [X+2p, Y+2p, Z+2p] (float32, device) of the lattice `axes` (host float32 arrays,
+    lattice_axes()), and the device int64 count of kept (occupied) points."""
+    lib = L.lib()
+    if not frame.c.occ:
+        frame.build_occupancy()
+    if frame.c.head_blob_ref is None:
+        raise L.GpnerfError("density_lattice: the frame's head blob must be pack_head()'s tensor (it carries the reference-order image)")
+    dev = frame.occ.device
+    ax = [torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev, non_blocking=False) for a in axes]
+    dims = (C.c_int32 * 3)(*[len(a) for a in axes])
+    cube = torch.empty(tuple(len(a) + 2 * pad for a in axes), device=dev, dtype=torch.float32)
+    n_kept = torch.empty((1,), device=dev, dtype=torch.int64)
+    L.check(lib.gpnerf_density_lattice(C.byref(frame.c), ax[0].data_ptr(), ax[1].data_ptr(), ax[2].data_ptr(), dims, int(pad),
+                                       int(bool(neg_ray)), cube.data_ptr(), n_kept.data_ptr(), _stream_ptr(dev)), "gpnerf_density_lattice")
+    # (the axis tensors may go out of scope here: the caching allocator hands their memory out again only in stream order, after
+    # the launch that reads them)
+    return cube, n_kept
+
+
+def marching_cubes(cube, iso=1.0 / 50.0):
+    """gpnerf_mesh_count + gpnerf_mesh_emit on a device float32 cube [X,Y,Z]: (vertices float32 [nv,3], faces int32 [nf,3]), device.
+    The two counts are the call's one device-to-host read (they size the outputs).  The workspace (8 bytes per cube point) is
+    allocated per call from torch's caching allocator and released when the call returns."""
+    lib = L.lib()
+    _require_gpu(cube, "cube")
+    if cube.dim() != 3 or cube.dtype != torch.float32 or not cube.is_contiguous():
+        raise L.GpnerfError("marching_cubes: expected a contiguous float32 [X,Y,Z] cube")
+    dev = cube.device
+    dims = (C.c_int32 * 3)(*cube.shape)
+    nbytes = int(lib.gpnerf_mesh_workspace_bytes(dims))
+    if nbytes <= 0:
+        raise L.GpnerfError(f"marching_cubes: dims {tuple(cube.shape)} refused (each >= 2, at most 2^28 points)")
+    ws = torch.empty((nbytes,), device=dev, dtype=torch.uint8)
+    counts = torch.empty((2,), device=dev, dtype=torch.int64)
+    st = _stream_ptr(dev)
+    L.check(lib.gpnerf_mesh_count(cube.data_ptr(), dims, float(iso), ws.data_ptr(), ws.numel(), counts.data_ptr(), st), "gpnerf_mesh_count")
+    nv, nf = (int(v) for v in counts.cpu().tolist())
+    verts = torch.empty((nv, 3), device=dev, dtype=torch.float32)
+    faces = torch.empty((nf, 3), device=dev, dtype=torch.int32)
+    L.check(lib.gpnerf_mesh_emit(cube.data_ptr(), dims, float(iso), ws.data_ptr(), ws.numel(), nv, nf,
+                                 verts.data_ptr() if nv else None, faces.data_ptr() if nf else None, st), "gpnerf_mesh_emit")
+    return verts, faces
+
+
+def extract_mesh(frame, voxel_size, bounds_min, Rh, Th, neg_ray=False, iso=1.0 / 50.0, host=None):
+    """The geometry mode of demo_render.py's render_rays (:166-175, 249-311, 366-376) on the device: the box of the occupied voxels,
+    the lattice, the alpha cube and its marching-cubes mesh.  Two host reads: the box (6 values) and the mesh counts (2).
+    Returns {"cube" (device [X+20,Y+20,Z+20]), "vertices", "faces" (device), "axes", "can_bounds", "n_kept" (device int64)}."""
+    box = mesh_box(frame, voxel_size, bounds_min, Rh, Th, host=host)
+    axes = lattice_axes(box, host[0] if host is not None else voxel_size)
+    cube, n_kept = density_lattice(frame, axes, neg_ray=neg_ray)
+    verts, faces = marching_cubes(cube, iso)
+    return {"cube": cube, "vertices": verts, "faces": faces, "axes": axes, "can_bounds": box, "n_kept": n_kept}

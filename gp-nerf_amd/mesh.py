@@ -1,0 +1,117 @@
+"""The mesh of the inference renderer's geometry mode (libs/renders/demo_render.py:366-376) and the marching-cubes case tables.
+
+`Mesh` stands in for the `trimesh.Trimesh` the reference returns: `.vertices` (float64 [nv,3], index units of the padded alpha
+cube, as mcubes returns them), `.faces` (int64 [nf,3]) and `.export(path)`, the one method its mesh evaluator calls
+(libs/evaluators/if_nerf_mesh.py).  trimesh is not a dependency: `export` writes a binary little-endian PLY itself.
+
+`case_tables()` is the derivation of the 256-case tables compiled into csrc/gpnerf_mesh.hip (tests hold the two equal):
+  * corners and edges numbered as in the classic tables (Lorensen & Cline; Bourke's listing): corner c at offset
+    (c in {1,2,5,6}, c in {2,3,6,7}, c >= 4) from the cell's lowest corner; edges 0-3 on the z = 0 face, 4-7 on z = 1, 8-11 along z;
+  * a corner's bit is set when its value is BELOW the iso value;
+  * every cube face is cut on its own: a segment joins the crossing on the edge where the face's boundary (counter-clockwise seen
+    from outside the cell) leaves a run of set corners with the crossing where it entered that run; on a face whose two diagonals
+    disagree (an ambiguous face) the two set corners are therefore cut off separately.  Two cells sharing a face cut it alike, so the surface
+    has no cracks;
+  * the directed segments of a case chain into loops (edge order: a loop starts at its lowest free edge), and a loop of n
+    crossings is fanned into n - 2 triangles from its first crossing, wound so that the normal points toward the set corners,
+    i.e. toward lower values.
+These are NOT the published triangle lists: those cannot be compared with here, and neither can PyMCubes' tie rule.
+"""
+import numpy as np
+
+# corner c -> (dx, dy, dz)
+CORNERS = [(0, 0, 0), (1, 0, 0), (1, 1, 0), (0, 1, 0), (0, 0, 1), (1, 0, 1), (1, 1, 1), (0, 1, 1)]
+# edge e -> (corner a, corner b)
+EDGES = [(0, 1), (1, 2), (2, 3), (3, 0), (4, 5), (5, 6), (6, 7), (7, 4), (0, 4), (1, 5), (2, 6), (3, 7)]
+# faces as corner cycles, counter-clockwise seen from outside the cell
+FACES = [(0, 3, 2, 1), (4, 5, 6, 7), (0, 1, 5, 4), (3, 7, 6, 2), (0, 4, 7, 3), (1, 2, 6, 5)]
+MAX_TRIS = 5
+ISO_REFERENCE = 1.0 / 50.0   # demo_render.py:372, a literal (cfg.test.mesh_th is not read there)
+
+
+def edge_owner(e):
+    """(dx, dy, dz, axis) of edge e: the lattice point at its lower end and the axis it runs along (0 = x, 1 = y, 2 = z)."""
+    a, b = EDGES[e]
+    pa, pb = CORNERS[a], CORNERS[b]
+    lo = tuple(min(u, v) for u, v in zip(pa, pb))
+    axis = [i for i in range(3) if pa[i] != pb[i]][0]
+    return lo + (axis,)
+
+
+def _edge_of(a, b):
+    for e, (u, v) in enumerate(EDGES):
+        if {u, v} == {a, b}:
+            return e
+    raise KeyError((a, b))
+
+
+def case_tables():
+    """(edge_mask [256] uint16, tri_count [256] uint8, tri_table [256][3 * MAX_TRIS] int8 padded with -1)."""
+    edge_mask = np.zeros(256, np.uint16)
+    tri_count = np.zeros(256, np.uint8)
+    tri_table = -np.ones((256, 3 * MAX_TRIS), np.int8)
+    for case in range(256):
+        inside = [(case >> c) & 1 for c in range(8)]
+        for e, (a, b) in enumerate(EDGES):
+            if inside[a] != inside[b]:
+                edge_mask[case] |= 1 << e
+        nxt = {}
+        for f in FACES:
+            for k in range(4):
+                c0, c1 = f[k], f[(k + 1) % 4]
+                if inside[c0] and not inside[c1]:          # the boundary leaves a run of set corners: the segment starts here
+                    j = (k + 3) % 4
+                    while True:                            # ... and ends where the boundary entered that run
+                        d0, d1 = f[j], f[(j + 1) % 4]
+                        if not inside[d0] and inside[d1]:
+                            break
+                        j = (j + 3) % 4
+                    nxt[_edge_of(c0, c1)] = _edge_of(d0, d1)
+        tris = []
+        todo = set(nxt)
+        while todo:
+            start = min(todo)
+            loop = [start]
+            todo.discard(start)
+            e = nxt[start]
+            while e != start:
+                loop.append(e)
+                todo.discard(e)
+                e = nxt[e]
+            for i in range(1, len(loop) - 1):
+                tris.append((loop[0], loop[i], loop[i + 1]))
+        assert len(tris) <= MAX_TRIS, (case, tris)
+        tri_count[case] = len(tris)
+        for i, t in enumerate(tris):
+            tri_table[case, 3 * i:3 * i + 3] = t
+    return edge_mask, tri_count, tri_table
+
+
+class Mesh:
+    """vertices float64 [nv,3], faces int64 [nf,3] (trimesh's names); export() writes a binary little-endian PLY."""
+
+    def __init__(self, vertices, faces):
+        self.vertices = np.ascontiguousarray(vertices, dtype=np.float64).reshape(-1, 3)
+        self.faces = np.ascontiguousarray(faces, dtype=np.int64).reshape(-1, 3)
+
+    def __repr__(self):
+        return f"Mesh(vertices={len(self.vertices)}, faces={len(self.faces)})"
+
+    def export(self, file_obj, file_type="ply"):
+        """Binary little-endian PLY: float64 x y z per vertex (the array as it is), one uint8-counted int32 index list per face."""
+        if file_type != "ply":
+            raise ValueError("only PLY is written (trimesh is not a dependency)")
+        if len(self.faces) and (self.faces.min() < 0 or self.faces.max() >= len(self.vertices) or len(self.vertices) >= 2 ** 31):
+            raise ValueError("face indices out of range for a PLY int32 list")
+        head = ("ply\nformat binary_little_endian 1.0\n"
+                f"element vertex {len(self.vertices)}\nproperty double x\nproperty double y\nproperty double z\n"
+                f"element face {len(self.faces)}\nproperty list uchar int vertex_indices\nend_header\n").encode("ascii")
+        faces = np.empty(len(self.faces), dtype=[("n", "u1"), ("i", "<i4", (3,))])
+        faces["n"] = 3
+        faces["i"] = self.faces
+        body = self.vertices.astype("<f8").tobytes() + faces.tobytes()
+        if hasattr(file_obj, "write"):
+            file_obj.write(head + body)
+        else:
+            with open(file_obj, "wb") as f:
+                f.write(head + body)

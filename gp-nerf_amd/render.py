@@ -28,6 +28,7 @@ import torch.nn as nn
 from . import _lib as L
 from . import encoder as E_
 from . import frame as F_
+from . import mesh as M_
 from . import parallel as P_
 
 
@@ -201,7 +202,10 @@ class Renderer(nn.Module):
 
     def render_progressive(self, batch):
         """libs/renders/demo_render.py:429-498 + :96-376: returns `pred_img` [H,W,3] (float64 numpy, background 0),
-        `mask_at_box`, `rgb_map`, `time_slots`, `rtime`, `etime` (libs/evaluators/if_nerf.py:50-56 reads pred_img[mask])."""
+        `mask_at_box`, `rgb_map`, `time_slots`, `rtime`, `etime` (libs/evaluators/if_nerf.py:50-56 reads pred_img[mask]).
+        With nerfhead.use_rgbhead False: the geometry mode instead (render_mesh)."""
+        if not self.nerfhead.use_rgbhead:
+            return self.render_mesh(batch)
         dev = batch["src_imgs"].device
         H, W = batch["src_imgs"].shape[-2:]
         torch.cuda.synchronize(dev)
@@ -263,6 +267,39 @@ class Renderer(nn.Module):
                                "bf_sigma": 0.0, "sigma_f": t3 - t2, "bf_rgb": 0.0, "rgb_f": 0.0},
                 # etime = the encoder alone (its device time), rtime = everything else of the call, as demo_render.py:441-446,494-497
                 # keeps its two clocks (libs/trainers/BaseTrainer.py:276 sums rtime into the reported render time)
+                "etime": etime, "rtime": max(0.0, (t4 - te) - etime)}
+
+    def render_mesh(self, batch):
+        """The inference renderer's geometry mode (demo_render.py:166-175, 249-311, 366-376, use_rgbhead False) on the device: returns
+        `mesh` (mesh.Mesh: vertices in index units of the padded cube, as mcubes gives them), `cube` (the padded alpha cube,
+        float32 numpy), `time_slots`, `etime`, `rtime`.  The iso value is the reference's literal 1 / 50 (cfg.test.mesh_th is not
+        read there either).  Host reads: the frame's constants before the encoder, the box (6 values), the mesh counts (2)."""
+        dev = batch["src_imgs"].device
+        torch.cuda.synchronize(dev)
+        te = time.time()
+        fetched = F_.fetch_host(batch["src_Ks"][0], batch["src_poses"][0], batch["Rh"][0], batch["Th"][0], batch["bounds"][0, 0],
+                                self.voxel_size, batch["out_sh"][0], self.voxel_size, batch["bounds"][0, 0], batch["Rh"][0], batch["Th"][0])
+        consts, box_host = fetched[:7], fetched[7:]
+        prepared = self.prepare_builder_inputs(batch, consts)
+        self.nerfhead.head_blob(dev)
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
+        ev[0].record()
+        featmaps = self.encode(batch)
+        ev[1].record()
+        frame = self.build_frame(batch, featmaps, consts, prepared)
+        frame.build_occupancy()
+        ev[2].record()
+        m = F_.extract_mesh(frame, self.voxel_size, batch["bounds"][0, 0], batch["Rh"][0], batch["Th"][0], neg_ray=self._neg_ray(batch),
+                            iso=M_.ISO_REFERENCE, host=box_host)
+        ev[3].record()
+        cube = m["cube"].cpu().numpy()
+        mesh = M_.Mesh(m["vertices"].cpu().numpy(), m["faces"].cpu().numpy())
+        t4 = time.time()
+        etime = ev[0].elapsed_time(ev[1]) * 1e-3
+        t_frame, t_mesh = ev[1].elapsed_time(ev[2]) * 1e-3, ev[2].elapsed_time(ev[3]) * 1e-3
+        return {"mesh": mesh, "cube": cube,
+                "time_slots": {"frame": t_frame, "mesh": t_mesh, "bc_time": 0.0, "sigma_c": 0.0, "bc_attn": 0.0, "sigma_attn": 0.0,
+                               "sp_encode": t_frame, "bf_sigma": 0.0, "sigma_f": t_mesh},
                 "etime": etime, "rtime": max(0.0, (t4 - te) - etime)}
 
     # ---- the hot path ---------------------------------------------------------------------------------

@@ -309,6 +309,46 @@ int gpnerf_make_rays_demo(int32_t H, int32_t W, const float* Kinv, const float* 
                           const int32_t* world_minmax_dev, int32_t neg_ray, const uint8_t* pixel_sel, float* rays, uint8_t* hit,
                           void* stream);
 
+/* ---- geometry mode of the inference renderer (libs/renders/demo_render.py:249-311,366-376: nerfhead.use_rgbhead False) ----
+ *
+ * gpnerf_density_lattice: alpha = 1 - exp(-sigma) of the density branch on the lattice axis_x (x) axis_y (x) axis_z (meshgrid 'ij':
+ * x slowest), written into cube, device float [X + 2 pad][Y + 2 pad][Z + 2 pad] (X, Y, Z = dims, host int32[3]), with pad zeros on
+ * every side (np.pad(cube, 10) at :370).  A point is evaluated iff the occupancy volume frame->occ interpolates to > 0 at its grid
+ * coordinates (pts_to_can_pts and the demo's get_grid_coords with its literal / 0.005, :270-283; the cull of
+ * GPNERF_FLAG_OCC_CULL); a culled point's alpha is 0.  A kept point's sigma is the reference-order form's (GPNERF_FLAG_REF_ORDER):
+ * the four volume levels, the sigma feature layer, Projector.compute of the three views under neg_ray, mean / variance,
+ * rgbhead.out_geometry_fc, 0 where no view is valid -- the fused kernel's step without its colour branch.  Every element of the
+ * cube is written (the caller does not clear it).  axis_*: device float32 lattice coordinates (frame.lattice_axis() makes them as
+ * torch.range does); n_kept: device int64 or NULL, receives the number of kept points.  Needs frame->occ, frame->head_blob_ref,
+ * the volumes and the image half of the frame. */
+int gpnerf_density_lattice(const GpnerfFrame* frame, const float* axis_x, const float* axis_y, const float* axis_z, const int32_t* dims,
+                           int32_t pad, int32_t neg_ray, float* cube, int64_t* n_kept, void* stream);
+
+/* Marching cubes over a float32 cube [X][Y][Z] (dims: host int32[3], each >= 2, X * Y * Z <= 2^28; x slowest), iso value iso
+ * (the reference's literal 1 / 50 at :372).  Two calls with the same cube, dims, iso and workspace:
+ *   gpnerf_mesh_count: counts: device int64[2] <- {n_vertices, n_triangles}; the workspace (gpnerf_mesh_workspace_bytes(dims)
+ *     bytes, device) keeps the offsets for
+ *   gpnerf_mesh_emit: vertices: device float [n][3], faces: device int32 [m][3]; only the first max_vertices / max_triangles
+ *     rows are written (the caller sizes them from the counts).
+ * Output, a function of the cube and iso alone (no atomics; independent of launch geometry):
+ *   - corner bit set where value < iso; case index = sum of bit(corner c) << c, corners c at offset (c in {1,2,5,6},
+ *     c in {2,3,6,7}, c >= 4) from the cell's lowest corner, edges numbered as in the classic tables (0-3 on z = 0, 4-7 on z = 1,
+ *     8-11 along z);
+ *   - one vertex per crossed lattice edge (an edge whose two ends disagree), ordered by (linear index of the edge's lower end,
+ *     axis x < y < z); position = lower end + t along the axis, t = (iso - f0) / (f1 - f0) in float32, lower end f0, upper f1;
+ *     in index units of the cube (as mcubes returns them);
+ *   - triangles ordered by (linear index of the cell's lowest corner, order in the case table), wound so that the normal
+ *     (v1 - v0) x (v2 - v0) points toward lower values;
+ *   - the triangle lists (gp-nerf_amd/mesh.py: case_tables) cut every cube face on its own, so that two cells agree on the face they
+ *     share: on an ambiguous face the two set corners are cut off separately.  They are NOT the published triangle lists, and
+ *     whether PyMCubes' tables and tie rule give the same mesh has not been checked (mcubes is not available to compare with).
+ * gpnerf_mesh_workspace_bytes returns 0 for dims it refuses. */
+int64_t gpnerf_mesh_workspace_bytes(const int32_t* dims);
+int gpnerf_mesh_count(const float* cube, const int32_t* dims, float iso, void* workspace, size_t workspace_bytes, int64_t* counts,
+                      void* stream);
+int gpnerf_mesh_emit(const float* cube, const int32_t* dims, float iso, const void* workspace, size_t workspace_bytes,
+                     int64_t max_vertices, int64_t max_triangles, float* vertices, int32_t* faces, void* stream);
+
 /* ---- per-frame sparse convolution pyramid (gpnerf_volume.hip), replacing the external spconv v1.2.1 calls of
  * libs/nerfheads/networks/SparseConvNet.py:22-111 (SubMConv3d / SparseConv3d + BatchNorm1d + ReLU, .dense()).
  * A sparse tensor is: features [M][C] fp32, coords [M][3] int32 (d,h,w), and a dense int32 index grid [D][H][W]
