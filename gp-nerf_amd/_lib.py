@@ -8,8 +8,8 @@ import ctypes as C
 import os
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-# The product loads the in-tree build, always.  GPNERF_LIB_PATH (a differently built library for the A/B measurements of
-# tools/) is honoured only together with GPNERF_DEBUG=1, the switch that also enables the launcher's experiment knobs.
+# The product loads the in-tree build, always.  GPNERF_LIB_PATH (a differently built library: the A/B measurements of
+# tools/ab_libs.sh, the stamps and wavetimes builds of csrc/diag/) is honoured only together with GPNERF_DEBUG=1.
 _DEBUG = os.environ.get("GPNERF_DEBUG", "0") == "1"
 LIB_PATH = (os.environ.get("GPNERF_LIB_PATH") if _DEBUG else None) or os.path.join(HERE, "csrc", "libgpnerf_hip.so")
 

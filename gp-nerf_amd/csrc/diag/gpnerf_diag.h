@@ -1,10 +1,8 @@
 // gpnerf_diag.h, LAB version (csrc/diag/): what the hook points of the kernels expand to in the diagnostic libraries that
-// csrc/diag/Makefile builds (libgpnerf_hip_diag.so, _stamps.so, _wavetimes.so).  Never on the product's include path; the
+// csrc/diag/Makefile builds (libgpnerf_hip_stamps.so, _wavetimes.so).  Never on the product's include path; the
 // product's (empty) version is csrc/nodiag/gpnerf_diag.h.  tools/ load these libraries with GPNERF_DEBUG=1 GPNERF_LIB_PATH=...
 //   -DGPNERF_STAMPS      per-phase cycle shares of the fused kernel (tools/stamps.py)
 //   -DGPNERF_WAVETIMES   per-wavefront entry / staged / first-step / exit times (tools/wave_times.py)
-//   (always)             launcher experiment knobs from the environment, clamped: GPNERF_WAVES, GPNERF_SPLIT, GPNERF_QSPLIT,
-//                        GPNERF_CHAIN_*, GPNERF_QUEUE_CHUNK, GPNERF_CONV_*, GPNERF_ATT_* ... (tools/probes/*.sh)
 #pragma once
 #ifndef DEV
 #define DEV __device__ __forceinline__
@@ -51,18 +49,6 @@ __device__ unsigned long long g_wt[16384 * 4];
 #define WT(i) ((void)0)
 #define WT_COUNT() ((void)0)
 #endif
-// Experiment knobs (tools/*.sh A/B runs): read ONLY when GPNERF_DEBUG=1 is set, and clamped to [lo, hi]
-inline const char* dbg_env(const char* name) {
-    static int on = -1;
-    if (on < 0) { const char* d = getenv("GPNERF_DEBUG"); on = (d && d[0] == '1') ? 1 : 0; }
-    return on ? getenv(name) : nullptr;
-}
-inline int dbg_int(const char* name, int dflt, int lo, int hi) {
-    const char* e = dbg_env(name);
-    if (!e) return dflt;
-    const int v = atoi(e);
-    return v < lo ? lo : (v > hi ? hi : v);
-}
 // the diagnostic libraries' extra exports (expanded inside gpnerf_kernels.hip's extern "C" block, after the anonymous namespace)
 #if defined(GPNERF_WAVETIMES) && defined(GPNERF_STAMPS)
 #error "one diagnostic at a time"

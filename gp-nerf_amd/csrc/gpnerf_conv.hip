@@ -1239,13 +1239,7 @@ int launch_conv(const ConvArgs& a, int N, void* stream) {
 // rows per wave of the 3x3 kernel for an (Ho x Wo) output: images of at most sixteen 8-row tiles (64 x 64 and smaller) take 4-row tiles (threshold swept: 8: 1.165, 16: 1.147, 64: 1.203 ms per frame).
 // A function of the output size ALONE, so that gpnerf_conv_out_tiles() can tell the caller how many tile rows the statistics have.
 int conv3x3_rows(int ho, int wo) {
-    static int f_rows = -1, f_max = -1;
-    if (f_rows < 0) {                      // experiment knobs (gpnerf_diag.h: the product takes the defaults)
-        f_rows = dbg_int("GPNERF_CONV_ROWS", 0, 0, 2);
-        f_max = dbg_int("GPNERF_CONV_ROWS_MAXTILES", 16, 0, 1 << 20);
-    }
-    if (f_rows) return f_rows;
-    return ((ho + 7) / 8) * ((wo + TW - 1) / TW) <= f_max && ho > 4 ? 1 : 2;
+    return ((ho + 7) / 8) * ((wo + TW - 1) / TW) <= 16 && ho > 4 ? 1 : 2;
 }
 
 template <int COT, int RW, int STRIDE = 1, int KSPLIT = 1, bool CAT = false, bool EXACT = false>
@@ -1271,20 +1265,14 @@ int launch_conv3x3_as(const ConvArgs& a, int N, int tiles, void* stream) {
 int launch_conv3x3(const ConvArgs& a, int N, void* stream) {
     const int rw = conv3x3_rows(a.Ho, a.Wo), th = tile_rows(rw);
     const int tiles = ((a.Ho + th - 1) / th) * ((a.Wo + TW - 1) / TW);
-    static int f_cot = -1;
-    if (f_cot < 0) f_cot = dbg_int("GPNERF_CONV_COT", 0, 0, 2);      // experiment knob (gpnerf_diag.h)
     // one 32-channel output tile per workgroup everywhere: with the weights in registers and 54 KB of LDS two workgroups share a CU,
-    // and one's staging runs under the other's MFMAs (two tiles per workgroup, GPNERF_CONV_COT=2: 1.19 -> 1.38 ms per frame)
-    const int cot = (f_cot == 2 && a.CT % 2 == 0) ? 2 : 1;
+    // and one's staging runs under the other's MFMAs (two tiles per workgroup: 1.19 -> 1.38 ms per frame)
     if (a.x2) return rw == 1 ? launch_conv3x3_as<1, 1, 1, 1, true>(a, N, tiles, stream) : launch_conv3x3_as<1, 2, 1, 1, true>(a, N, tiles, stream);
     // a grid of at most one workgroup per CU (the 32 x 32 stage: 192): the channel blocks are split over the two halves of an
     // eight-wave workgroup (encoder 1.097 -> 1.030 ms; at <= 400 workgroups, which takes in the 64 x 64 stage: 1.087)
-    static int f_ksplit = -1;
-    if (f_ksplit < 0) f_ksplit = dbg_int("GPNERF_CONV_KSPLIT_MAXWG", 256, 0, 1 << 20);     // experiment knob (gpnerf_diag.h)
-    if (cot == 1 && rw == 1 && a.CB % 2 == 0 && a.CB >= 4 && (long)tiles * N * a.CT <= f_ksplit)
+    if (rw == 1 && a.CB % 2 == 0 && a.CB >= 4 && (long)tiles * N * a.CT <= 256)
         return launch_conv3x3_as<1, 1, 1, 2>(a, N, tiles, stream);
-    if (rw == 1) return cot == 2 ? launch_conv3x3_as<2, 1>(a, N, tiles, stream) : launch_conv3x3_as<1, 1>(a, N, tiles, stream);
-    return cot == 2 ? launch_conv3x3_as<2, 2>(a, N, tiles, stream) : launch_conv3x3_as<1, 2>(a, N, tiles, stream);
+    return rw == 1 ? launch_conv3x3_as<1, 1>(a, N, tiles, stream) : launch_conv3x3_as<1, 2>(a, N, tiles, stream);
 }
 
 // 3x3 stride 2 (the entry of every residual stage): the same kernel on 4-row output tiles, whose input patch is 9 x 65 pixels

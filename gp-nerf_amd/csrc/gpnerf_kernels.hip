@@ -32,7 +32,7 @@ constexpr int NV = GPNERF_VIEWS;
 constexpr int RAYS_PER_WAVE = 32;
 constexpr float LOG2E = 1.44269504088896340736f;
 
-// The lab's hook points (per-phase cycle stamps, per-wavefront time stamps, launcher experiment knobs): EMPTY in the product --
+// The lab's hook points (per-phase cycle stamps, per-wavefront time stamps): EMPTY in the product --
 // this resolves to csrc/nodiag/gpnerf_diag.h on the product's include path; csrc/diag/Makefile builds the diagnostic libraries
 // with csrc/diag/gpnerf_diag.h instead (never loaded by the product).
 #include "gpnerf_diag.h"
@@ -1269,10 +1269,8 @@ struct KArgs {            // the fused kernel's only argument (see render_fused_
     // chained sample segments (early termination, render_fused_kernel<., true>): this launch walks samples
     // [seg * chain, (seg + 1) * chain) of the rays listed in `list_in` (nullptr: every ray, segment 0), 32 list entries per
     // wavefront, and appends the rays that are neither finished nor opaque to `list_out` for the next launch
-    int chain, seg, wave_cap;
+    int chain, seg;
     int k_begin, k_end;       // chained form: the launch's sample range [k_begin, k_end) (segments need not be equally long, chain_schedule())
-    int stagger;              // experiment: wavefronts start up to this many x 1.7 us late, scattered over the chip
-    int seg_major;            // split > 1 on the tile queue: units ordered segment-major (1) or tile-major (0)
     int skip;                 // reference-order form: bit 0 = empty-space exit of the sigma feature layer, bit 1 = zero-density exit of the colour branch
     int chunk;                // tiles per chunk of the XCD queues (queue_tile())
     int tail_p;               // chain_plan(): samples per step of the units the last whole round is cut into
@@ -1297,7 +1295,6 @@ struct KArgs {            // the fused kernel's only argument (see render_fused_
     unsigned* gd_ctrl;
     unsigned* gd_flag;        // unified form: gd_flag[u] = 1 once unit u's 32 entries are written (zero at launch)
     int gd_waves;             // unified form: wavefronts of the launch (every one reports to GD_DONE when it has listed its last entry)
-    int uni_budget;           // unified form: units a wavefront may evaluate between two tiles
     uint4* gd_ent;
     f32x4* gd_rgbw;
     int* gd_cnt;
@@ -2127,8 +2124,8 @@ DEV bool render_tile(float* lds, const int lane, const long tile, const int seg,
 // 8-wave workgroup resident per CU a static grid holds the CU until its slowest tile is done -- the queue hands the next
 // tile to whichever wave is free.  Static launches (one unit per wave, XCD-aware remap) remain for frames smaller than
 // one round and for the sample-split geometry.
-// Unified form (render_fused_kernel<., false, false, true, true, true>): the launch's wavefronts evaluate the list themselves,
-// between tiles and when the tile queue has nothing left for them.  `pending` = the unit this wavefront holds a ticket for (-1:
+// Unified form (render_fused_kernel<., false, false, true, true, true>): the launch's wavefronts evaluate the list themselves
+// once the tile queue has nothing left for them.  `pending` = the unit this wavefront holds a ticket for (-1:
 // none).  Takes tickets UNI_BATCH at a time, evaluates the next unit if its flag is up, returns whether it did.
 // One 32-entry unit of the colour list: lane i (both halves) evaluates entry i exactly as render_tile's colour pass does -- sample_point
 // from the ray's row, gather_views, mean / variance, mlp_colour: same operands, same order, same bits -- and writes (r, g, b, w) where
@@ -2218,13 +2215,6 @@ render_fused_kernel(const KArgs ka) {
     int qx = home, dry = 0;
     int samples_per_step = 1;                   // chained form: render_tile's P and list offset of the current unit
     long entry_base = 0;
-    long uni_pending = 0, uni_pending_end = 0;  // unified form: the units this wavefront holds tickets for
-    int uni_left = 0;
-    bool uni_drain = false;
-    if (ka.stagger) {
-        const int u = (int)((blockIdx.x * 8u + (unsigned)wave) * 2654435761u >> 27);        // 0..31, scattered over the chip
-        for (int i = 0; i < ((u * ka.stagger) >> 5); ++i) __builtin_amdgcn_s_sleep(64);
-    }
     for (;;) {
         typedef const __attribute__((address_space(4))) KArgs* kargs_ptr;
         kargs_ptr kq = (kargs_ptr)__builtin_amdgcn_kernarg_segment_ptr();
@@ -2243,14 +2233,9 @@ render_fused_kernel(const KArgs ka) {
             long n_tiles = (kq->n_rays + RAYS_PER_WAVE - 1) / RAYS_PER_WAVE;
             ChainPlan plan;
             if constexpr (CHAIN) { plan = chain_plan(kq); n_tiles = plan.bulk_tiles + plan.rem_tiles; }
-            // plain form with kq->split > 1: the queue's units are (tile, sample segment) pairs, tile-major -- a frame of one to two
-            // rounds of wavefronts then ends in short units instead of whole 64-step tiles (see gpnerf_render_fused)
-            const int usplit = CHAIN ? 1 : kq->split;
-            const long tiles_per_seg = n_tiles;
-            n_tiles *= usplit;
             // fewer tiles than waves: deal them evenly, so that every CU runs the same few waves (each then steps faster) rather
             // than the first workgroups to arrive running eight and the rest none
-            const long share = kq->wave_cap ? (long)kq->wave_cap : (n_tiles + gridDim.x - 1) / gridDim.x;
+            const long share = (n_tiles + gridDim.x - 1) / gridDim.x;
             if (wave >= share) { if constexpr (UNI) { have_tile = false; dry = 8; } else return; }
             STAMP_T0();
             if (have_tile) {
@@ -2263,10 +2248,6 @@ render_fused_kernel(const KArgs ka) {
                 have_tile = false;
             } else
             tile = queue_tile(kq->chunk, qx, t);
-            }
-            if (usplit > 1) {
-                if (kq->seg_major) { seg = (int)(tile / tiles_per_seg); tile -= (long)seg * tiles_per_seg; }      // all tiles' first segment, then the second ...
-                else { seg = (int)(tile % usplit); tile /= usplit; }
             }
             if constexpr (CULL) { if (kq->tile_order) tile = kq->tile_order[tile]; }
             if constexpr (CHAIN) {
@@ -2294,26 +2275,23 @@ render_fused_kernel(const KArgs ka) {
         WT_COUNT();
         }
         if constexpr (UNI) {
-            // between tiles: what the list holds beyond the tickets, at most uni_budget units; with no tile left (drain): units until
-            // every wavefront has listed its last entry -- render_tile flushes at every tile's end -- and this one's ticket lies
-            // beyond the list.  ONE site for both (the colour branch's code is 28 KB of the instruction cache).
-            uni_left = kq->uni_budget;
-            if (!have_tile && !uni_drain) {
+            // no tile left: report done once, then drain -- evaluate units until every wavefront has listed its last entry
+            // (render_tile flushes at every tile's end) and this one's ticket lies beyond the list.  ONE consume_unit site (the
+            // colour branch's code is 28 KB of the instruction cache).
+            if (!have_tile) {
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                 wave_add(kq->gd_ctrl + GD_DONE, 1u, lane);
-                uni_drain = true;
-            }
-            for (;;) {
-                if (!uni_drain && uni_left <= 0) break;
-                if (consume_unit<F>(lds, lane, uni_pending, uni_pending_end)) { --uni_left; continue; }
-                if (!uni_drain) break;
-                typedef const __attribute__((address_space(4))) KArgs* kargs_ptr;
-                kargs_ptr kd = (kargs_ptr)__builtin_amdgcn_kernarg_segment_ptr();
-                asm volatile("" : "+s"(kd));
-                if (wave_load(kd->gd_ctrl + GD_DONE, lane) >= (unsigned)kd->gd_waves) {
-                    if (uni_pending >= (long)wave_load(kd->gd_ctrl + GD_COUNT, lane)) return;     // (every ticket it holds lies beyond the list)
+                long uni_pending = 0, uni_pending_end = 0;      // the units this wavefront holds tickets for
+                for (;;) {
+                    if (consume_unit<F>(lds, lane, uni_pending, uni_pending_end)) continue;
+                    typedef const __attribute__((address_space(4))) KArgs* kargs_ptr;
+                    kargs_ptr kd = (kargs_ptr)__builtin_amdgcn_kernarg_segment_ptr();
+                    asm volatile("" : "+s"(kd));
+                    if (wave_load(kd->gd_ctrl + GD_DONE, lane) >= (unsigned)kd->gd_waves) {
+                        if (uni_pending >= (long)wave_load(kd->gd_ctrl + GD_COUNT, lane)) return;     // (every ticket it holds lies beyond the list)
+                    }
+                    __builtin_amdgcn_s_sleep(32);
                 }
-                __builtin_amdgcn_s_sleep(32);
             }
         }
     }
@@ -3135,7 +3113,7 @@ void pack_layer_ref(int L, const float* W, const float* b, int n_out, int n_in, 
 // waves share its SIMD (measured: ~86k cycles per 32-sample step with one wave per SIMD, ~134k with two), and a work unit
 // (32 rays x S samples) is long, so a grid that is not many times 256 workgroups quantises badly.  Choose the waves per
 // workgroup and, when the caller lends a workspace, how many waves share the samples of one tile (split), minimising
-// rounds x step time x samples per unit.  GPNERF_WAVES / GPNERF_SPLIT override (diagnostics).
+// rounds x step time x samples per unit.
 constexpr int GPNERF_MAX_SPLIT = 8;     // waves that may share one tile's samples
 constexpr size_t QUEUE_BYTES = 256;     // head of the workspace: 8 tile-queue counters (one per XCD), padded
 // frame-level deferral (colour_units_kernel): per launch slot its entry count, and room for an entry and a result per SAMPLE (a
@@ -3154,8 +3132,6 @@ size_t gdef_bytes(int64_t n_rays, int32_t n_samples) {
 // Early termination walks the samples in segments of chain_len(), one launch per segment over the rays still alive (see
 // gpnerf_render_fused); the workspace then holds a control block (per segment: 8 queue counters + the length of its output
 // list), two ray lists (written and read alternately) and 16 floats of parked state per ray.
-// Experiment knobs (dbg_int / dbg_env, tools/*.sh A/B runs): hook points of gpnerf_diag.h.  The product's version returns the
-// default, always -- it has no getenv; the diagnostic libraries of csrc/diag/ read the environment under GPNERF_DEBUG=1, clamped.
 // One launch of the fused kernel: which arithmetic (`sel`), whether the colour branch is deferred sample by sample (render_tile), and
 // the sample loop (chained segments / culled) as template arguments.  Dynamic LDS = the form's head image (+ the split form's guard
 // slots) + the wavefronts' colour queues.
@@ -3173,8 +3149,6 @@ enum { SEL_REF = 0, SEL_FOLD = 1, SEL_SPLIT = 2, SEL_GUARD = 3 };
 // -- so the instance stays inferred; the class is measured.)  Since round 6 every fragment that becomes an MFMA operand passes
 // through settle_operand(), which carries the wait state itself, and tools/isa_mfma_hazards.py fails the CPU suite on any
 // inline-asm producer closer to its MFMA than the measured requirement (tests/test_abi.py).
-constexpr bool SPLIT_DEFERS = true;
-template <int FORM> constexpr bool form_defers() { return SPLIT_DEFERS || (FORM != FORM_SPLIT && FORM != FORM_SPLIT_GUARD); }
 template <int FORM, bool CHAIN, bool CULL>
 void launch_form(bool deferred, dim3 grid, dim3 block, size_t lds, hipStream_t stream, const KArgs& ka) {
     if constexpr ((FORM == FORM_F32 || FORM == FORM_F32_FOLD) && !CULL) {
@@ -3185,9 +3159,7 @@ void launch_form(bool deferred, dim3 grid, dim3 block, size_t lds, hipStream_t s
         if (deferred && ka.gd_ent && ka.gd_flag) { hipLaunchKernelGGL((render_fused_kernel<FORM, CHAIN, false, true, true, true>), grid, block, lds, stream, ka); return; }
         if (deferred && ka.gd_ent) { hipLaunchKernelGGL((render_fused_kernel<FORM, CHAIN, false, true, true>), grid, block, lds, stream, ka); return; }
     }
-    if constexpr (form_defers<FORM>()) {
-        if (deferred) { hipLaunchKernelGGL((render_fused_kernel<FORM, CHAIN, CULL, true>), grid, block, lds, stream, ka); return; }
-    }
+    if (deferred) { hipLaunchKernelGGL((render_fused_kernel<FORM, CHAIN, CULL, true>), grid, block, lds, stream, ka); return; }
     hipLaunchKernelGGL((render_fused_kernel<FORM, CHAIN, CULL, false>), grid, block, lds, stream, ka);
 }
 template <bool CHAIN, bool CULL>
@@ -3205,64 +3177,27 @@ constexpr int CHAIN_SEG = 16;
 constexpr int CHAIN_MAX_SEGS = 64;
 size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 int chain_len(int S) {
-    static int f_seg = -1;
-    if (f_seg < 0) f_seg = dbg_int("GPNERF_CHAIN_SEG", CHAIN_SEG, 1, 256);
     const int least = (S + CHAIN_MAX_SEGS - 1) / CHAIN_MAX_SEGS;
-    return f_seg > least ? f_seg : least;
+    return CHAIN_SEG > least ? CHAIN_SEG : least;
 }
-// GPNERF_CHAIN_SCHEDULE="16,8,8,8,16" (experiment knob, under GPNERF_DEBUG=1): the launches' segment lengths, the last one repeated
-// to the end of the ray; at most CHAIN_MAX_SEGS entries.  Empty (default): equal segments.
-const int* chain_custom(int* n) {
-    static int f_n = -1, f_len[CHAIN_MAX_SEGS];
-    if (f_n < 0) {
-        f_n = 0;
-        const char* e = dbg_env("GPNERF_CHAIN_SCHEDULE");
-        while (e && *e && f_n < CHAIN_MAX_SEGS) {
-            const int v = atoi(e);
-            if (v < 1) break;
-            f_len[f_n++] = v > 256 ? 256 : v;
-            while (*e && *e != ',') ++e;
-            if (*e == ',') ++e;
-        }
-    }
-    *n = f_n;
-    return f_len;
-}
-// The launches' sample ranges.  Default: three segments of chain_len(), one twice as long, then segments three times as long.  GPNERF_CHAIN_MERGE_AFTER=k (experiment knob, under
-// GPNERF_DEBUG=1): from sample k on every segment is as long as all the samples before it ([0,16) .. [48,64), [64,128), ...).
-// Measured on the 512x512x128 bench frame, where 5 % of the rays are alive after 64 samples: 8.82 ms with equal segments,
-// 8.89 ms with the four tail launches merged into one -- the tail levels already run several samples of a ray per step
-// (chain_plan's P), so their launches cost little, and inside a long segment an opaque ray idles to the segment's end.
+// The launches' sample ranges: three segments of chain_len(), one twice as long, then segments three times as long
+// (512x512x128: 16,16,16,32,48: the few rays alive past sample 48 need fewer, fuller launches.  Round 5 had 16,16,16,16,32,32;
+// with the colour work out of the segment launches, three boxes: 6.93 -> 6.86 ms, with the two-sample tail units below 6.84).
 // begins[] gets n + 1 entries; returns n <= chain_segs(S).
 int chain_schedule(int S, int* begins) {
-    static int f_merge = -1;
-    if (f_merge < 0) f_merge = dbg_int("GPNERF_CHAIN_MERGE_AFTER", 0, 0, 1 << 20);       // 0 (default): equal segments throughout
-    int nc = 0;
-    const int* custom = chain_custom(&nc);
     const int len = chain_len(S);
-    int n = 0, k = 0, cur = len;
-    while (k < S && n < CHAIN_MAX_SEGS) {
+    int n = 0, k = 0;
+    while (k < S) {
         begins[n] = k;
-        if (nc > 0) cur = custom[n < nc ? n : nc - 1];
-        else if (f_merge > 0 && k >= f_merge) { cur = k; }            // from here on every segment is as long as all before it
-        else if (f_merge == 0 && n >= 3) cur = n == 3 ? 2 * len : 3 * len;   // default: three segments of `len`, one twice, then three
-                                                                      // times as long (512x512x128: 16,16,16,32,48: the few rays
-                                                                      // alive past sample 48 need fewer, fuller launches.  Round 5
-                                                                      // had 16,16,16,16,32,32; with the colour work out of the
-                                                                      // segment launches, three boxes: 6.93 -> 6.86 ms, with the
-                                                                      // two-sample tail units below 6.84)
+        k += n < 3 ? len : (n == 3 ? 2 * len : 3 * len);
         ++n;
-        k += cur;
-        if (n == CHAIN_MAX_SEGS - 1 && k < S) { begins[n++] = k; k = S; }     // (the schedule ran out of launches: one last segment to the end)
     }
     begins[n] = S;
     return n;
 }
-int chain_segs(int S) {               // upper bound on the launches (workspace sizing)
-    int begins[CHAIN_MAX_SEGS + 2];
-    const int n = chain_schedule(S, begins), len = chain_len(S), eq = (S + len - 1) / len;
-    return n > eq ? n : eq;
-}
+// upper bound on the launches (workspace sizing): every segment but the last is at least chain_len() long, so
+// n <= ceil(S / chain_len(S)) <= CHAIN_MAX_SEGS
+int chain_segs(int S) { return (S + chain_len(S) - 1) / chain_len(S); }
 size_t chain_chunks(int64_t n_rays) { return (size_t)((n_rays + 2047) / 2048); }       // LIST_CHUNK entries each
 // control block: per segment 8 queue counters, the length of its output list, and one survivor counter per LIST_CHUNK input entries
 size_t chain_ctrl_bytes(int n_seg, int64_t n_rays) { return align256((size_t)n_seg * (9 + chain_chunks(n_rays)) * sizeof(unsigned)); }
@@ -3282,19 +3217,12 @@ size_t chain_bytes(int64_t n_rays, int S) {
 struct Geometry { int waves, split; };
 
 Geometry choose_geometry(int64_t tiles, int S, bool may_split, size_t ws_bytes, int64_t n_rays, int n_cus) {
-    static int f_waves = -1, f_split = -1;
-    if (f_waves < 0) {
-        f_waves = dbg_int("GPNERF_WAVES", 0, 0, 8);
-        f_split = dbg_int("GPNERF_SPLIT", 0, 0, 8);
-    }
     const int64_t cus = n_cus > 0 ? n_cus : 256;
     Geometry best{8, 1};
     double best_t = 1e300;
     for (int split = 1; split <= GPNERF_MAX_SPLIT; split *= 2) {
         if (split > 1 && (!may_split || S / split < 8 || ws_bytes < (size_t)n_rays * split * 16 * sizeof(float))) continue;
-        if (f_split > 0 && split != f_split && !(split == 1 && f_split > 1 && !may_split)) continue;
         for (int w = GPNERF_MAX_WAVES; w >= 1; --w) {
-            if (f_waves > 0 && w != f_waves) continue;
             const int64_t blocks = (tiles * split + w - 1) / w;
             const int64_t rounds = (blocks + cus - 1) / cus;
             const double step = w <= 4 ? 82.0 : (w <= 8 ? 133.0 : 190.0);  // kilo-cycles per 32-sample step (measured)
@@ -3357,11 +3285,10 @@ int device_ready(int* cus) {
                 constexpr int F = decltype(form_tag)::value;
                 d.ok = d.ok && lds_ok(reinterpret_cast<const void*>(&render_fused_kernel<F, false, false, false>), bytes) &&
                        lds_ok(reinterpret_cast<const void*>(&render_fused_kernel<F, true, false, false>), bytes) &&
-                       lds_ok(reinterpret_cast<const void*>(&render_fused_kernel<F, false, true, false>), bytes);
-                if constexpr (form_defers<F>())
-                    d.ok = d.ok && lds_ok(reinterpret_cast<const void*>(&render_fused_kernel<F, false, false, true>), bytes) &&
-                           lds_ok(reinterpret_cast<const void*>(&render_fused_kernel<F, true, false, true>), bytes) &&
-                           lds_ok(reinterpret_cast<const void*>(&render_fused_kernel<F, false, true, true>), bytes);
+                       lds_ok(reinterpret_cast<const void*>(&render_fused_kernel<F, false, true, false>), bytes) &&
+                       lds_ok(reinterpret_cast<const void*>(&render_fused_kernel<F, false, false, true>), bytes) &&
+                       lds_ok(reinterpret_cast<const void*>(&render_fused_kernel<F, true, false, true>), bytes) &&
+                       lds_ok(reinterpret_cast<const void*>(&render_fused_kernel<F, false, true, true>), bytes);
             };
             all_of(std::integral_constant<int, FORM_F32>{}, lds_bytes);
             all_of(std::integral_constant<int, FORM_F32_FOLD>{}, lds_bytes);
@@ -3789,9 +3716,7 @@ int gpnerf_render_fused(const GpnerfFrame* f, const float* rays, int64_t n_rays,
     // occupancy culling: the keep bits of every sample in one pass before the launch (occupancy_mask_kernel), in the last
     // cull_mask_bytes() of the workspace (before the guard's block); outputs that need every step written keep the in-loop test
     unsigned long long* cull_mask = nullptr;
-    static int f_mask = -1;
-    if (f_mask < 0) f_mask = dbg_int("GPNERF_CULL_MASK", 3, 0, 3);       // experiments: 1 = keep bits, 2 = + tile order
-    if ((f_mask & 1) && culling && workspace && n_samples <= 128 && !out->weights && !out->raw && workspace_bytes >= QUEUE_BYTES + cull_mask_bytes(n_rays)) {
+    if (culling && workspace && n_samples <= 128 && !out->weights && !out->raw && workspace_bytes >= QUEUE_BYTES + cull_mask_bytes(n_rays)) {
         workspace_bytes = (workspace_bytes - cull_mask_bytes(n_rays)) & ~(size_t)255;
         cull_mask = reinterpret_cast<unsigned long long*>(static_cast<char*>(workspace) + workspace_bytes);
     }
@@ -3810,46 +3735,21 @@ int gpnerf_render_fused(const GpnerfFrame* f, const float* rays, int64_t n_rays,
     const bool may_split = seg_bytes && !(flags & GPNERF_FLAG_EARLY_TERM) && !out->samples_done &&
                            !(can_list && tiles * 4 >= (int64_t)n_cus * GPNERF_MAX_WAVES * 5);
     Geometry g = choose_geometry(tiles, n_samples, may_split, seg_bytes, n_rays, n_cus);
-    // whole rounds of full workgroups + a remainder launch (below) when the frame is that shape
-    static int f_rem = -1;
-    if (f_rem < 0) f_rem = dbg_int("GPNERF_REMAINDER", 2, 0, 2);     // 1: two launches (whole rounds, then the remainder); 2: one launch (below)
+    // whole rounds of full workgroups + the remainder's units (below) when the frame is that shape
     const int64_t slots = (int64_t)n_cus * GPNERF_MAX_WAVES;
     const int64_t rem_tiles = tiles % slots;
-    const bool remainder = f_rem && workspace && workspace_bytes >= QUEUE_BYTES && !(flags & (GPNERF_FLAG_EARLY_TERM | GPNERF_FLAG_OCC_CULL)) &&
-                           n_cus >= 8 && tiles > slots && rem_tiles > 0 && rem_tiles * 8 <= slots && n_samples >= 8 && !dbg_env("GPNERF_WAVES");
+    const bool remainder = workspace && workspace_bytes >= QUEUE_BYTES && !(flags & (GPNERF_FLAG_EARLY_TERM | GPNERF_FLAG_OCC_CULL)) &&
+                           n_cus >= 8 && tiles > slots && rem_tiles > 0 && rem_tiles * 8 <= slots && n_samples >= 8;
     if (remainder) { g.waves = GPNERF_MAX_WAVES; g.split = 1; }
-    // EXPERIMENT, not the default (GPNERF_DEBUG=1 GPNERF_QSPLIT=2 / 4 / 8): a frame of one to two rounds of wavefronts (2 048 < tiles
-    // <= 4 096 on 256 CUs: the 74 k-ray ZJU-sized frame, 272^2 ... 360^2 crops) ends with every SIMD's last whole tile running alone
-    // (profiles/r04/l_survey_frame_analysis.md).  Here the persistent workgroups pull (tile, sample segment) UNITS of
-    // S / n samples from the queue instead of whole tiles (same 32 rays per wavefront, same cost per step), each unit parks its
-    // partial composite and combine_segments_kernel merges them as it does for small frames.  Measured, reference-order form
-    // (profiles/r05/l_qsplit_sweep.txt): n = 8: 272^2 4.83 -> 4.40 ms, 320^2 6.39 -> 5.79, 360^2 7.49 -> 7.31, the survey frame
-    // 4.61 -> 4.52 (n = 4: 4.34), exactly one round (256^2) 3.83 -> 3.90; segment-major against tile-major unit order: no
-    // difference.  NOT adopted: the merge associates the transmittance product per segment (~1e-7 relative), so a frame in that
-    // range would no longer be bit-identical to its own shards or to the same rays inside a larger launch -- the invariant the
-    // strong-scaling path is tested on (tests/test_gpu_configs.py: the 8-rank plan of the 1024^2 frame has shares of exactly 4 096
-    // tiles) -- for 2 % on the frame size that matters.  A bit-exact version needs the units of a tile to resume each other's
-    // state in order (the chained form's parked state inside one launch).
-    static int f_dynamic = -1;
-    if (f_dynamic < 0) f_dynamic = dbg_int("GPNERF_DYNAMIC", 1, 0, 1);
-    static int f_qsplit = -1;
-    if (f_qsplit < 0) f_qsplit = dbg_int("GPNERF_QSPLIT", 0, 0, 8);
-    bool qsplit = false;
-    {
-        int q = f_qsplit > 1 ? f_qsplit : 0;
-        while (q > 1 && n_samples / q < 8) q >>= 1;
-        if (q > 1 && may_split && !culling && seg_bytes >= (size_t)n_rays * q * 16 * sizeof(float) && tiles > n_cus && f_dynamic) {
-            g.waves = GPNERF_MAX_WAVES; g.split = q; qsplit = true;
-        }
-    }
     int64_t blocks = (tiles * g.split + g.waves - 1) / g.waves;
-    // more than one round of workgroups and nothing split: persistent workgroups + tile queue (see render_fused_kernel)
-    const bool dynamic = f_dynamic && workspace && workspace_bytes >= QUEUE_BYTES && (g.split == 1 || qsplit) && blocks > n_cus;
+    // more than one round of workgroups and nothing split: persistent workgroups + tile queue (see render_fused_kernel), whose
+    // units are whole tiles -- every dynamic launch has split == 1
+    const bool dynamic = workspace && workspace_bytes >= QUEUE_BYTES && g.split == 1 && blocks > n_cus;
     if (dynamic) {
         if (!zero_async(workspace, QUEUE_BYTES, stream)) return GPNERF_E_LAUNCH;
         blocks = n_cus;
     }
-    const bool do_remainder = remainder && dynamic && !qsplit;
+    const bool do_remainder = remainder && dynamic;
     const OutK ok = to_outk(out, ray_order);
     KArgs ka;
     memset(&ka, 0, sizeof(ka));
@@ -3864,7 +3764,7 @@ int gpnerf_render_fused(const GpnerfFrame* f, const float* rays, int64_t n_rays,
         if (hipGetLastError() != hipSuccess) return GPNERF_E_LAUNCH;
         KArgs kf = ka;
         kf.flags = (unsigned)flags & ~(GPNERF_FLAG_SPLIT_F16 | GPNERF_FLAG_SPLIT_GUARD);
-        kf.split = 1; kf.part = nullptr; kf.dynamic = 1; kf.queue = guard_words + 8; kf.wave_cap = 0;
+        kf.split = 1; kf.part = nullptr; kf.dynamic = 1; kf.queue = guard_words + 8;
         kf.chain = 0; kf.seg = 0; kf.list_in = nullptr; kf.count_in = nullptr; kf.list_out = nullptr; kf.count_out = nullptr;
         const int64_t wg = (tiles + GPNERF_MAX_WAVES - 1) / GPNERF_MAX_WAVES;
         if (kf.cull_mask)
@@ -3875,21 +3775,14 @@ int gpnerf_render_fused(const GpnerfFrame* f, const float* rays, int64_t n_rays,
                                S_(stream), kf);
         return launch_status();
     };
-    static int f_cap = -1;
-    if (f_cap < 0) f_cap = dbg_int("GPNERF_WAVE_CAP", 0, 0, 8);      // experiments: waves per CU that pull tiles
-    ka.wave_cap = f_cap;
     ka.skip = (flags & GPNERF_FLAG_NO_EXITS) ? 0 : 3;
     // every form defers the colour branch sample by sample (render_tile) unless the exits are off or `raw` wants every rgb
-    static int f_defer = -1;
-    if (f_defer < 0) f_defer = dbg_int("GPNERF_DEFER", 1, 0, 1);
-    const bool deferred = f_defer && (ka.skip & 2) && !out->raw;
+    const bool deferred = (ka.skip & 2) && !out->raw;
     const int sel = guard ? SEL_GUARD : (split16 ? SEL_SPLIT : (folded ? SEL_FOLD : SEL_REF));
     // Frame-level deferral (fp32 forms, persistent launches of whole tiles): the sample loop only LISTS the samples whose weight is
     // not zero; the list is evaluated by the launch's own wavefronts (`unify`, below) or by colour_units_kernel, and
     // colour_accumulate_kernel adds every ray's terms in order (see there).
-    static int f_gdef = -1;
-    if (f_gdef < 0) f_gdef = dbg_int("GPNERF_FRAME_DEFER", 1, 0, 1);
-    const bool gdef_ok = f_gdef && deferred && !culling && !cull_mask && (sel == SEL_REF || sel == SEL_FOLD) && !(flags & GPNERF_FLAG_OCC_CULL) &&
+    const bool gdef_ok = deferred && !culling && !cull_mask && (sel == SEL_REF || sel == SEL_FOLD) && !(flags & GPNERF_FLAG_OCC_CULL) &&
                          gdef_fits(n_rays, n_samples) && workspace != nullptr;
     unsigned* gd_flags = nullptr;
     // the block sits behind what the launch's own form keeps in the workspace (`behind` bytes); false: no room, the wavefronts keep their passes
@@ -3906,18 +3799,13 @@ int gpnerf_render_fused(const GpnerfFrame* f, const float* rays, int64_t n_rays,
         kx.gd_rgbw = reinterpret_cast<f32x4*>(b + GDEF_HEAD_BYTES + cnt_bytes + flag_bytes + gdef_entries(n_rays, n_samples) * sizeof(uint4));
         return true;
     };
-    // unified form: the listing launch's own wavefronts evaluate the list once they have no tile left (render_fused_kernel, UNI)
-    static int f_uni = -1, f_budget = -1;
-    // (uni_budget = units a wavefront may evaluate between two tiles: measured 0 / 4 / 24 / 100 -> 9.72 / 9.75 / 9.82 / 11.8 ms on the
-    //  bench frame -- colour work between tiles buys no overlap and unbalances the tile queue; the list is evaluated when a wavefront
-    //  has no tile left, which is what fills the end of a launch whose tiles differ in cost)
-    if (f_uni < 0) { f_uni = dbg_int("GPNERF_UNIFIED", 3, 0, 3); f_budget = dbg_int("GPNERF_UNI_BUDGET", 0, 0, 4096); }
+    // unified form: the listing launch's own wavefronts evaluate the list once they have no tile left (render_fused_kernel, UNI),
+    // which is what fills the end of a launch whose tiles differ in cost
     auto unify = [&](KArgs& kx, long waves) -> bool {
         if (!kx.gd_ent || !gd_flags || (flags & GPNERF_FLAG_SHARED_DEVICE)) return false;
         if (!zero_async(gd_flags, gdef_flag_bytes(n_rays, n_samples), stream)) return false;
         kx.gd_flag = gd_flags;
         kx.gd_waves = (int)waves;
-        kx.uni_budget = f_budget;
         return true;
     };
     // the list's evaluation and the colour map of launch slots [0, n_slots) (behind the launches that listed the entries)
@@ -3929,9 +3817,7 @@ int gpnerf_render_fused(const GpnerfFrame* f, const float* rays, int64_t n_rays,
             return hipGetLastError() == hipSuccess;
         }
         KArgs kc = kx;
-        static int f_uchunk = -1;
-        if (f_uchunk < 0) f_uchunk = dbg_int("GPNERF_UNIT_CHUNK", 64, 1, 4096);
-        kc.chunk = f_uchunk;
+        kc.chunk = 64;                  // units per chunk of the unit queue
         if (sel == SEL_FOLD) hipLaunchKernelGGL((colour_units_kernel<FORM_F32_FOLD>), dim3((unsigned)n_cus), dim3(64 * UNIT_WAVES), lds_bytes, S_(stream), kc);
         else hipLaunchKernelGGL((colour_units_kernel<FORM_F32>), dim3((unsigned)n_cus), dim3(64 * UNIT_WAVES), lds_bytes, S_(stream), kc);
         if (hipGetLastError() != hipSuccess) return false;
@@ -3939,24 +3825,14 @@ int gpnerf_render_fused(const GpnerfFrame* f, const float* rays, int64_t n_rays,
                            (const f32x4*)kx.gd_rgbw, n_slots, (int)n_samples, ok.order, ok.rgb);
         return hipGetLastError() == hipSuccess;
     };
-    static int f_segmajor = -1;
-    if (f_segmajor < 0) f_segmajor = dbg_int("GPNERF_QSPLIT_SEGMAJOR", 0, 0, 1);
-    ka.seg_major = f_segmajor;
-    static int f_stagger = -1;
-    if (f_stagger < 0) f_stagger = dbg_int("GPNERF_STAGGER", 0, 0, 4096);
-    ka.stagger = f_stagger;
-    static int f_chunk = -1;
-    if (f_chunk < 0) f_chunk = dbg_int("GPNERF_QUEUE_CHUNK", 64, 1, 4096);
-    ka.chunk = f_chunk > 0 ? f_chunk : (int)((tiles + 7) / 8);        // 0: one contiguous run per XCD
-    static int f_tail = -1;
-    if (f_tail < 0) f_tail = dbg_int("GPNERF_CHAIN_TAILP", 2, 1, 8);
-    ka.tail_p = f_tail;
+    ka.chunk = 64;                      // tiles per chunk of the XCD queues
+    ka.tail_p = 2;                      // samples per step of the units the last whole round is cut into (chain_plan)
     // ONE launch for a frame of whole rounds + a few tiles: the segmented form's kernel over all S samples as a single segment
     // (term_eps = 0: nothing is ever frozen), whose work units are the whole rounds' 32-ray tiles at one sample per step AND the
     // remaining tiles at eight samples of a ray per step (chain_plan), all on one tile queue.  In a lone round a SIMD's older
     // wavefront is through its tile after ~2.7 ms and the younger after ~4.0 ms: the short remainder units fill exactly that
-    // gap, where a second launch (f_rem = 1) had to wait for the first to drain.  73 689-ray frame: 4.58 -> 4.36 ms.
-    if (do_remainder && f_rem == 2 && tiles < 2 * slots && !out->samples_done) {      // (several whole rounds: the plain kernel's loop is ~2 % faster than the segmented form's, two launches win: 576x576x64 17.08 against 17.46 ms)
+    // gap, where a second launch had to wait for the first to drain.  73 689-ray frame: 4.58 -> 4.36 ms.
+    if (do_remainder && tiles < 2 * slots && !out->samples_done) {      // (several whole rounds: the plain kernel's loop is ~2 % faster than the segmented form's, two launches win: 576x576x64 17.08 against 17.46 ms)
         KArgs ku = ka;
         ku.split = 1; ku.dynamic = 1; ku.part = nullptr;
         ku.chain = (int)n_samples; ku.seg = 0; ku.term_eps = 0.f;
@@ -3965,7 +3841,7 @@ int gpnerf_render_fused(const GpnerfFrame* f, const float* rays, int64_t n_rays,
         ku.list_in = nullptr; ku.count_in = nullptr; ku.list_out = nullptr; ku.count_out = nullptr; ku.chunk_cnt = nullptr;
         ku.p_cap = (long)(slots * RAYS_PER_WAVE);
         const bool listed = gdef_setup(ku, QUEUE_BYTES);
-        if (listed && (f_uni & 2)) unify(ku, (long)n_cus * GPNERF_MAX_WAVES);
+        if (listed) unify(ku, (long)n_cus * GPNERF_MAX_WAVES);
         launch_render<true, false>(sel, deferred, dim3((unsigned)n_cus), full_block, S_(stream), ku);
         if (listed && !colour_phase(ku, (long)n_rays)) return GPNERF_E_LAUNCH;
         return fixup();
@@ -3976,7 +3852,7 @@ int gpnerf_render_fused(const GpnerfFrame* f, const float* rays, int64_t n_rays,
     // bench frame a ray needs 20 % of its samples, a fixed 32-ray tile 35-43 % (until its last ray is opaque).  The launches
     // are enqueued unconditionally -- one that finds its list empty returns before it stages anything.
     // (frames of less than one round of waves gain nothing from it, and every XCD's queue needs workgroups of its own)
-    const size_t need_chain = (flags & GPNERF_FLAG_EARLY_TERM) && !culling && f_dynamic && tiles >= (int64_t)n_cus * GPNERF_MAX_WAVES && n_cus >= 8
+    const size_t need_chain = (flags & GPNERF_FLAG_EARLY_TERM) && !culling && tiles >= (int64_t)n_cus * GPNERF_MAX_WAVES && n_cus >= 8
                                   ? chain_bytes(n_rays, n_samples) : 0;
     if (need_chain && workspace && workspace_bytes >= need_chain) {
         const int n_seg = chain_segs(n_samples);
@@ -3991,9 +3867,7 @@ int gpnerf_render_fused(const GpnerfFrame* f, const float* rays, int64_t n_rays,
         ka.part = reinterpret_cast<float*>(base + ctrl_bytes + 3 * list_bytes);
         const int64_t wg = (tiles + GPNERF_MAX_WAVES - 1) / GPNERF_MAX_WAVES;
         const unsigned grid = (unsigned)(wg < n_cus ? wg : n_cus);
-        static float f_fill = -1.f;
-        if (f_fill < 0.f) { const char* e = dbg_env("GPNERF_CHAIN_PFILL"); f_fill = e ? fminf(fmaxf((float)atof(e), 0.f), 8.f) : 1.f; }
-        ka.p_cap = (long)((double)grid * GPNERF_MAX_WAVES * RAYS_PER_WAVE * f_fill);
+        ka.p_cap = (long)grid * GPNERF_MAX_WAVES * RAYS_PER_WAVE;
         ka.first_slot = 0; ka.first_items = (long)n_rays;
         const bool listed = gdef_setup(ka, need_chain);
         int begins[CHAIN_MAX_SEGS + 2];
@@ -4026,18 +3900,18 @@ int gpnerf_render_fused(const GpnerfFrame* f, const float* rays, int64_t n_rays,
     // P), S / 8 steps each, with the plain form's arithmetic per ray (term_eps = 0: nothing is ever frozen).  Bit-identical
     // results; 576x576x64: 18.8 -> 18.0 ms.  (A larger remainder is better left to the queue: CUs with few waves step faster.)
     if (do_remainder) ka.n_rays = (long)((tiles - rem_tiles) * RAYS_PER_WAVE);
-    const bool gdef = dynamic && !qsplit && !(flags & GPNERF_FLAG_EARLY_TERM) && gdef_setup(ka, QUEUE_BYTES);
+    const bool gdef = dynamic && !(flags & GPNERF_FLAG_EARLY_TERM) && gdef_setup(ka, QUEUE_BYTES);
     // unified form, unless a remainder launch follows (with both launches unified -- the second's tickets starting where the first's
     // list ends -- 576 squared measured 12.67 -> 12.89 ms, 370 squared 5.70 -> 6.01):
     // 300 / 320 / 340 / 384 squared: 4.42 / 5.04 / 5.13 / 6.15 ms with the second kernel, 4.17 / 4.51 / 5.00 / 5.62 unified
-    if (gdef && (f_uni & 1) && !do_remainder && !cull_mask) unify(ka, (long)blocks * g.waves);
+    if (gdef && !do_remainder && !cull_mask) unify(ka, (long)blocks * g.waves);
     if (cull_mask) {
         ka.cull_mask = cull_mask;
         {
             hipLaunchKernelGGL(occupancy_mask_kernel, dim3((unsigned)((tiles + 3) / 4)), dim3(256), 0, S_(stream), k, rays, ok.order, (long)n_rays,
                                (int)n_samples, (flags & GPNERF_FLAG_FLIP_SAMPLES) ? 1 : 0, cull_mask);
             if (hipGetLastError() != hipSuccess) return GPNERF_E_LAUNCH;
-            if (dynamic && (f_mask & 2)) {      // longest tiles first (see tile_steps_kernel)
+            if (dynamic) {      // longest tiles first (see tile_steps_kernel)
                 char* const after = reinterpret_cast<char*>(cull_mask) + align256((size_t)n_rays * 2 * sizeof(unsigned long long));
                 int* const steps = reinterpret_cast<int*>(after);
                 int* const order = reinterpret_cast<int*>(after + align256(cull_tiles(n_rays) * sizeof(int)));

@@ -954,22 +954,17 @@ int gpnerf_vertex_attention(const float* q, const float* kv, const float* wq, co
     if (d_k & (d_k - 1)) return GPNERF_E_ARG;          // the per-head reduction is a butterfly
     // two workgroups per CU: a wavefront reads its 4 x 32 weight rows once and walks ~3 vertices (6 890 vertices: 128 / 256 / 512 /
     // 768 / 1 024 / 1 723 workgroups: 52 / 32 / 30 / 37 / 40 / 57 us, tools/probes/attention_time.py)
-    // the reference's shape: the matrix-core form (GPNERF_ATT_SHUFFLE=1 under GPNERF_DEBUG=1 keeps the shuffle form for comparison)
+    // the reference's shape: the matrix-core form; other shapes: the shuffle form
     if (d_model == 32 && kv_dim == 32 && d_k >= 4) {
-        static int f_shuffle = -1;
-        if (f_shuffle < 0) f_shuffle = dbg_int("GPNERF_ATT_SHUFFLE", 0, 0, 1);       // experiment knob (gpnerf_diag.h: 0 in the product)
-        if (!f_shuffle) {
-            const dim3 grid((unsigned)((n + 31) / 32)), block(64);
-            hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-            if (views == 1) hipLaunchKernelGGL(vertex_attention_mfma_kernel<1>, grid, block, 0, st, q, kv, wq, wk, wv, wfc, (int)n, (int)n_head, out);
-            else if (views == 2) hipLaunchKernelGGL(vertex_attention_mfma_kernel<2>, grid, block, 0, st, q, kv, wq, wk, wv, wfc, (int)n, (int)n_head, out);
-            else if (views == 3) hipLaunchKernelGGL(vertex_attention_mfma_kernel<3>, grid, block, 0, st, q, kv, wq, wk, wv, wfc, (int)n, (int)n_head, out);
-            else hipLaunchKernelGGL(vertex_attention_mfma_kernel<4>, grid, block, 0, st, q, kv, wq, wk, wv, wfc, (int)n, (int)n_head, out);
-            return hipGetLastError() == hipSuccess ? GPNERF_OK : GPNERF_E_LAUNCH;
-        }
+        const dim3 grid((unsigned)((n + 31) / 32)), block(64);
+        hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+        if (views == 1) hipLaunchKernelGGL(vertex_attention_mfma_kernel<1>, grid, block, 0, st, q, kv, wq, wk, wv, wfc, (int)n, (int)n_head, out);
+        else if (views == 2) hipLaunchKernelGGL(vertex_attention_mfma_kernel<2>, grid, block, 0, st, q, kv, wq, wk, wv, wfc, (int)n, (int)n_head, out);
+        else if (views == 3) hipLaunchKernelGGL(vertex_attention_mfma_kernel<3>, grid, block, 0, st, q, kv, wq, wk, wv, wfc, (int)n, (int)n_head, out);
+        else hipLaunchKernelGGL(vertex_attention_mfma_kernel<4>, grid, block, 0, st, q, kv, wq, wk, wv, wfc, (int)n, (int)n_head, out);
+        return hipGetLastError() == hipSuccess ? GPNERF_OK : GPNERF_E_LAUNCH;
     }
-    int blocks = n < 2048 ? (n + 3) / 4 : 512;
-    blocks = dbg_int("GPNERF_ATT_BLOCKS", blocks, 1, 4096);                         // experiment knob (gpnerf_diag.h)
+    const int blocks = n < 2048 ? (n + 3) / 4 : 512;
     if (d_model <= 32 && kv_dim <= 32)
         hipLaunchKernelGGL(vertex_attention_kernel<32>, dim3((unsigned)blocks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), q,
                            kv, wq, wk, wv, wfc, (int)n, (int)d_model, (int)kv_dim, (int)n_head, (int)views, out);

@@ -171,10 +171,7 @@ class SparseConvNet(nn.Module):
 
     @staticmethod
     def _split16(mod):
-        """the split-precision kernel's shapes (gpnerf_sparse_conv3_mfma16); GPNERF_SPARSE_FP32=1 under GPNERF_DEBUG=1 keeps the fp32 form"""
-        import os
-        if os.environ.get("GPNERF_DEBUG") == "1" and os.environ.get("GPNERF_SPARSE_FP32") == "1":
-            return False
+        """the split-precision kernel's shapes (gpnerf_sparse_conv3_mfma16); the other shapes take the fp32 form"""
         return mod.cin in (16, 32) and mod.cout <= 32
 
     def plan_levels(self, coord, out_sh, channels=None):

@@ -51,6 +51,14 @@ def test_the_product_sources_carry_no_lab_paths():
     hooks = open(os.path.join(csrc, "nodiag", "gpnerf_diag.h")).read()
     code = re.sub(r"//[^\n]*", "", hooks)
     assert "getenv" not in code and "atomicAdd" not in code and "s_memtime" not in code
+    # no launcher experiment knob either: the product neither defines nor calls dbg_int / dbg_env (every product translation
+    # unit and header, i.e. everything in csrc/ outside the lab's diag/)
+    knob = re.compile(r"\bdbg_(int|env)\s*\(")
+    assert not knob.search(code)
+    for name in sorted(os.listdir(csrc)) + [os.path.join("nodiag", n) for n in sorted(os.listdir(os.path.join(csrc, "nodiag")))]:
+        if name.endswith((".hip", ".h")):
+            for i, line in enumerate(open(os.path.join(csrc, name)), 1):
+                assert not knob.search(line.split("//")[0]), f"{name}:{i}: {line.strip()}"
     r = subprocess.run(["make", "-n", "-C", csrc, "HIPFLAGS=-O3 -DGPNERF_X_ANYTHING"], capture_output=True, text=True)
     assert r.returncode != 0 and "takes no -DGPNERF_" in (r.stderr + r.stdout)
 

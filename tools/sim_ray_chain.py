@@ -2,7 +2,7 @@
 """Schedule model of per-ray early termination with re-packing (diagnostic): level-synchronous (one launch per segment, what
 gpnerf_render_fused does) against a barrier-free ray FIFO inside one launch.
 Input: per-ray stop indices (tools/et_potential.py -> gpurun_out/stop_rays.npy) and the measured step time of a wave against
-the number of waves active on its CU (GPNERF_WAVE_CAP sweep of the headline frame)."""
+the number of waves active on its CU (round 2's sweep of the waves per CU that pull tiles, headline frame)."""
 import sys
 import heapq
 import numpy as np
