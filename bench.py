@@ -14,13 +14,18 @@ launches with.  Inputs are resident in HBM before the timed region.
   N > 1   STRONG scaling (default): the same frame's rays are split over the N ranks in round-robin bands
           (gp-nerf_amd/parallel.py ShardPlan); a step = render my share + ONE all_gather_into_tensor of the packed pixels
           (rgb + depth, 16 B/ray) + re-assembly in ray order on every rank.  value = rays of the frame / step time, so
-          value(N) / value(1) is the speed-up on one frame (north_star: >= 6x at 8 GPUs).  After the headline region the
-          same flow is timed on a 1024x1024x64 frame (BASELINE.json configs[3]) and reported as `config4_1024`.
+          value(N) / value(1) is the speed-up on one frame (north_star: >= 6x at 8 GPUs).  With --full, after the headline
+          region the same flow is timed on a 1024x1024x64 frame (BASELINE.json configs[3]) and reported as `config4_1024`.
           --scaling weak: every rank renders its own full frame (a band of an N-times larger image) + the same all-gather.
 
-One JSON line is printed by rank 0; see DESIGN.md for the accounting behind `roofline`.  `ms_per_step` is the wall time of one
-timed step (--steps of them, after --warmup untimed ones).  --dump-outputs DIR writes the maps the last timed step returned
-(dump_outputs); the inputs depend on the arguments alone (--seed), so two builds can be compared output for output.
+One JSON line is printed by rank 0.  `ms_per_step` is the wall time of one timed step (--steps of them, after --warmup untimed
+ones).  --dump-outputs DIR writes the maps the last timed step returned (dump_outputs); the inputs depend on the arguments alone
+(--seed), so two builds can be compared output for output.
+
+A plain run does only what the headline needs: it sets up, warms up, times the steps, dumps if asked and prints the line.  --full
+then measures everything reported beside the headline, each after the timed region and never part of `value`: `roofline` (see
+DESIGN.md for its accounting; with the dense launch), `early_term`, `trained_like`, `beside_headline`, `cpu_baseline` and, for
+N > 1, `config4_1024` (--no-extras / --no-cpu-baseline leave parts of it out).
 """
 import argparse
 import importlib
@@ -67,6 +72,53 @@ def price_work_done(stats, flops_algorithmic):
     return flops_algorithmic * frac_done, exits
 
 
+def roofline(args, world, samples, step_stats, kernel_ms, evaluated, dense):
+    """--full: the MFMA roofline of the timed launches.  `samples` = rays x samples per ray of one launch (this rank's share),
+    `step_stats` = the exit counters of the launch before the warm-up, `kernel_ms` = the timed steps' mean event time around the
+    call, `evaluated` = the fraction of the samples an early-terminated / culled launch evaluated (else None), `dense` = the same
+    launch under GPNERF_FLAG_NO_EXITS (or None)."""
+    flops_per_launch = samples * FLOP_PER_SAMPLE
+    if evaluated is not None:
+        # the units a launch processes are the samples it evaluates: terminated / culled samples are not work done
+        flops_per_launch *= evaluated
+    # The fp32 forms leave out work that provably cannot change any output, wave step by wave step (bit-exact, see
+    # include/gpnerf_hip.h step_stats).  The roofline prices the work DONE: `achieved` = FLOPs of the layers the launch
+    # evaluated / its duration, so `frac` never exceeds 1 and is what the matrix pipe was asked to do; the rate of ANSWERS
+    # (every sample the launch is answerable for x 110 848 FLOP, which can exceed the pipe's peak when most colour branches are
+    # provably not needed) is roofline.algorithmic_rate; the same launch with every layer evaluated for every sample
+    # (GPNERF_FLAG_NO_EXITS, data-independent) is roofline.dense_ms / dense_frac.
+    flops_done, exits = price_work_done(step_stats, flops_per_launch)
+    exits["note"] = ("bit-exact exits (GPNERF_FLAG_NO_EXITS switches them off: roofline.dense_*): a volume level whose features are zero in all 32 "
+                     "samples of a step is left out of the sigma feature layer; a sample whose weight alpha*T is exactly zero (nn.ReLU on the density; "
+                     "masked_fill) adds fma(0, rgb, c) = c to the colour map, so its colour branch is not evaluated: the sample loop lists the samples "
+                     "that need it, colour_units_kernel runs the branch on 32 list entries at a time and colour_accumulate_kernel adds every ray's terms "
+                     "in sample order (kernel_ms is the whole call: the three kernels); steps behind the sample at which all 32 rays' transmittance is exactly "
+                     "0 are settled without a gather or an MFMA")
+    algorithmic = flops_per_launch / (kernel_ms * 1e-3) / 1e12
+    achieved = flops_done / (kernel_ms * 1e-3) / 1e12
+    traffic, traffic_src = measured_traffic(args, world)
+    peak = PEAK_F16_MFMA_TFLOPS if args.split_f16 else PEAK_F32_MFMA_TFLOPS
+    r = {"bound": "mfma", "achieved": achieved, "peak": peak, "unit": "TFLOP/s",
+         "frac": achieved / peak, "traffic": traffic, "traffic_source": traffic_src,
+         "kernel": "render_fused_kernel" if args.split_f16 else
+         "render_fused_kernel + colour_units_kernel + colour_accumulate_kernel (one gpnerf_render_fused call; kernel_ms = HIP events around the call = the sum of their rocprofv3 averages)",
+         "kernel_ms": kernel_ms, "flop_per_launch": flops_done,
+         "accounting": "work done: FLOPs of the dense layers the launch evaluated (step_stats) / kernel_ms; never above the peak",
+         "algorithmic_rate": {"tflops": algorithmic, "flop_per_launch": flops_per_launch, "over_peak": algorithmic / peak,
+                              "note": "every sample the launch answers for x 110 848 FLOP per second: a rate of answers, not of MFMAs"},
+         "exits": exits}
+    if dense is not None:
+        r.update(dense)
+    if args.split_f16:
+        r["split_note"] = ("peak = dense f16 MFMA; the form issues 3 MFMAs per 16-deep k-step (3x the algorithmic FLOPs) and is "
+                           "bound by vector-ALU issue, not by the matrix pipe (30 % busy: profiles/r02/b_pmc_summary_split_guarded.json)")
+    if evaluated is not None:
+        r["samples_evaluated_frac"] = evaluated
+        r["note"] = ("flop_per_launch counts the samples the launch evaluated (a ray stops once its T < term_eps / a wavefront skips "
+                     "steps whose 32 samples are all unoccupied), not the S per ray the reference would")
+    return r
+
+
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -84,8 +136,13 @@ def parse():
                          "become opaque, which a trained net's do and a random one's do not)")
     ap.add_argument("--outputs", default="api", choices=["api", "light"],
                     help="api: every map Renderer.render returns; light: rgb/depth/acc/disp only")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the measurements reported beside the headline")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, measure what is reported beside it: the roofline, the dense and early-termination launches, "
+                         "the trained-like frame, the other forms and entry points (beside_headline), the CPU baseline, the 1024x1024 frame "
+                         "of N > 1.  Without it a run sets up, warms up, times the steps and prints the headline line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: without cpu_baseline")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="with --full: without trained_like, beside_headline and config4_1024 (the measurements on other frames and forms)")
     ap.add_argument("--cpu-seconds", type=float, default=16.0, help="target CPU time of the cpu_baseline samples (half per CPU program)")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
@@ -375,7 +432,8 @@ def main():
     flow = Flow(wl)
     # how many 32-sample steps take the kernel's bit-exact exits: counted by one launch BEFORE the warm-up (it is the process's cold
     # launch; behind the timed region it would be a second cold one -- the device clocks down while the host reduces the timings --
-    # and sit in the profiler's average of this kernel)
+    # and sit in the profiler's average of this kernel).  A plain run makes it too, so that its warm-up and timed steps follow the
+    # same launches as --full's; only --full's roofline reads the counters.
     step_stats = fm.render_fused(wl.frame, flow.rays, S, want=flow.want + ("step_stats",), ray_order=flow.order, fold=flow.fold, **kw)["step_stats"].cpu().numpy()
     dt, kernel_ms, out = flow.timed(args.steps, args.warmup)
     # what the last timed step returned, on the host before anything else runs on the device
@@ -388,7 +446,7 @@ def main():
     # the data-independent figure: the same launch with every layer evaluated for every sample (GPNERF_FLAG_NO_EXITS; same bits),
     # measured right behind the timed region, never part of `value`
     dense = None
-    if world == 1 and rank == 0 and not args.split_f16 and not args.early_term and not args.occ_cull:
+    if args.full and world == 1 and rank == 0 and not args.split_f16 and not args.early_term and not args.occ_cull:
         d_ms, d_out = time_launches(lambda: fm.render_fused(wl.frame, flow.rays, S, want=flow.want, ray_order=flow.order, fold=flow.fold, exits=False, **kw),
                                     args.steps, args.warmup)
         d_tf = float(flow.n_local) * S * FLOP_PER_SAMPLE / (d_ms * 1e-3) / 1e12
@@ -396,7 +454,7 @@ def main():
                  "dense_same_bits": bool(all(torch.equal(torch.nan_to_num(d_out[k]), torch.nan_to_num(out[k])) for k in ("rgb_map", "depth_map", "acc_map"))),
                  "dense_note": "GPNERF_FLAG_NO_EXITS: every layer of every sample evaluated (all 110 848 FLOP x samples on the matrix pipe), same maps bit for bit"}
     extras = {}
-    if world > 1 and strong and not args.no_extras and args.size != 1024:
+    if args.full and world > 1 and strong and not args.no_extras and args.size != 1024:
         # BASELINE.json configs[3]: one 1024x1024x64 frame over the same ranks, same flow
         wl4 = Workload(args, 1024, 64, dev, 0.0)
         f4 = Flow(wl4)
@@ -411,30 +469,13 @@ def main():
     if rank == 0:
         ms_per_step = dt / args.steps * 1e3
         value = flow.rays_per_step * args.steps / dt
-        flops_per_launch = float(flow.n_local) * S * FLOP_PER_SAMPLE
         evaluated = None
         alive_after = None
-        if args.early_term or args.occ_cull:
-            # the units a launch processes are the samples it evaluates: terminated / culled samples are not work done
+        if args.full and (args.early_term or args.occ_cull):
+            # how many of its samples the launch evaluates (--full's roofline prices those)
             done = fm.render_fused(wl.frame, flow.rays, S, want=("samples_done",), ray_order=flow.order, fold=flow.fold, **kw)["samples_done"]
             evaluated = float(done.float().mean()) / S
             alive_after = {str(k): float((done > k).float().mean()) for k in range(32, S, 32)}
-            flops_per_launch *= evaluated
-        # The fp32 forms leave out work that provably cannot change any output, wave step by wave step (bit-exact, see
-        # include/gpnerf_hip.h step_stats).  The roofline prices the work DONE: `achieved` = FLOPs of the layers the launch
-        # evaluated / its duration, so `frac` never exceeds 1 and is what the matrix pipe was asked to do; the rate of ANSWERS
-        # (every sample the launch is answerable for x 110 848 FLOP, which can exceed the pipe's peak when most colour branches are
-        # provably not needed) is roofline.algorithmic_rate; the same launch with every layer evaluated for every sample
-        # (GPNERF_FLAG_NO_EXITS, data-independent) is roofline.dense_ms / dense_frac.
-        flops_done, exits = price_work_done(step_stats, flops_per_launch)
-        exits["note"] = ("bit-exact exits (GPNERF_FLAG_NO_EXITS switches them off: roofline.dense_*): a volume level whose features are zero in all 32 "
-                         "samples of a step is left out of the sigma feature layer; a sample whose weight alpha*T is exactly zero (nn.ReLU on the density; "
-                         "masked_fill) adds fma(0, rgb, c) = c to the colour map, so its colour branch is not evaluated: the sample loop lists the samples "
-                         "that need it, colour_units_kernel runs the branch on 32 list entries at a time and colour_accumulate_kernel adds every ray's terms "
-                         "in sample order (kernel_ms is the whole call: the three kernels); steps behind the sample at which all 32 rays' transmittance is exactly "
-                         "0 are settled without a gather or an MFMA")
-        algorithmic = flops_per_launch / (kernel_ms * 1e-3) / 1e12
-        achieved = flops_done / (kernel_ms * 1e-3) / 1e12
         cfg_no = 2 if args.early_term else (3 if (args.size == 1024 and world > 1) else 1)
         if world == 1:
             parallelism = "single GPU"
@@ -443,8 +484,6 @@ def main():
                            f"of rgb+depth (16 B/ray) per frame")
         else:
             parallelism = f"weak: every one of {world} GPUs renders its own frame-sized band, all-gather of rgb+depth"
-        traffic, traffic_src = measured_traffic(args, world)
-        peak = PEAK_F16_MFMA_TFLOPS if args.split_f16 else PEAK_F32_MFMA_TFLOPS
         line = {
             "metric": "rays_per_sec", "value": value, "unit": "rays/s", "n_gpus": world, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": ms_per_step, "ms_per_frame": ms_per_step,
@@ -457,50 +496,36 @@ def main():
                        "early_term": bool(args.early_term), "term_eps": args.term_eps if args.early_term else None, "sigma_bias": sigma_bias,
                        "form": "split-f16" if args.split_f16 else ("fp32, folded coarse levels (round 4)" if flow.fold else "fp32, reference summation order"),
                        "exits": "none (the split-precision forms evaluate every layer of every sample)" if args.split_f16 else
-                                "bit-exact (roofline.exits): zero-weight samples' colour branch, all-zero volume levels, samples behind an exactly zero "
-                                "transmittance are not evaluated; the same launch with everything evaluated is roofline.dense_ms / dense_frac",
+                                "bit-exact (--full: roofline.exits): zero-weight samples' colour branch, all-zero volume levels, samples behind an exactly zero "
+                                "transmittance are not evaluated; the same launch with everything evaluated is --full's roofline.dense_ms / dense_frac",
                        "folded_volumes": bool(flow.fold), "occ_cull": bool(args.occ_cull), "split_f16": bool(args.split_f16), "split_guard": bool(args.split_f16 and not args.no_guard), "vol_occupancy": args.occupancy,
                        "out_sh_dhw": [int(x) for x in wl.sc["out_sh"][0]], "parallelism": parallelism},
-            "roofline": {"bound": "mfma", "achieved": achieved, "peak": peak, "unit": "TFLOP/s",
-                         "frac": achieved / peak, "traffic": traffic, "traffic_source": traffic_src,
-                         "kernel": "render_fused_kernel" if args.split_f16 else
-                         "render_fused_kernel + colour_units_kernel + colour_accumulate_kernel (one gpnerf_render_fused call; kernel_ms = HIP events around the call = the sum of their rocprofv3 averages)",
-                         "kernel_ms": kernel_ms, "flop_per_launch": flops_done,
-                         "accounting": "work done: FLOPs of the dense layers the launch evaluated (step_stats) / kernel_ms; never above the peak",
-                         "algorithmic_rate": {"tflops": algorithmic, "flop_per_launch": flops_per_launch, "over_peak": algorithmic / peak,
-                                              "note": "every sample the launch answers for x 110 848 FLOP per second: a rate of answers, not of MFMAs"},
-                         "exits": exits},
         }
-        if dense is not None:
-            line["roofline"].update(dense)
+        if args.full:
+            line["roofline"] = roofline(args, world, float(flow.n_local) * S, step_stats, kernel_ms, evaluated, dense)
         line.update(extras)
         line.update(rank_summary)
         if args.split_f16:
             line["dtype"] = "f32 operands as f16 hi+lo pairs on v_mfma_f32_32x32x16_f16, f32 accumulation"
-            line["roofline"]["split_note"] = ("peak = dense f16 MFMA; the form issues 3 MFMAs per 16-deep k-step (3x the algorithmic FLOPs) and is "
-                                              "bound by vector-ALU issue, not by the matrix pipe (30 % busy: profiles/r02/b_pmc_summary_split_guarded.json)")
-        if evaluated is not None:
-            line["roofline"]["samples_evaluated_frac"] = evaluated
-            line["roofline"]["note"] = ("flop_per_launch counts the samples the launch evaluated (a ray stops once its T < term_eps / a wavefront skips "
-                                        "steps whose 32 samples are all unoccupied), not the S per ray the reference would")
-        if args.early_term:
-            line["early_term"] = {"samples_evaluated_frac": evaluated, "rays_alive_after_samples": alive_after,
-                                  "note": "a ray stops once its T < term_eps; the launch walks the samples in 16-sample segments and re-packs the rays still alive "
-                                          "32 to a wavefront for every segment (frames smaller than one round of wavefronts: a 32-ray tile stops as a whole)"}
-        if world == 1 and not args.no_extras:
-            try:        # the second fixed workload: trained-like distributions at the headline's size
-                line["trained_like"] = trained_like_workload(args, fm)
-            except Exception as e:
-                line["trained_like"] = {"error": repr(e)[:300]}
-            line["beside_headline"] = beside_headline(args, fm, wl, kw, flow)
-        if world == 1 and not args.no_cpu_baseline:
-            line["cpu_baseline"] = cpu_baseline(wl.sc, wl.rays_h, S, args.cpu_seconds)
-            try:        # BASELINE.json configs[0] (the reference's own CPU-runnable case): the whole 64x64x32 crop on the same cores
-                line["cpu_baseline"]["config1_64x64x32"] = cpu_config1(args.seed)
-            except Exception as e:
-                line["cpu_baseline"]["config1_64x64x32"] = {"error": repr(e)[:200]}
-            line["vs_cpu"] = value / line["cpu_baseline"]["value"]                           # against the blocked (fast) CPU twin
-            line["vs_cpu_scalar_oracle"] = value / line["cpu_baseline"]["scalar_oracle"]["value"]
+        if args.full:
+            if args.early_term:
+                line["early_term"] = {"samples_evaluated_frac": evaluated, "rays_alive_after_samples": alive_after,
+                                      "note": "a ray stops once its T < term_eps; the launch walks the samples in 16-sample segments and re-packs the rays still alive "
+                                              "32 to a wavefront for every segment (frames smaller than one round of wavefronts: a 32-ray tile stops as a whole)"}
+            if world == 1 and not args.no_extras:
+                try:        # the second fixed workload: trained-like distributions at the headline's size
+                    line["trained_like"] = trained_like_workload(args, fm)
+                except Exception as e:
+                    line["trained_like"] = {"error": repr(e)[:300]}
+                line["beside_headline"] = beside_headline(args, fm, wl, kw, flow)
+            if world == 1 and not args.no_cpu_baseline:
+                line["cpu_baseline"] = cpu_baseline(wl.sc, wl.rays_h, S, args.cpu_seconds)
+                try:        # BASELINE.json configs[0] (the reference's own CPU-runnable case): the whole 64x64x32 crop on the same cores
+                    line["cpu_baseline"]["config1_64x64x32"] = cpu_config1(args.seed)
+                except Exception as e:
+                    line["cpu_baseline"]["config1_64x64x32"] = {"error": repr(e)[:200]}
+                line["vs_cpu"] = value / line["cpu_baseline"]["value"]                           # against the blocked (fast) CPU twin
+                line["vs_cpu_scalar_oracle"] = value / line["cpu_baseline"]["scalar_oracle"]["value"]
         # sanity on the product's own output (not a parity check; tests/ do that)
         assert bool(torch.isfinite(out["rgb_map"]).all()), "non-finite rgb"
         line["maps_finite"] = bool(torch.isfinite(out["rgb_map"]).all() and torch.isfinite(out["depth_map"]).all())

@@ -1,6 +1,6 @@
 """The driver's contract with bench.py: one JSON line with the fields it parses (metric, value, unit, n_gpus, steps, warmup,
-ms_per_step, higher_is_better, scaling, vs_baseline, dtype, data, config.workload, roofline{bound, achieved, peak, unit, frac,
-traffic}, cpu_baseline{value, unit, cores, kind, sample})."""
+ms_per_step, higher_is_better, scaling, vs_baseline, dtype, data, config.workload); with --full also roofline{bound, achieved,
+peak, unit, frac, traffic}, cpu_baseline{value, unit, cores, kind, sample} and the measurements beside the headline."""
 import importlib
 import json
 import os
@@ -20,9 +20,32 @@ def run_bench(*args):
     return json.loads(lines[0])
 
 
+def test_full_is_an_option_and_off_by_default(monkeypatch):
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "2", "--warmup", "1"])
+    assert bench.parse().full is False
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "2", "--warmup", "1", "--full"])
+    assert bench.parse().full is True
+
+
+@pytest.mark.gpu
+def test_plain_bench_line_is_the_headline():
+    """Without --full the line is the headline alone: the contract's fields, and none of what --full measures beside it."""
+    j = run_bench("--gpus", "1", "--steps", "2", "--warmup", "1", "--size", "64", "--samples", "16")
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype",
+              "data", "config"):
+        assert k in j, k
+    assert j["metric"] == "rays_per_sec" and j["unit"] == "rays/s" and j["n_gpus"] == 1 and j["steps"] == 2 and j["warmup"] == 1
+    assert j["higher_is_better"] is True and j["dtype"] == "f32" and j["maps_finite"] is True
+    assert abs(j["value"] - j["config"]["rays_total"] / (j["ms_per_step"] * 1e-3)) < 1e-3 * j["value"]
+    for k in ("roofline", "trained_like", "beside_headline", "cpu_baseline", "vs_cpu", "early_term", "config4_1024"):
+        assert k not in j, k
+
+
 @pytest.mark.gpu
 def test_bench_line_has_the_contracts_fields():
-    j = run_bench("--steps", "2", "--warmup", "1", "--size", "64", "--samples", "16", "--cpu-seconds", "0.5")
+    j = run_bench("--full", "--steps", "2", "--warmup", "1", "--size", "64", "--samples", "16", "--cpu-seconds", "0.5")
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype",
               "data", "config", "roofline", "cpu_baseline"):
         assert k in j, k
@@ -48,7 +71,7 @@ def test_bench_line_has_the_contracts_fields():
 
 @pytest.mark.gpu
 def test_bench_early_termination_line():
-    j = run_bench("--steps", "2", "--warmup", "1", "--size", "256", "--samples", "48", "--early-term", "--no-cpu-baseline", "--no-extras")
+    j = run_bench("--full", "--steps", "2", "--warmup", "1", "--size", "256", "--samples", "48", "--early-term", "--no-cpu-baseline", "--no-extras")
     assert j["config"]["early_term"] is True and 0.0 < j["early_term"]["samples_evaluated_frac"] <= 1.0
     assert j["roofline"]["samples_evaluated_frac"] == j["early_term"]["samples_evaluated_frac"]
 
@@ -155,10 +178,10 @@ def test_bench_starts_its_own_ranks():
     """`python bench.py --gpus 2` with no WORLD_SIZE in the environment (how a driver might issue the SCALE run) launches its two
     ranks itself -- RCCL when two devices are visible, the gloo dry run with both ranks on cuda:0 otherwise -- and relays rank 0's
     single line: the strong-scaling flow of one frame (libs/renders/BaseRender.py:160-184 as N ranks x one launch) plus the
-    1024x1024 frame of BASELINE.json configs[3]."""
+    1024x1024 frame of BASELINE.json configs[3], which --full measures."""
     import torch
     extra = {} if torch.cuda.device_count() >= 2 else {"GPNERF_BENCH_BACKEND": "gloo"}
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--size", "128"],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--size", "128", "--full"],
                          capture_output=True, text=True, timeout=900, env=_env_without_ranks(**extra))
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]

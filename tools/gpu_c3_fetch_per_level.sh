@@ -3,7 +3,7 @@ cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 out=gpurun_out/c3_fetch; rm -rf $out; mkdir -p $out
 for c in "FETCH_SIZE" "WRITE_SIZE" "TCC_HIT_sum TCC_MISS_sum"; do
   d=$out/$(echo $c | cut -d' ' -f1)
-  rocprofv3 --pmc $c --output-format csv -d $d -- python3 bench.py --steps 2 --warmup 1 --samples 128 --early-term --no-cpu-baseline --no-extras > $d.log 2>&1
+  rocprofv3 --pmc $c --output-format csv -d $d -- python3 bench.py --full --steps 2 --warmup 1 --samples 128 --early-term --no-cpu-baseline --no-extras > $d.log 2>&1
 done
 python3 - <<'PY'
 import csv, glob, collections

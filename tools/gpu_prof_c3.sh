@@ -1,10 +1,11 @@
 # rocprofv3 kernel trace of the configs[2] bench: durations of the per-segment launches of one frame
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
-rm -rf gpurun_out/c3_prof; mkdir -p gpurun_out/c3_prof
-rocprofv3 --kernel-trace --output-format csv -d gpurun_out/c3_prof -- python3 bench.py --steps 4 --warmup 2 ${ARGS:---samples 128 --early-term} --no-cpu-baseline --no-extras > gpurun_out/c3_prof/bench.json 2> gpurun_out/c3_prof/err.txt
-python3 - <<'PY'
-import csv, glob
-f = glob.glob("gpurun_out/c3_prof/**/*kernel_trace.csv", recursive=True)[0]
+o=${1:?usage: tools/gpu_prof_c3.sh <output directory>}/c3_prof
+rm -rf $o; mkdir -p $o
+rocprofv3 --kernel-trace --output-format csv -d $o -- python3 bench.py --full --steps 4 --warmup 2 ${ARGS:---samples 128 --early-term} --no-cpu-baseline --no-extras > $o/bench.json 2> $o/err.txt
+python3 - "$o" <<'PY'
+import csv, glob, sys
+f = glob.glob(f"{sys.argv[1]}/**/*kernel_trace.csv", recursive=True)[0]
 rows = sorted(csv.DictReader(open(f)), key=lambda r: int(r["Start_Timestamp"]))
 ks = [r for r in rows if "render_fused_kernel" in r["Kernel_Name"]]
 import os

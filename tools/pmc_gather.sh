@@ -12,7 +12,7 @@ i=0
 while read -r counters; do
   [ -z "$counters" ] && continue
   i=$((i+1))
-  timeout 150 rocprofv3 --pmc $counters --output-format csv -d $out/pass$i -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline "$@" > $out/pass$i.log 2>&1
+  timeout 150 rocprofv3 --pmc $counters --output-format csv -d $out/pass$i -- python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline "$@" > $out/pass$i.log 2>&1
   echo "pass $i ($counters): rc=$?"
 done <<'LIST'
 TA_TA_BUSY_sum TA_FLAT_READ_WAVEFRONTS_sum GRBM_GUI_ACTIVE

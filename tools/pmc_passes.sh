@@ -10,7 +10,7 @@ i=0
 while read -r counters; do
   [ -z "$counters" ] && continue
   i=$((i+1))
-  rocprofv3 --pmc $counters --output-format csv -d $out/pass$i -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline "$@" > $out/pass$i.log 2>&1
+  rocprofv3 --pmc $counters --output-format csv -d $out/pass$i -- python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline "$@" > $out/pass$i.log 2>&1
   echo "pass $i ($counters): rc=$?"
 done <<'LIST'
 SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_MFMA
