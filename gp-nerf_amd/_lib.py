@@ -91,6 +91,7 @@ FLAG_SPLIT_GUARD = 32
 FLAG_REF_ORDER = 64
 FLAG_NO_EXITS = 128
 FLAG_SHARED_DEVICE = 256
+FLAG_DENSITY_ONLY = 512
 FOLD_FIRST_LEVEL = 2
 
 # every symbol include/gpnerf_hip.h declares: (restype, argtypes)
@@ -169,6 +170,8 @@ SYMBOLS = {
     "gpnerf_patch_order": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gpnerf_density_lattice": (C.c_int, [C.POINTER(GpnerfFrame), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_int32,
                                          C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gpnerf_query_points": (C.c_int, [C.POINTER(GpnerfFrame), C.c_void_p, C.c_int64, C.c_uint32, C.POINTER(C.c_double), C.c_void_p,
+                                      C.c_void_p, C.c_void_p]),
     "gpnerf_mesh_workspace_bytes": (C.c_int64, [C.POINTER(C.c_int32)]),
     "gpnerf_mesh_count": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_float, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "gpnerf_mesh_emit": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_float, C.c_void_p, C.c_size_t, C.c_int64, C.c_int64,

@@ -2699,6 +2699,96 @@ __global__ void __launch_bounds__(LAT_WAVES * 64, LAT_WAVES / 4) density_lattice
 }
 
 // ---------------------------------------------------------------------------------------------
+// the radiance field at caller-given points: NeRFHead.forward (trainhead.py:159-163) in the reference-order form
+// ---------------------------------------------------------------------------------------------
+// One lane per point, 32 consecutive points of the caller's list per wavefront (the two lane halves split K, as in the sample loop
+// and density_lattice_kernel); persistent workgroups, the reference-order head image staged once per workgroup.  Each point runs
+// the same device functions as the fused kernel's FORM_F32 step and the lattice kernel: the four volume levels (multiply-then-add
+// taps; ELU(bias) where all 32 lanes' features are zero), the sigma feature layer, Projector.compute of the three views, mean /
+// variance, the density branch and -- unless COLOUR is false -- the colour branch.  Optional: the occupancy cull of
+// GPNERF_FLAG_OCC_CULL (a culled point gets zeros; a tile whose 32 points are all culled stores zeros, no gather, no matrix work),
+// and points given in index units of a padded lattice cube (marching-cubes vertices), mapped as lattice_axis() makes its values.
+constexpr int QRY_WAVES = 8;
+struct QueryArgs {            // the kernel's only argument, read through the kernarg segment (as render_fused_kernel's)
+    FrameK fr;
+    const float* pts;         // [n][3], device
+    long n, n_tiles;
+    int neg;                  // Projector(neg_ray)
+    int cull;                 // GPNERF_FLAG_OCC_CULL
+    int lattice;              // pts are lattice indices: p = lo + (v - pad) * step, in double
+    double lo[3], step[3], pad;
+    float* raw;               // [n][4] = rgb, sigma
+    float* alpha;             // [n] or nullptr
+};
+typedef const __attribute__((address_space(4))) QueryArgs* query_ptr;
+
+template <bool COLOUR>
+__global__ void __launch_bounds__(QRY_WAVES * 64, QRY_WAVES / 4) field_points_kernel(const QueryArgs) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    query_ptr ka = (query_ptr)__builtin_amdgcn_kernarg_segment_ptr();
+    {
+        const f32x4* src = reinterpret_cast<const f32x4*>(ka->fr.head_blob_ref);
+        f32x4* dst = reinterpret_cast<f32x4*>(lds);
+        for (int i = threadIdx.x; i < gpl::BLOB_FLOATS / 4; i += QRY_WAVES * 64) dst[i] = src[i];
+    }
+    __syncthreads();
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, n = lane & 31, half = lane >> 5;
+    for (long tile = (long)blockIdx.x * QRY_WAVES + wave; tile < ka->n_tiles; tile += (long)gridDim.x * QRY_WAVES) {
+        query_ptr kt = (query_ptr)__builtin_amdgcn_kernarg_segment_ptr();         // re-read per tile (see render_tile)
+        asm volatile("" : "+s"(kt));
+        const __attribute__((address_space(4))) FrameK& fr = kt->fr;
+        const long p = tile * 32 + n;
+        const bool active = p < kt->n;
+        const long q = active ? p : kt->n - 1;                         // (the tail's idle lanes repeat the last point)
+        float px = kt->pts[q * 3 + 0], py = kt->pts[q * 3 + 1], pz = kt->pts[q * 3 + 2];
+        if (kt->lattice) {
+            // lattice_axis(): value i = float32(lo + i * step) in float64, multiply then add (the build keeps them unfused)
+            px = (float)(kt->lo[0] + ((double)px - kt->pad) * kt->step[0]);
+            py = (float)(kt->lo[1] + ((double)py - kt->pad) * kt->step[1]);
+            pz = (float)(kt->lo[2] + ((double)pz - kt->pad) * kt->step[2]);
+        }
+        float gx, gy, gz;
+        grid_coords(fr, px, py, pz, gx, gy, gz);
+        bool keep = active;
+        if (kt->cull)
+            keep = keep && sample_occupancy(fr.occ, fr.vol_dhw[0][0], fr.vol_dhw[0][1], fr.vol_dhw[0][2], gx, gy, gz) > 0.f;
+        float sigma = 0.f, rgb[3] = {0.f, 0.f, 0.f};
+        if (__ballot(keep) & 0xffffffffull) {
+            // SparseConvNet.forward sampling (:113-122) and the sigma feature layer: test_forward (trainhead.py:61-76)
+            float fv[64], sf[32];
+#pragma unroll
+            for (int l = 0; l < GPNERF_LEVELS; ++l)
+                gather_volume<true>(fr.vol[l], fr.vol_dhw[l][0], fr.vol_dhw[l][1], fr.vol_dhw[l][2], gx, gy, gz, half, fv + 16 * l);
+            unsigned bits = 0u;
+#pragma unroll
+            for (int t = 0; t < 64; t += 2) bits |= __builtin_bit_cast(unsigned, fv[t]) | __builtin_bit_cast(unsigned, fv[t + 1]);
+            if (__all((bits << 1) == 0u)) geo_bias_ref(lds, lane, sf);      // all volume features zero: ELU(bias), same bits
+            else {
+                float fk[64];
+#pragma unroll
+                for (int l = 0; l < GPNERF_LEVELS; ++l) interleave16(fv + 16 * l, fk + 16 * l);
+                geo_eval_ref(lds, lane, fk, sf);
+            }
+            // Projector.compute (BaseRender.py:326-363), fused_mean_variance, the density branch + masked_fill, the colour branch
+            float xv[NV][18], vrgb[NV][3], mv[36];
+            const float nvalid = gather_views<FORM_F32>(fr, px, py, pz, kt->neg != 0, half, xv, vrgb);
+            mean_var_ref(xv, mv);
+            mlp_density_ref(lds, lane, sf, mv, nvalid, sigma);
+            if constexpr (COLOUR) {
+                Stamps st;
+                mlp_colour_ref(lds, lane, xv, mv, rgb, st);
+            }
+            if (!keep) { sigma = 0.f; rgb[0] = 0.f; rgb[1] = 0.f; rgb[2] = 0.f; }
+        }
+        if (active && half == 0) {
+            f32x4 rw; rw[0] = rgb[0]; rw[1] = rgb[1]; rw[2] = rgb[2]; rw[3] = sigma;
+            *reinterpret_cast<f32x4*>(kt->raw + p * 4) = rw;
+            if (kt->alpha) kt->alpha[p] = keep ? 1.f - expf(-sigma) : 0.f;     // sigma2alpha, as density_lattice_kernel
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
 // stage entry points: the same device functions as the fused kernel, one stage per launch
 // ---------------------------------------------------------------------------------------------
 // get_sampling_points + pts_to_can_pts + get_grid_coords (BaseRender.py:35-73): one lane per sample
@@ -3314,6 +3404,10 @@ int device_ready(int* cus) {
                    hipFuncSetAttribute(reinterpret_cast<const void*>(&head_forward_kernel<FUSED_WAVES, 2>),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes) == hipSuccess &&
                    hipFuncSetAttribute(reinterpret_cast<const void*>(&density_lattice_kernel),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sizeof(float) * gpl::BLOB_FLOATS)) == hipSuccess &&
+                   hipFuncSetAttribute(reinterpret_cast<const void*>(&field_points_kernel<true>),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sizeof(float) * gpl::BLOB_FLOATS)) == hipSuccess &&
+                   hipFuncSetAttribute(reinterpret_cast<const void*>(&field_points_kernel<false>),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sizeof(float) * gpl::BLOB_FLOATS)) == hipSuccess;
         }
         (void)hipGetLastError();
@@ -4132,6 +4226,42 @@ int gpnerf_density_lattice(const GpnerfFrame* f, const float* axis_x, const floa
     const long wgs = (a.n_tiles + LAT_WAVES - 1) / LAT_WAVES;
     const unsigned grid = (unsigned)(wgs < n_cus ? wgs : n_cus);
     hipLaunchKernelGGL(density_lattice_kernel, dim3(grid), dim3(LAT_WAVES * 64), sizeof(float) * gpl::BLOB_FLOATS, S_(stream), a);
+    return launch_status();
+}
+
+int gpnerf_query_points(const GpnerfFrame* f, const float* pts, int64_t n_points, uint32_t flags, const double* lattice, float* raw,
+                        float* alpha, void* stream) {
+    if (!f || n_points < 0 || (flags & ~(GPNERF_FLAG_NEG_RAY | GPNERF_FLAG_OCC_CULL | GPNERF_FLAG_DENSITY_ONLY))) return GPNERF_E_ARG;
+    if (!f->head_blob_ref || ((flags & GPNERF_FLAG_OCC_CULL) && !f->occ)) return GPNERF_E_ARG;
+    FrameK k;
+    if (!to_framek(f, k, true, true)) return GPNERF_E_ARG;
+    if (n_points == 0) return GPNERF_OK;
+    if (!pts || !raw) return GPNERF_E_ARG;
+    if (flags & GPNERF_FLAG_OCC_CULL) k.voxel[0] = k.voxel[1] = k.voxel[2] = 0.005f;   // demo_render.py:91 `xyz / 0.005`
+    int n_cus = 0;
+    if (device_ready(&n_cus) != GPNERF_OK) return GPNERF_E_DEVICE;
+    QueryArgs a;
+    a.fr = k;
+    a.pts = pts;
+    a.n = (long)n_points;
+    a.n_tiles = (a.n + 31) / 32;
+    a.neg = (flags & GPNERF_FLAG_NEG_RAY) != 0;
+    a.cull = (flags & GPNERF_FLAG_OCC_CULL) != 0;
+    a.lattice = lattice != nullptr;
+    for (int i = 0; i < 3; ++i) {
+        a.lo[i] = lattice ? lattice[i] : 0.0;
+        a.step[i] = lattice ? lattice[3 + i] : 0.0;
+    }
+    a.pad = lattice ? lattice[6] : 0.0;
+    a.raw = raw;
+    a.alpha = alpha;
+    // one workgroup per CU (the head image fills most of its LDS), persistent over the tiles
+    const long wgs = (a.n_tiles + QRY_WAVES - 1) / QRY_WAVES;
+    const unsigned grid = (unsigned)(wgs < n_cus ? wgs : n_cus);
+    if (flags & GPNERF_FLAG_DENSITY_ONLY)
+        hipLaunchKernelGGL(field_points_kernel<false>, dim3(grid), dim3(QRY_WAVES * 64), sizeof(float) * gpl::BLOB_FLOATS, S_(stream), a);
+    else
+        hipLaunchKernelGGL(field_points_kernel<true>, dim3(grid), dim3(QRY_WAVES * 64), sizeof(float) * gpl::BLOB_FLOATS, S_(stream), a);
     return launch_status();
 }
 

@@ -693,6 +693,52 @@ def density_lattice(frame, axes, neg_ray=False, pad=MESH_PAD):
     return cube, n_kept
 
 
+def lattice_of(axes, voxel_size, pad=MESH_PAD):
+    """query_points' `lattice` for the padded cube of `axes` (lattice_axes(box, voxel_size)): (lo [3] float64 = the float32 axis
+    starts widened, step [3] float64 = the voxel size lattice_axis() multiplied by, pad)."""
+    lo = np.array([np.float64(a[0]) if len(a) else 0.0 for a in axes], dtype=np.float64)
+    return lo, np.asarray(voxel_size, dtype=np.float64).ravel()[:3].copy(), int(pad)
+
+
+def query_points(frame, pts, neg_ray=False, occ_cull=False, want=("rgb", "sigma"), lattice=None):
+    """gpnerf_query_points: the radiance field (NeRFHead.forward in the reference-order form) at pts [n,3] (device float32,
+    contiguous): a dict of device tensors, "rgb" [n,3] and "sigma" [n] (views of the reference's `raw` layout [n,4], also returned
+    as "raw") and, if wanted, "alpha" [n] (1 - exp(-sigma)).  Without "rgb" in `want` the colour branch is left out (raw's rgb
+    columns are 0).  occ_cull: the progressive renderer's occupancy cull (GPNERF_FLAG_OCC_CULL: grid coordinates with the literal
+    0.005, points whose occupancy interpolates to 0 get zeros).  lattice: (lo[3], step[3], pad) -- pts are then index units of
+    the padded lattice cube (marching-cubes vertices), mapped on the device to lo + (v - pad) * step in float64."""
+    lib = L.lib()
+    _require_gpu(pts, "pts")
+    if pts.dtype != torch.float32 or not pts.is_contiguous() or pts.dim() != 2 or pts.shape[1] != 3:
+        raise L.GpnerfError(f"query_points: expected contiguous float32 points [n,3], got {pts.dtype} {tuple(pts.shape)}")
+    unknown = set(want) - {"rgb", "sigma", "alpha", "raw"}
+    if unknown:
+        raise L.GpnerfError(f"query_points: unknown outputs {sorted(unknown)}")
+    if frame.c.head_blob_ref is None:
+        raise L.GpnerfError("query_points: the frame's head blob must be pack_head()'s tensor (it carries the reference-order image)")
+    if occ_cull and not frame.c.occ:
+        frame.build_occupancy()
+    dev = pts.device
+    n = pts.shape[0]
+    raw = torch.empty((n, 4), device=dev, dtype=torch.float32)
+    alpha = torch.empty((n,), device=dev, dtype=torch.float32) if "alpha" in want else None
+    flags = (L.FLAG_NEG_RAY if neg_ray else 0) | (L.FLAG_OCC_CULL if occ_cull else 0) | (0 if "rgb" in want else L.FLAG_DENSITY_ONLY)
+    lat = None
+    if lattice is not None:
+        lo, step, pad = lattice
+        lat = (C.c_double * 7)(*[float(v) for v in np.asarray(lo, np.float64).ravel()[:3]],
+                               *[float(v) for v in np.asarray(step, np.float64).ravel()[:3]], float(pad))
+    L.check(lib.gpnerf_query_points(C.byref(frame.c), pts.data_ptr() if n else None, n, flags, lat,
+                                    raw.data_ptr() if n else None, alpha.data_ptr() if alpha is not None and n else None,
+                                    _stream_ptr(dev)), "gpnerf_query_points")
+    res = {"raw": raw, "sigma": raw[:, 3]}
+    if "rgb" in want:
+        res["rgb"] = raw[:, :3]
+    if alpha is not None:
+        res["alpha"] = alpha
+    return res
+
+
 def marching_cubes(cube, iso=1.0 / 50.0):
     """gpnerf_mesh_count + gpnerf_mesh_emit on a device float32 cube [X,Y,Z]: (vertices float32 [nv,3], faces int32 [nf,3]), device.
     The two counts are the call's one device-to-host read (they size the outputs).  The workspace (8 bytes per cube point) is
@@ -721,9 +767,12 @@ def marching_cubes(cube, iso=1.0 / 50.0):
 def extract_mesh(frame, voxel_size, bounds_min, Rh, Th, neg_ray=False, iso=1.0 / 50.0, host=None):
     """The geometry mode of demo_render.py's render_rays (:166-175, 249-311, 366-376) on the device: the box of the occupied voxels,
     the lattice, the alpha cube and its marching-cubes mesh.  Two host reads: the box (6 values) and the mesh counts (2).
-    Returns {"cube" (device [X+20,Y+20,Z+20]), "vertices", "faces" (device), "axes", "can_bounds", "n_kept" (device int64)}."""
+    Returns {"cube" (device [X+20,Y+20,Z+20]), "vertices", "faces" (device), "axes", "can_bounds", "n_kept" (device int64),
+    "lattice" (lattice_of(axes): query_points at the vertices as they come)}."""
     box = mesh_box(frame, voxel_size, bounds_min, Rh, Th, host=host)
-    axes = lattice_axes(box, host[0] if host is not None else voxel_size)
+    vs = host[0] if host is not None else voxel_size
+    axes = lattice_axes(box, vs)
     cube, n_kept = density_lattice(frame, axes, neg_ray=neg_ray)
     verts, faces = marching_cubes(cube, iso)
-    return {"cube": cube, "vertices": verts, "faces": faces, "axes": axes, "can_bounds": box, "n_kept": n_kept}
+    return {"cube": cube, "vertices": verts, "faces": faces, "axes": axes, "can_bounds": box, "n_kept": n_kept,
+            "lattice": lattice_of(axes, vs)}

@@ -88,30 +88,51 @@ def case_tables():
 
 
 class Mesh:
-    """vertices float64 [nv,3], faces int64 [nf,3] (trimesh's names); export() writes a binary little-endian PLY."""
+    """vertices float64 [nv,3], faces int64 [nf,3] (trimesh's names), vertex_colors float32 [nv,3] in [0, 1] or None; export() writes a
+    binary little-endian PLY."""
 
-    def __init__(self, vertices, faces):
+    def __init__(self, vertices, faces, vertex_colors=None):
         self.vertices = np.ascontiguousarray(vertices, dtype=np.float64).reshape(-1, 3)
         self.faces = np.ascontiguousarray(faces, dtype=np.int64).reshape(-1, 3)
+        self.vertex_colors = None
+        if vertex_colors is not None:
+            self.vertex_colors = np.ascontiguousarray(vertex_colors, dtype=np.float32).reshape(-1, 3)
+            if len(self.vertex_colors) != len(self.vertices):
+                raise ValueError(f"{len(self.vertex_colors)} vertex colours for {len(self.vertices)} vertices")
 
     def __repr__(self):
-        return f"Mesh(vertices={len(self.vertices)}, faces={len(self.faces)})"
+        c = "" if self.vertex_colors is None else ", coloured"
+        return f"Mesh(vertices={len(self.vertices)}, faces={len(self.faces)}{c})"
 
     def export(self, file_obj, file_type="ply"):
-        """Binary little-endian PLY: float64 x y z per vertex (the array as it is), one uint8-counted int32 index list per face."""
+        """Binary little-endian PLY: float64 x y z per vertex (the array as it is) -- followed, when the mesh has vertex colours, by
+        uchar red green blue = clip(rint(255 c), 0, 255) -- and one uint8-counted int32 index list per face."""
         if file_type != "ply":
             raise ValueError("only PLY is written (trimesh is not a dependency)")
         if len(self.faces) and (self.faces.min() < 0 or self.faces.max() >= len(self.vertices) or len(self.vertices) >= 2 ** 31):
             raise ValueError("face indices out of range for a PLY int32 list")
+        colour = ("property uchar red\nproperty uchar green\nproperty uchar blue\n" if self.vertex_colors is not None else "")
         head = ("ply\nformat binary_little_endian 1.0\n"
-                f"element vertex {len(self.vertices)}\nproperty double x\nproperty double y\nproperty double z\n"
+                f"element vertex {len(self.vertices)}\nproperty double x\nproperty double y\nproperty double z\n{colour}"
                 f"element face {len(self.faces)}\nproperty list uchar int vertex_indices\nend_header\n").encode("ascii")
         faces = np.empty(len(self.faces), dtype=[("n", "u1"), ("i", "<i4", (3,))])
         faces["n"] = 3
         faces["i"] = self.faces
-        body = self.vertices.astype("<f8").tobytes() + faces.tobytes()
+        if self.vertex_colors is None:
+            verts = self.vertices.astype("<f8").tobytes()
+        else:
+            v = np.empty(len(self.vertices), dtype=[("xyz", "<f8", (3,)), ("rgb", "u1", (3,))])
+            v["xyz"] = self.vertices
+            v["rgb"] = colour_bytes(self.vertex_colors)
+            verts = v.tobytes()
+        body = verts + faces.tobytes()
         if hasattr(file_obj, "write"):
             file_obj.write(head + body)
         else:
             with open(file_obj, "wb") as f:
                 f.write(head + body)
+
+
+def colour_bytes(c):
+    """float colours in [0, 1] -> uint8: clip(rint(255 c), 0, 255), in float32"""
+    return np.clip(np.rint(np.float32(255) * np.asarray(c, dtype=np.float32)), 0, 255).astype(np.uint8)

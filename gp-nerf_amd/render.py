@@ -35,7 +35,8 @@ from . import parallel as P_
 class Renderer(nn.Module):
     def __init__(self, encoder, nerfhead, is_train=False, neg_ray_train=False, neg_ray_val=False, n_rays=1024,
                  n_samples=64, voxel_size=(0.005, 0.005, 0.005), chunk=64, mesh_th=-1, early_term=None, term_eps=1e-5,
-                 progressive=False, split_f16=None, sharded_outputs="all", shard_group=None, encoder_graph=None, fold_levels=None, reserve_cus=None):
+                 progressive=False, split_f16=None, sharded_outputs="all", shard_group=None, encoder_graph=None, fold_levels=None, reserve_cus=None,
+                 mesh_colors=None):
         super().__init__()
         self.encoder = encoder
         self.nerfhead = nerfhead
@@ -87,6 +88,10 @@ class Renderer(nn.Module):
         # several rounds of wavefronts (512x512 full frame: -3 % kernel for -1.4 ms of producers); on a ZJU-sized frame of ~one
         # round the smaller chip quantises badly and it loses (profiles/r05/d_pipeline.txt).  Default 0.
         self.reserve_cus = int(os.environ.get("GPNERF_RESERVE_CUS", "0")) if reserve_cus is None else int(reserve_cus)
+        # mesh_colors (not in the reference, whose geometry mode returns a grey mesh): render_mesh colours every vertex with the
+        # field's rgb there (gpnerf_query_points; GP-NeRF's colour does not depend on a viewing direction).  Off by default;
+        # GPNERF_MESH_COLORS=1 turns it on from outside, e.g. for the reference's tools/inference.py run.
+        self.mesh_colors = (os.environ.get("GPNERF_MESH_COLORS", "0") == "1") if mesh_colors is None else bool(mesh_colors)
 
     # ---- helpers the reference exposes as methods (stage entry points) ----------------------------
     def _neg_ray(self, batch):
@@ -273,7 +278,9 @@ class Renderer(nn.Module):
         """The inference renderer's geometry mode (demo_render.py:166-175, 249-311, 366-376, use_rgbhead False) on the device: returns
         `mesh` (mesh.Mesh: vertices in index units of the padded cube, as mcubes gives them), `cube` (the padded alpha cube,
         float32 numpy), `time_slots`, `etime`, `rtime`.  The iso value is the reference's literal 1 / 50 (cfg.test.mesh_th is not
-        read there either).  Host reads: the frame's constants before the encoder, the box (6 values), the mesh counts (2)."""
+        read there either).  Host reads: the frame's constants before the encoder, the box (6 values), the mesh counts (2).
+        With mesh_colors, the mesh carries vertex_colors: the field's rgb at every vertex (query_points on the device, the vertices
+        as they come in index units of the padded cube), copied to the host with the vertices."""
         dev = batch["src_imgs"].device
         torch.cuda.synchronize(dev)
         te = time.time()
@@ -291,9 +298,12 @@ class Renderer(nn.Module):
         ev[2].record()
         m = F_.extract_mesh(frame, self.voxel_size, batch["bounds"][0, 0], batch["Rh"][0], batch["Th"][0], neg_ray=self._neg_ray(batch),
                             iso=M_.ISO_REFERENCE, host=box_host)
+        colours = None
+        if self.mesh_colors:
+            colours = F_.query_points(frame, m["vertices"], neg_ray=self._neg_ray(batch), want=("rgb",), lattice=m["lattice"])["rgb"]
         ev[3].record()
         cube = m["cube"].cpu().numpy()
-        mesh = M_.Mesh(m["vertices"].cpu().numpy(), m["faces"].cpu().numpy())
+        mesh = M_.Mesh(m["vertices"].cpu().numpy(), m["faces"].cpu().numpy(), colours.cpu().numpy() if colours is not None else None)
         t4 = time.time()
         etime = ev[0].elapsed_time(ev[1]) * 1e-3
         t_frame, t_mesh = ev[1].elapsed_time(ev[2]) * 1e-3, ev[2].elapsed_time(ev[3]) * 1e-3
@@ -301,6 +311,18 @@ class Renderer(nn.Module):
                 "time_slots": {"frame": t_frame, "mesh": t_mesh, "bc_time": 0.0, "sigma_c": 0.0, "bc_attn": 0.0, "sigma_attn": 0.0,
                                "sp_encode": t_frame, "bf_sigma": 0.0, "sigma_f": t_mesh},
                 "etime": etime, "rtime": max(0.0, (t4 - te) - etime)}
+
+    def query_points(self, batch, pts, want=("rgb", "sigma"), occ_cull=False):
+        """The frame's radiance field at world points pts [n,3] (device float32): the producers as render_mesh runs them (encoder,
+        volumes, frame, occupancy), then frame.query_points under the batch's neg_ray.  Returns its dict of device tensors
+        ("rgb" [n,3], "sigma" [n], "raw" [n,4], "alpha" [n] if wanted); nothing is read back to the host."""
+        consts = F_.Frame.consts_of_batch(batch, self.voxel_size)
+        prepared = self.prepare_builder_inputs(batch, consts)
+        self.nerfhead.head_blob(batch["src_imgs"].device)
+        featmaps = self.encode(batch)
+        frame = self.build_frame(batch, featmaps, consts, prepared)
+        frame.build_occupancy()
+        return F_.query_points(frame, pts, neg_ray=self._neg_ray(batch), occ_cull=occ_cull, want=want)
 
     # ---- the hot path ---------------------------------------------------------------------------------
     def _produce(self, batch):

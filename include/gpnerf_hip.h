@@ -324,6 +324,29 @@ int gpnerf_make_rays_demo(int32_t H, int32_t W, const float* Kinv, const float* 
 int gpnerf_density_lattice(const GpnerfFrame* frame, const float* axis_x, const float* axis_y, const float* axis_z, const int32_t* dims,
                            int32_t pad, int32_t neg_ray, float* cube, int64_t* n_kept, void* stream);
 
+/* gpnerf_query_points: the radiance field at n_points caller-given world points -- NeRFHead.forward (trainhead.py:159-163) in the
+ * reference-order form (GPNERF_FLAG_REF_ORDER), the arithmetic of the fused kernel's step: grid coordinates (pts_to_can_pts +
+ * get_grid_coords), the four volume levels (multiply-then-add trilinear taps), the sigma feature layer, Projector.compute of the three
+ * views, mean / variance, the density branch (0 where no view is valid) and the colour branch (sigmoid rgb).  GP-NeRF's colour does
+ * not depend on a viewing direction, so a point's rgb is the value the renderer composites there.  Bit for bit: raw at the sample
+ * points of a ray equals gpnerf_render_fused's `raw` of the reference-order form; with GPNERF_FLAG_OCC_CULL and the lattice input at
+ * the lattice's integer indices, alpha equals gpnerf_density_lattice's cube.  Points keep the caller's order (one lane per point, 32
+ * consecutive points per wavefront: spatially coherent lists run faster); the result of a point depends on that point alone.
+ *   pts: device float32 [n_points][3], world xyz -- or, with `lattice` (host double[7] = {lo[3], step[3], pad}), index units of a
+ *     padded lattice cube (gpnerf_mesh_emit's vertices as they come): each coordinate becomes p = (float)(lo + ((double)v - pad) * step),
+ *     in float64, multiply then add, unfused; at v = pad + i that is frame.lattice_axis()'s value i bit for bit when lo is the
+ *     float64 value of the float32 axis start and step the float64 voxel size;
+ *   raw: device float32 [n_points][4] = r, g, b, sigma (the reference's `raw` layout); alpha: device float32 [n_points] or NULL,
+ *     1 - exp(-sigma) as gpnerf_density_lattice computes it;
+ *   flags: GPNERF_FLAG_NEG_RAY (Projector(neg_ray)); GPNERF_FLAG_OCC_CULL (grid coordinates with the literal voxel size 0.005, a point
+ *     whose occupancy frame->occ interpolates to 0 gets raw = 0 and alpha = 0; a 32-point tile with no kept point does no gather and
+ *     no matrix work); GPNERF_FLAG_DENSITY_ONLY (the colour branch is left out, rgb is written as 0).  Other flags are refused.
+ * Needs frame->head_blob_ref, the volumes and the image half of the frame (and frame->occ with GPNERF_FLAG_OCC_CULL).  n_points == 0
+ * is a no-op. */
+#define GPNERF_FLAG_DENSITY_ONLY 512u   /* gpnerf_query_points: sigma (and alpha) only, rgb written as 0 */
+int gpnerf_query_points(const GpnerfFrame* frame, const float* pts, int64_t n_points, uint32_t flags, const double* lattice, float* raw,
+                        float* alpha, void* stream);
+
 /* Marching cubes over a float32 cube [X][Y][Z] (dims: host int32[3], each >= 2, X * Y * Z <= 2^28; x slowest), iso value iso
  * (the reference's literal 1 / 50 at :372).  Two calls with the same cube, dims, iso and workspace:
  *   gpnerf_mesh_count: counts: device int64[2] <- {n_vertices, n_triangles}; the workspace (gpnerf_mesh_workspace_bytes(dims)

@@ -1,0 +1,281 @@
+"""GPU: the field query (gpnerf_query_points) -- against the reference's own stage vectors, bit for bit against the fused kernel's `raw`
+and the density lattice's cube, order / size / determinism, the coloured mesh of the geometry mode, and its speed against the stage
+composition."""
+import glob
+import importlib
+import os
+import sys
+from types import SimpleNamespace as NS
+
+import numpy as np
+import pytest
+import torch
+import torch.nn.functional as TF
+
+from golden_cases import GOLDEN_DIR, load, scene_of, sha_inputs
+from test_field_host import read_ply_any
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+F = importlib.import_module("gp-nerf_amd.frame")
+M = importlib.import_module("gp-nerf_amd.mesh")
+DEV = "cuda:0"
+TOL = 1e-4          # the bound test_gpu_parity.py holds the stage vectors (st_raw) to
+
+
+def _dev(a):
+    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
+
+
+def _frame(sc, occupancy=True):
+    blob = F.pack_head(sc["head"], torch.device(DEV))
+    fr = F.Frame(_dev(sc["src_imgs"][0]), _dev(sc["featmaps"]), [_dev(v) for v in sc["volumes"]], _dev(sc["src_Ks"][0]),
+                 _dev(sc["src_poses"][0]), sc["Rh"][0], sc["Th"][0], sc["bounds"][0, 0], sc["voxel_size"], sc["out_sh"][0], blob)
+    if occupancy:
+        fr.build_occupancy()
+    return fr, blob
+
+
+def _bits(t):
+    return t.contiguous().view(torch.int32)
+
+
+def _stage_cases():
+    return sorted(os.path.basename(p)[:-4] for p in glob.glob(os.path.join(GOLDEN_DIR, "*.npz")) if "st_pts" in np.load(p).files)
+
+
+@pytest.mark.parametrize("name", _stage_cases())
+def test_query_at_the_reference_sample_points_is_its_raw(name):
+    """NeRFHead.forward at the reference's own sample points (st_pts) against the reference's `raw` there (st_raw)"""
+    z, meta = load(name)
+    sc = scene_of(meta)
+    fr, _ = _frame(sc, occupancy=False)
+    pts = _dev(z["st_pts"].reshape(-1, 3))
+    q = F.query_points(fr, pts, neg_ray=meta["neg_ray"], want=("rgb", "sigma", "alpha"))
+    raw = q["raw"].cpu().numpy()
+    ref = z["st_raw"].reshape(-1, 4)
+    err = float(np.abs(raw.astype(np.float64) - ref).max())
+    print(f"{name}: query vs the reference's raw max-abs {err:.2e} over {len(ref)} points")
+    assert np.isfinite(raw).all() and err <= TOL
+    assert np.array_equal(q["rgb"].cpu().numpy(), raw[:, :3]) and np.array_equal(q["sigma"].cpu().numpy(), raw[:, 3])
+    a = q["alpha"].cpu().numpy()
+    assert float(np.abs(a - (1.0 - np.exp(-raw[:, 3].astype(np.float64)))).max()) <= 1e-6
+    if name == "allmasked_s32":
+        assert not raw[:, 3].any(), "no view sees these points: sigma must be exactly 0"
+
+
+@pytest.fixture(scope="module")
+def dense(syn):
+    """a synthetic frame of 4 096 rays x 32 samples (131 072 points), and the fused kernel's reference-order `raw` on it"""
+    sc = syn.make_scene(H=64, W=64, seed=23, pose="random", bias_std=0.1, sigma_bias=0.5)
+    fr, blob = _frame(sc)
+    rays = _dev(np.concatenate([sc["ray_o"][0], sc["ray_d"][0], sc["near"][0][:, None], sc["far"][0][:, None]], 1))
+    S = 32
+    raw = F.render_fused(fr, rays, S, want=("raw",))["raw"]
+    pts, _, _ = F.sample_points(fr, rays, S)
+    torch.cuda.synchronize()
+    return NS(sc=sc, fr=fr, blob=blob, rays=rays, S=S, raw=raw.reshape(-1, 4), pts=pts.reshape(-1, 3).contiguous())
+
+
+def test_query_is_the_fused_kernels_raw_bit_for_bit(dense):
+    assert dense.pts.shape[0] >= 100_000
+    q = F.query_points(dense.fr, dense.pts)
+    got, want = q["raw"], dense.raw
+    diff = (_bits(got) != _bits(want)).any(1)
+    assert float(want[:, 3].max()) > 0
+    assert not bool(diff.any()), f"{int(diff.sum())} of {len(diff)} points differ; max-abs {float((got - want).abs().max()):.2e}"
+
+
+def test_order_and_determinism(dense):
+    pts = dense.pts
+    full = F.query_points(dense.fr, pts)["raw"]
+    again = F.query_points(dense.fr, pts)["raw"]
+    assert torch.equal(_bits(full), _bits(again)), "two calls must give the same bytes"
+    perm = torch.from_numpy(np.random.default_rng(3).permutation(pts.shape[0])).to(DEV)
+    shuffled = F.query_points(dense.fr, pts.index_select(0, perm).contiguous())["raw"]
+    assert torch.equal(_bits(shuffled), _bits(full.index_select(0, perm))), "a permutation of the points permutes the outputs"
+    dens = F.query_points(dense.fr, pts, want=("sigma", "alpha"))
+    assert torch.equal(_bits(dens["sigma"]), _bits(full[:, 3])), "density only: the same sigma"
+    assert "rgb" not in dens and not bool(dens["raw"][:, :3].any())
+    part = F.query_points(dense.fr, pts[:33].contiguous())["raw"]
+    assert part.shape == (33, 4) and torch.equal(_bits(part), _bits(full[:33]))
+    empty = F.query_points(dense.fr, pts[:0].contiguous(), want=("rgb", "sigma", "alpha"))
+    assert empty["raw"].shape == (0, 4) and empty["rgb"].shape == (0, 3) and empty["alpha"].shape == (0,)
+
+
+def test_many_rounds_of_wavefronts(dense):
+    """>= 2 M points (many rounds of the persistent workgroups): the 131 072 sample points 16 times, shuffled"""
+    reps = 16
+    base = F.query_points(dense.fr, dense.pts)["raw"]
+    idx = torch.from_numpy(np.random.default_rng(9).integers(0, dense.pts.shape[0], reps * dense.pts.shape[0])).to(DEV)
+    big = dense.pts.index_select(0, idx).contiguous()
+    assert big.shape[0] >= 2_000_000
+    got = F.query_points(dense.fr, big)["raw"]
+    assert torch.equal(_bits(got), _bits(base.index_select(0, idx)))
+
+
+def test_query_refuses_bad_point_tensors(dense):
+    with pytest.raises(F.L.GpnerfError):
+        F.query_points(dense.fr, dense.pts.double())
+    with pytest.raises(F.L.GpnerfError):
+        F.query_points(dense.fr, dense.pts.t())
+    with pytest.raises(F.L.GpnerfError):
+        F.query_points(dense.fr, dense.pts.reshape(-1))
+    with pytest.raises(F.L.GpnerfError):
+        F.query_points(dense.fr, dense.pts, want=("normals",))
+
+
+@pytest.fixture(scope="module")
+def body(syn):
+    """test_gpu_mesh.py's person-shaped frame (capsule limbs, 1.0 x 1.8 x 0.5 m box) at the demo's 5 mm lattice, its alpha cube and
+    the lattice points the occupancy keeps"""
+    sc = syn.make_scene(H=64, W=64, seed=11, focal_mul=6.0, pose="random", body="capsules", bias_std=0.1, sigma_bias=0.5, vol_relu=True)
+    fr, blob = _frame(sc)
+    box = F.mesh_box(fr, sc["voxel_size"], sc["bounds"][0, 0], sc["Rh"][0], sc["Th"][0])
+    axes = F.lattice_axes(box, sc["voxel_size"])
+    cube, n_kept = F.density_lattice(fr, axes)
+    ax = [torch.from_numpy(a).to(DEV) for a in axes]
+    pts = torch.stack(torch.meshgrid(*ax, indexing="ij"), -1).reshape(-1, 3)
+    # grid coordinates with the demo's 0.005 (gpnerf_sample_points on zero-length rays), occupancy > 0 (a non-negative volume: the
+    # decision does not depend on the summation order), as tools/mesh_time.py selects them
+    rays = torch.zeros((pts.shape[0], 8), device=DEV)
+    rays[:, :3] = pts
+    saved = tuple(fr.c.voxel)
+    for a in range(3):
+        fr.c.voxel[a] = 0.005
+    try:
+        _, _, grid = F.sample_points(fr, rays, 1)
+    finally:
+        for a in range(3):
+            fr.c.voxel[a] = saved[a]
+    grid = grid.reshape(-1, 3)
+    occ = TF.grid_sample(fr.occ[None, None], grid[None, None, None], align_corners=True, padding_mode="zeros").reshape(-1)
+    kept = torch.nonzero(occ > 0).squeeze(1)
+    del rays
+    torch.cuda.synchronize()
+    return NS(sc=sc, fr=fr, blob=blob, axes=axes, cube=cube, n_kept=n_kept, pts=pts, kp=pts.index_select(0, kept).contiguous(),
+              kg=grid.index_select(0, kept).contiguous())
+
+
+def test_culled_lattice_query_is_the_density_lattice_bit_for_bit(body):
+    axes, pad = body.axes, F.MESH_PAD
+    X, Y, Z = (len(a) for a in axes)
+    assert X * Y * Z > 5_000_000, (X, Y, Z)
+    idx = [torch.arange(n, device=DEV, dtype=torch.float32) + pad for n in (X, Y, Z)]
+    v = torch.stack(torch.meshgrid(*idx, indexing="ij"), -1).reshape(-1, 3).contiguous()
+    q = F.query_points(body.fr, v, occ_cull=True, want=("rgb", "sigma", "alpha"), lattice=F.lattice_of(axes, body.sc["voxel_size"]))
+    inner = body.cube[pad:-pad, pad:-pad, pad:-pad].reshape(-1)
+    diff = _bits(q["alpha"]) != _bits(inner)
+    assert not bool(diff.any()), f"{int(diff.sum())} of {diff.numel()} lattice points differ"
+    culled = q["alpha"] == 0
+    assert int((~culled).sum()) <= int(body.n_kept.item()) and int(body.n_kept.item()) > 0
+    dens = F.query_points(body.fr, v, occ_cull=True, want=("sigma", "alpha"), lattice=F.lattice_of(axes, body.sc["voxel_size"]))
+    assert torch.equal(_bits(dens["alpha"]), _bits(q["alpha"])) and torch.equal(_bits(dens["sigma"]), _bits(q["sigma"]))
+    # the world points themselves (the lattice values, no index mapping) give the same alpha
+    w = F.query_points(body.fr, body.pts, occ_cull=True, want=("sigma", "alpha"))
+    assert torch.equal(_bits(w["alpha"]), _bits(q["alpha"]))
+
+
+def test_query_is_faster_than_the_stage_composition(body):
+    """the query against gather + volume + head launches on the same kept points (alternating, device events)"""
+    fr, blob, kp, kg = body.fr, body.blob, body.kp, body.kg
+    t_q, t_stage = [], []
+    for _ in range(5):
+        e = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+        e[0].record()
+        F.query_points(fr, kp)
+        e[1].record()
+        feat, mask = F.project_gather(fr, kp)
+        vol = F.sample_volume(fr, kg)
+        F.head_forward(blob, vol, feat, mask)
+        e[2].record()
+        torch.cuda.synchronize()
+        t_q.append(e[0].elapsed_time(e[1]))
+        t_stage.append(e[1].elapsed_time(e[2]))
+    q, stage = float(np.median(t_q[1:])), float(np.median(t_stage[1:]))
+    print(f"query {q:.3f} ms vs stage composition {stage:.3f} ms on {kp.shape[0]} kept points")
+    assert q < stage
+
+
+@pytest.fixture(scope="module")
+def demo():
+    p = os.path.join(ROOT, "gp-nerf_amd", "plugins")
+    if p not in sys.path:
+        sys.path.insert(0, p)
+    import types
+    m = types.ModuleType("fixed_encoder")
+
+    class Enc(torch.nn.Module):
+        def forward(self, x):
+            raise AssertionError("tests pass featmaps in the batch")
+
+    m.build_encoder = lambda cfg: Enc()
+    sys.modules["fixed_encoder"] = m
+    return importlib.import_module("hip_demo_render")
+
+
+def _renderer(demo, sc):
+    cfg = NS(encoder=NS(file="fixed_encoder", name="resnet34", out_ch=32),
+             head=NS(file="hip_head", rgb=NS(use_rgbhead=False),
+                     sigma=NS(code_dim=32, n_heads=4, n_layers=4, n_smpl=6890, outdims=[32, 32, 32, 32])),
+             dataset=NS(train=NS(name="zju_mocap", chunk=400), test=NS(name="zju_mocap", chunk=2000),
+                        voxel_size=[float(x) for x in sc["voxel_size"]]),
+             train=NS(n_rays=1024, n_samples=32), test=NS(mesh_th=50))
+    r = demo.build_render(cfg).to(DEV).eval()
+    sd = r.state_dict()
+    for k, v in sc["head"].items():
+        sd["nerfhead." + k] = torch.from_numpy(v.copy())
+    r.load_state_dict(sd, strict=True)
+    return r
+
+
+def _batch(sc):
+    keys = ("src_imgs", "src_Ks", "src_poses", "feature", "coord", "out_sh", "bounds", "Rh", "R", "Th")
+    b = {k: _dev(sc[k]) for k in keys}
+    b["featmaps"] = _dev(sc["featmaps"])
+    b["volumes"] = [_dev(v) for v in sc["volumes"]]
+    b["target_K"] = _dev(sc["target_K"])
+    b["target_pose"] = _dev(sc["target_pose"])
+    return b
+
+
+@pytest.mark.parametrize("name", ["mesh/mesh_body", "mesh/mesh_trained"])
+def test_coloured_mesh_is_the_plain_mesh_with_the_fields_colours(name, demo, monkeypatch, tmp_path):
+    z, meta = load(name)
+    sc = scene_of(meta)
+    assert sha_inputs(sc) == meta["sha256_inputs"]
+    monkeypatch.delenv("GPNERF_MESH_COLORS", raising=False)
+    plain_r = _renderer(demo, sc)
+    monkeypatch.setenv("GPNERF_MESH_COLORS", "1")          # how tools/inference.py switches it on (build_render passes no option)
+    col_r = _renderer(demo, sc)
+    assert plain_r.mesh_colors is False and col_r.mesh_colors is True
+    b = _batch(sc)
+    with torch.no_grad():
+        plain = plain_r.render(b)
+        col = col_r.render(b)
+    pm, cm = plain["mesh"], col["mesh"]
+    assert pm.vertex_colors is None and cm.vertex_colors is not None
+    assert np.array_equal(plain["cube"].view(np.int32), col["cube"].view(np.int32))
+    assert np.array_equal(pm.vertices, cm.vertices) and np.array_equal(pm.faces, cm.faces) and len(cm.faces) > 0
+    c = cm.vertex_colors
+    assert c.dtype == np.float32 and c.shape == (len(cm.vertices), 3) and np.all((c >= 0) & (c <= 1))
+    # the query at the mapped vertices, on a frame built from the same inputs
+    fr, _ = _frame(sc)
+    box = F.mesh_box(fr, sc["voxel_size"], sc["bounds"][0, 0], sc["Rh"][0], sc["Th"][0])
+    axes = F.lattice_axes(box, sc["voxel_size"])
+    q = F.query_points(fr, _dev(cm.vertices.astype(np.float32)), neg_ray=meta["neg_ray"], want=("rgb",),
+                       lattice=F.lattice_of(axes, sc["voxel_size"]))
+    assert np.array_equal(q["rgb"].cpu().numpy().view(np.int32), c.view(np.int32))
+    print(f"{name}: {len(cm.vertices)} vertices, colour range [{c.min():.3f}, {c.max():.3f}]")
+    path = tmp_path / "c.ply"
+    cm.export(str(path))
+    el, props = read_ply_any(path.read_bytes())
+    assert props == ["x", "y", "z", "red", "green", "blue"]
+    rgb = np.stack([el["vertex"][k] for k in ("red", "green", "blue")], 1)
+    assert np.array_equal(rgb, M.colour_bytes(c)) and np.array_equal(el["face"]["i"].astype(np.int64), cm.faces)
+    # Renderer.query_points: the producers, then the query -- the same values as on the hand-built frame
+    pts = _dev(np.stack(np.meshgrid(*[a[::7] for a in axes], indexing="ij"), -1).reshape(-1, 3))
+    with torch.no_grad():
+        rq = col_r.query_points(b, pts)
+    fq = F.query_points(fr, pts, neg_ray=meta["neg_ray"])
+    assert torch.equal(_bits(rq["rgb"]), _bits(fq["rgb"])) and torch.equal(_bits(rq["sigma"]), _bits(fq["sigma"]))
