@@ -3205,67 +3205,56 @@ void pack_layer_ref(int L, const float* W, const float* b, int n_out, int n_in, 
 // workgroup and, when the caller lends a workspace, how many waves share the samples of one tile (split), minimising
 // rounds x step time x samples per unit.
 constexpr int GPNERF_MAX_SPLIT = 8;     // waves that may share one tile's samples
-constexpr size_t QUEUE_BYTES = 256;     // head of the workspace: 8 tile-queue counters (one per XCD), padded
+size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
+// the split geometry's partial composites: 16 floats per ray and segment
+size_t part_bytes(int64_t n_rays, int split) { return (size_t)n_rays * split * 16 * sizeof(float); }
+struct Geometry { int waves, split; };
+
+Geometry choose_geometry(int64_t tiles, int S, bool may_split, size_t ws_bytes, int64_t n_rays, int n_cus) {
+    const int64_t cus = n_cus > 0 ? n_cus : 256;
+    Geometry best{8, 1};
+    double best_t = 1e300;
+    for (int split = 1; split <= GPNERF_MAX_SPLIT; split *= 2) {
+        if (split > 1 && (!may_split || S / split < 8 || ws_bytes < part_bytes(n_rays, split))) continue;
+        for (int w = GPNERF_MAX_WAVES; w >= 1; --w) {
+            const int64_t blocks = (tiles * split + w - 1) / w;
+            const int64_t rounds = (blocks + cus - 1) / cus;
+            const double step = w <= 4 ? 82.0 : (w <= 8 ? 133.0 : 190.0);  // kilo-cycles per 32-sample step (measured)
+            const double t = (double)rounds * step * ((double)S / split) + (split > 1 ? 60.0 : 0.0);
+            if (t < best_t * 0.97) { best_t = t; best = Geometry{w, split}; }   // ties: wider workgroup, no split
+        }
+    }
+    return best;
+}
+// persistent workgroups of GPNERF_MAX_WAVES wavefronts: one per CU, no more than the tiles fill
+unsigned full_grid(int64_t tiles, int n_cus) {
+    const int64_t wg = (tiles + GPNERF_MAX_WAVES - 1) / GPNERF_MAX_WAVES;
+    return (unsigned)(wg < n_cus ? wg : n_cus);
+}
+
+// The workspace of gpnerf_render_fused, as plan_render lays it out.  Head: the tile queue's counters, then the split geometry's
+// partial composites or the colour list; the chain block of early termination starts at 0 instead, the list behind it.  Tail:
+// the cull mask, then the split form's guard at the very end.  Each region's size and inner layout is defined here, once.
+constexpr size_t QUEUE_BYTES = 256;     // 8 tile-queue counters (one per XCD) per launch on the queue (the remainder launch's: words 8..15), padded
 // frame-level deferral (colour_units_kernel): per launch slot its entry count, and room for an entry and a result per SAMPLE (a
 // frame whose every weight is non-zero); frames beyond 2^26 samples (1024 x 1024 x 64: 2.1 GB) keep the tile-level passes
-size_t align256(size_t v);
 bool gdef_fits(int64_t n_rays, int32_t n_samples) { return n_samples <= 256 && n_rays * (int64_t)n_samples <= ((int64_t)1 << 26); }
 constexpr size_t GDEF_HEAD_BYTES = 256;        // gd_ctrl: the unit queue's counters, the entry / unit count, the tickets, the wavefronts that are done listing
 // entries: one per sample + a unit per VISIT of a work unit (the unified form pads what a visit leaves to a whole unit; a 32-ray tile
 // is one visit, or up to eight where it runs as units of several samples per step); flags: one word per unit
 size_t gdef_entries(int64_t n_rays, int32_t n_samples) { return (size_t)n_rays * n_samples + ((size_t)((n_rays + 31) / 32) * 8 + 64) * 32; }
-size_t gdef_flag_bytes(int64_t n_rays, int32_t n_samples) { return align256((gdef_entries(n_rays, n_samples) / 32 + 64) * sizeof(unsigned)); }
-size_t gdef_bytes(int64_t n_rays, int32_t n_samples) {
-    return GDEF_HEAD_BYTES + align256((size_t)n_rays * sizeof(int)) + gdef_flag_bytes(n_rays, n_samples) + gdef_entries(n_rays, n_samples) * sizeof(uint4) +
-           (size_t)n_rays * n_samples * sizeof(f32x4);
-}
-// Early termination walks the samples in segments of chain_len(), one launch per segment over the rays still alive (see
-// gpnerf_render_fused); the workspace then holds a control block (per segment: 8 queue counters + the length of its output
-// list), two ray lists (written and read alternately) and 16 floats of parked state per ray.
-// One launch of the fused kernel: which arithmetic (`sel`), whether the colour branch is deferred sample by sample (render_tile), and
-// the sample loop (chained segments / culled) as template arguments.  Dynamic LDS = the form's head image (+ the split form's guard
-// slots) + the wavefronts' colour queues.
-enum { SEL_REF = 0, SEL_FOLD = 1, SEL_SPLIT = 2, SEL_GUARD = 3 };
-// Every form defers the colour branch (round 6; rounds 1-5 kept it in the step for the split-precision forms).  Round 5 built the
-// split forms' deferral (bench frame 7.3 -> 6.4 ms) and did not ship it: ONE build's unguarded instantiation gave colour passes
-// 10-30 % off, the same wrong values on every box, cured by any change that moved the schedule (an opaque copy of the regathered
-// inputs, `volatile` on lo_pair's asm, lo_pair written without asm) and not by waits around the pass.  The mechanism class is
-// now demonstrated on the hardware (tools/micro/asm_producer_hazards.hip, profiles/r06/i_asm_producer_hazards.txt): gfx950 does
-// not interlock a VALU write of a VGPR with an MFMA that reads it as a source operand in the next issue slot -- the MFMA gets the
-// register's previous contents, in every lane alike -- LLVM pads the producers it can see, and lo_pair's v_fma_mixlo/hi_f16 are
-// inline assembly it cannot: whether one lands directly in front of its MFMA is the scheduler's accident, which is exactly how
-// the failure came and went with unrelated edits.  (That build itself can no longer be reproduced -- revision c9a579c without the
-// opaque copy compiles to a schedule with one instruction in between and is bit-exact today, profiles/r06/i_split_defer_rebuild.txt
-// -- so the instance stays inferred; the class is measured.)  Since round 6 every fragment that becomes an MFMA operand passes
-// through settle_operand(), which carries the wait state itself, and tools/isa_mfma_hazards.py fails the CPU suite on any
-// inline-asm producer closer to its MFMA than the measured requirement (tests/test_abi.py).
-template <int FORM, bool CHAIN, bool CULL>
-void launch_form(bool deferred, dim3 grid, dim3 block, size_t lds, hipStream_t stream, const KArgs& ka) {
-    if constexpr ((FORM == FORM_F32 || FORM == FORM_F32_FOLD) && !CULL) {
-        // (the unified form's wavefronts wait for each other -- every one reports before any leaves -- which assumes the grid becomes
-        //  resident without depending on another tenant that waits the same way: GPNERF_FLAG_SHARED_DEVICE selects the second kernel.
-        //  As a cooperative launch, which guarantees residency, it cost 0.04 ms per call and, with the next frame's producers on a
-        //  second stream, the whole overlap of the pipelined evaluation loop: 7.0 -> 8.5 ms per frame)
-        if (deferred && ka.gd_ent && ka.gd_flag) { hipLaunchKernelGGL((render_fused_kernel<FORM, CHAIN, false, true, true, true>), grid, block, lds, stream, ka); return; }
-        if (deferred && ka.gd_ent) { hipLaunchKernelGGL((render_fused_kernel<FORM, CHAIN, false, true, true>), grid, block, lds, stream, ka); return; }
-    }
-    if (deferred) { hipLaunchKernelGGL((render_fused_kernel<FORM, CHAIN, CULL, true>), grid, block, lds, stream, ka); return; }
-    hipLaunchKernelGGL((render_fused_kernel<FORM, CHAIN, CULL, false>), grid, block, lds, stream, ka);
-}
-template <bool CHAIN, bool CULL>
-void launch_render(int sel, bool deferred, dim3 grid, dim3 block, hipStream_t stream, const KArgs& ka) {
-    const size_t f32 = sizeof(float) * gpl::BLOB_FLOATS + DEFER_LDS_BYTES, split = sizeof(unsigned) * gph::BLOB_WORDS + DEFER_LDS_BYTES;
-    switch (sel) {
-        case SEL_GUARD: launch_form<FORM_SPLIT_GUARD, CHAIN, CULL>(deferred, grid, block, split + GUARD_LDS_SLOTS * 8, stream, ka); break;
-        case SEL_SPLIT: launch_form<FORM_SPLIT, CHAIN, CULL>(deferred, grid, block, split, stream, ka); break;
-        case SEL_FOLD:  launch_form<FORM_F32_FOLD, CHAIN, CULL>(deferred, grid, block, f32, stream, ka); break;
-        default:        launch_form<FORM_F32, CHAIN, CULL>(deferred, grid, block, f32, stream, ka); break;
-    }
+// the list's block: gd_ctrl at 0, then gd_cnt, gd_flag, gd_ent and gd_rgbw (KArgs)
+struct ListLayout { size_t cnt, flag, ent, rgbw, bytes; };
+ListLayout list_layout(int64_t n_rays, int32_t n_samples) {
+    const size_t cnt = GDEF_HEAD_BYTES, flag = cnt + align256((size_t)n_rays * sizeof(int));
+    const size_t ent = flag + align256((gdef_entries(n_rays, n_samples) / 32 + 64) * sizeof(unsigned));
+    const size_t rgbw = ent + gdef_entries(n_rays, n_samples) * sizeof(uint4);
+    return ListLayout{cnt, flag, ent, rgbw, rgbw + (size_t)n_rays * n_samples * sizeof(f32x4)};
 }
 
+// early termination: the samples in segments of chain_len(), one launch each (plan_render)
 constexpr int CHAIN_SEG = 16;
 constexpr int CHAIN_MAX_SEGS = 64;
-size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 int chain_len(int S) {
     const int least = (S + CHAIN_MAX_SEGS - 1) / CHAIN_MAX_SEGS;
     return CHAIN_SEG > least ? CHAIN_SEG : least;
@@ -3289,38 +3278,201 @@ int chain_schedule(int S, int* begins) {
 // n <= ceil(S / chain_len(S)) <= CHAIN_MAX_SEGS
 int chain_segs(int S) { return (S + chain_len(S) - 1) / chain_len(S); }
 size_t chain_chunks(int64_t n_rays) { return (size_t)((n_rays + 2047) / 2048); }       // LIST_CHUNK entries each
-// control block: per segment 8 queue counters, the length of its output list, and one survivor counter per LIST_CHUNK input entries
-size_t chain_ctrl_bytes(int n_seg, int64_t n_rays) { return align256((size_t)n_seg * (9 + chain_chunks(n_rays)) * sizeof(unsigned)); }
+// the chain block: a control block (per segment 8 queue counters, the length of its output list, and one survivor counter per
+// LIST_CHUNK input entries), two ray lists (written and read alternately), the sparse list and 16 floats of parked state per ray
+struct ChainLayout { size_t ctrl, list, sparse, part, bytes; };      // the ray lists at ctrl and at ctrl + list
+ChainLayout chain_layout(int64_t n_rays, int S) {
+    const size_t ctrl = align256((size_t)chain_segs(S) * (9 + chain_chunks(n_rays)) * sizeof(unsigned));
+    const size_t list = align256((size_t)n_rays * sizeof(int));
+    return ChainLayout{ctrl, list, ctrl + 2 * list, ctrl + 3 * list, ctrl + 3 * list + (size_t)n_rays * 16 * sizeof(float)};
+}
+// 0: the samples are not walked in segments (a single one, or rays beyond 32-bit list entries)
+size_t chain_bytes(int64_t n_rays, int S) { return chain_segs(S) < 2 || n_rays >= ((int64_t)1 << 31) ? 0 : chain_layout(n_rays, S).bytes; }
+
 // range guard of the split form: header (flag count, the fix-up launch's queue counters) + one word per tile, at the workspace's end
 size_t guard_bytes(int64_t n_rays) {
     return align256((GUARD_HEADER_WORDS + (size_t)((n_rays + RAYS_PER_WAVE - 1) / RAYS_PER_WAVE)) * sizeof(unsigned));
 }
 // occupancy culling: keep bits per ray, then per tile its step count and its place in the longest-first order
-size_t cull_tiles(int64_t n_rays) { return (size_t)((n_rays + RAYS_PER_WAVE - 1) / RAYS_PER_WAVE); }
-size_t cull_mask_bytes(int64_t n_rays) {
-    return align256((size_t)n_rays * 2 * sizeof(unsigned long long)) + 2 * align256(cull_tiles(n_rays) * sizeof(int));
+struct MaskLayout { size_t steps, order, bytes; };
+MaskLayout mask_layout(int64_t n_rays) {
+    const size_t steps = align256((size_t)n_rays * 2 * sizeof(unsigned long long));
+    const size_t per_tile = align256((size_t)((n_rays + RAYS_PER_WAVE - 1) / RAYS_PER_WAVE) * sizeof(int));
+    return MaskLayout{steps, steps + per_tile, steps + 2 * per_tile};
 }
-size_t chain_bytes(int64_t n_rays, int S) {
-    if (chain_segs(S) < 2 || n_rays >= ((int64_t)1 << 31)) return 0;
-    return chain_ctrl_bytes(chain_segs(S), n_rays) + 3 * align256((size_t)n_rays * sizeof(int)) + (size_t)n_rays * 16 * sizeof(float);
-}
-struct Geometry { int waves, split; };
 
-Geometry choose_geometry(int64_t tiles, int S, bool may_split, size_t ws_bytes, int64_t n_rays, int n_cus) {
-    const int64_t cus = n_cus > 0 ? n_cus : 256;
-    Geometry best{8, 1};
-    double best_t = 1e300;
-    for (int split = 1; split <= GPNERF_MAX_SPLIT; split *= 2) {
-        if (split > 1 && (!may_split || S / split < 8 || ws_bytes < (size_t)n_rays * split * 16 * sizeof(float))) continue;
-        for (int w = GPNERF_MAX_WAVES; w >= 1; --w) {
-            const int64_t blocks = (tiles * split + w - 1) / w;
-            const int64_t rounds = (blocks + cus - 1) / cus;
-            const double step = w <= 4 ? 82.0 : (w <= 8 ? 133.0 : 190.0);  // kilo-cycles per 32-sample step (measured)
-            const double t = (double)rounds * step * ((double)S / split) + (split > 1 ? 60.0 : 0.0);
-            if (t < best_t * 0.97) { best_t = t; best = Geometry{w, split}; }   // ties: wider workgroup, no split
-        }
+// The arithmetic of a call: the split-precision forms under GPNERF_FLAG_SPLIT_F16; otherwise the fp32 form in reference order
+// (FORM_F32, head_blob_ref) unless the frame carries folded volumes and the caller did not ask for the reference's order.  The
+// guarded split form's fix-up launch is the reference-order form too.
+enum { SEL_REF = 0, SEL_FOLD = 1, SEL_SPLIT = 2, SEL_GUARD = 3 };
+int render_sel(uint32_t flags, const FrameK& k) {
+    if (flags & GPNERF_FLAG_SPLIT_F16) return (flags & GPNERF_FLAG_SPLIT_GUARD) ? SEL_GUARD : SEL_SPLIT;
+    return k.vol_fold[GPNERF_LEVELS - 1] && !(flags & GPNERF_FLAG_REF_ORDER) ? SEL_FOLD : SEL_REF;
+}
+// Where a sample's colour branch runs: in the STEP (GPNERF_FLAG_NO_EXITS, a `raw` output); deferred to each WAVEfront's own queue
+// (render_tile); LISTed for the launch as a whole and evaluated by colour_units_kernel; or listed and evaluated by the listing
+// launch's own wavefronts once they have no tile left (UNIFIED).
+enum class Colour { STEP, WAVE, LIST, UNIFIED };
+// The render launches of a call: STATIC, one unit per wave (a split tile's segment, perhaps); persistent workgroups on the tile
+// QUEUE; the same over the whole rounds and a launch of the segmented form over the remaining tiles (QUEUE_REMAINDER); ONE launch
+// of the segmented form whose units are the whole rounds' tiles and the remainder's (REMAINDER_UNITS); early termination's
+// CHAINED segment launches.  Behind them: the list's evaluation, the split geometry's combine, the guard's fix-up, as planned.
+enum class Shape { STATIC, QUEUE, QUEUE_REMAINDER, REMAINDER_UNITS, CHAINED };
+struct Region { size_t off = 0, bytes = 0; };       // in the workspace; bytes == 0: not used by the call
+struct RenderPlan {
+    int sel;
+    Colour colour;
+    Shape shape;
+    Geometry g;
+    unsigned grid;              // workgroups of every render launch (of g.waves wavefronts)
+    int64_t tiles, main_rays;   // main_rays: the launch slots of the first launch (QUEUE_REMAINDER: the whole rounds)
+    Region queue, part, chain, list, mask, guard;
+};
+
+// Every decision of gpnerf_render_fused (flags: without the RESERVE_CUS bits, which n_cus has taken off; ws_bytes: 0 without a
+// workspace).  A region is placed only where the bytes left hold it.  The split partials and the list share the bytes behind the
+// queue's counters: a split geometry is static, and only a launch on the tile queue lists.
+RenderPlan plan_render(int64_t n_rays, int S, uint32_t flags, int n_cus, const GpnerfOutputs& out, const FrameK& fr, size_t ws_bytes) {
+    RenderPlan p;
+    p.sel = render_sel(flags, fr);
+    const bool split16 = p.sel == SEL_SPLIT || p.sel == SEL_GUARD, early = (flags & GPNERF_FLAG_EARLY_TERM) != 0;
+    const int64_t tiles = (n_rays + RAYS_PER_WAVE - 1) / RAYS_PER_WAVE, slots = (int64_t)n_cus * GPNERF_MAX_WAVES;
+    p.tiles = tiles;
+    p.main_rays = n_rays;
+    size_t end = ws_bytes;
+    auto tail = [&end](size_t bytes) { end = (end - bytes) & ~(size_t)255; return Region{end, bytes}; };
+    // GPNERF_FLAG_SPLIT_GUARD: the split form records the tiles in which an MFMA operand reached the f16 range, and a second
+    // launch renders exactly those again in the fp32 form (it returns at once when there are none).  (The caller has checked
+    // that the workspace holds it.)
+    if (p.sel == SEL_GUARD) p.guard = tail(guard_bytes(n_rays));
+    // occupancy culling: the keep bits of every sample in one pass before the launch (occupancy_mask_kernel); outputs that need
+    // every step written keep the in-loop test
+    const bool culling = (flags & GPNERF_FLAG_OCC_CULL) != 0 && fr.occ != nullptr;
+    const size_t mask_bytes = mask_layout(n_rays).bytes;
+    if (culling && S <= 128 && !out.weights && !out.raw && end >= QUEUE_BYTES + mask_bytes) p.mask = tail(mask_bytes);
+    const size_t part_room = end > QUEUE_BYTES ? end - QUEUE_BYTES : 0;
+    // Frame-level deferral (fp32 forms, persistent launches of whole tiles): the sample loop only LISTS the samples whose weight is
+    // not zero; the list is evaluated by the launch's own wavefronts (Colour::UNIFIED) or by colour_units_kernel, and
+    // colour_accumulate_kernel adds every ray's terms in order (see there).  The list sits behind the head's block (`at` bytes).
+    const size_t list_bytes = list_layout(n_rays, S).bytes;
+    auto list_fits = [&](size_t at) {
+        return !split16 && !(flags & GPNERF_FLAG_OCC_CULL) && gdef_fits(n_rays, S) && end >= align256(at) + list_bytes;
+    };
+    // A frame of more than ~1.25 rounds of wavefronts whose launch can list its colour work keeps whole tiles on the queue: the
+    // sample loop's tiles then cost the same and the listed colour work is balanced by construction, which is what splitting a
+    // tile's samples bought (384 x 384 x 64: 7.06 ms split in two, 6.17 ms whole; 300 / 320 / 448: the same either way; 272 x 272,
+    // 1.13 rounds, still gains from the split: 3.86 against 4.24) -- and the maps stay bit-identical to the same rays' in any
+    // other launch.
+    // (decided by the frame and the workspace alone -- not by GPNERF_FLAG_NO_EXITS or a `raw` output, whose launches list nothing: a
+    //  launch and its diagnostic twin must cut the frame the same way to be compared bit for bit)
+    const bool can_list = !early && list_fits(QUEUE_BYTES);
+    const bool may_split = part_room && !early && !out.samples_done && !(can_list && tiles * 4 >= slots * 5);
+    Geometry g = choose_geometry(tiles, S, may_split, part_room, n_rays, n_cus);
+    // A frame of q whole rounds of wavefronts plus a FEW tiles (at most an eighth of a round) ends with those few running alone,
+    // S dependent steps at one wave per CU.  The persistent launch then takes the whole rounds, and the remainder goes to the
+    // segmented form's kernel as ONE segment of all S samples: its work units put 8 samples of a ray side by side (render_tile's
+    // P), S / 8 steps each, with the plain form's arithmetic per ray (term_eps = 0: nothing is ever frozen).  Bit-identical
+    // results; 576x576x64: 18.8 -> 18.0 ms.  (A larger remainder is better left to the queue: CUs with few waves step faster.)
+    const int64_t rem_tiles = tiles % slots;
+    const bool remainder = end >= QUEUE_BYTES && !(flags & (GPNERF_FLAG_EARLY_TERM | GPNERF_FLAG_OCC_CULL)) && n_cus >= 8 &&
+                           tiles > slots && rem_tiles > 0 && rem_tiles * 8 <= slots && S >= 8;
+    if (remainder) g = Geometry{GPNERF_MAX_WAVES, 1};
+    const int64_t blocks = (tiles * g.split + g.waves - 1) / g.waves;
+    // more than one round of workgroups and nothing split: persistent workgroups + tile queue (see render_fused_kernel), whose
+    // units are whole tiles (so is every frame with a remainder)
+    const bool persistent = end >= QUEUE_BYTES && g.split == 1 && blocks > n_cus;
+    // Early termination on frames of at least one round of wavefronts: the samples are walked in segments of chain_len(), one
+    // persistent-queue launch per segment.  A ray that is opaque stops (per ray, not per tile); the rays that go on park 16
+    // floats and are appended to the next launch's list, so every launch packs the survivors 32 to a wavefront again: on the
+    // bench frame a ray needs 20 % of its samples, a fixed 32-ray tile 35-43 % (until its last ray is opaque).
+    // (frames of less than one round of waves gain nothing from it, and every XCD's queue needs workgroups of its own)
+    const size_t chain = chain_bytes(n_rays, S);
+    const bool chains = early && !culling && tiles >= slots && n_cus >= 8 && chain && end >= chain;
+    p.g = g;
+    p.grid = (unsigned)(persistent ? n_cus : blocks);
+    // ONE launch for a frame of whole rounds + a few tiles: the segmented form's kernel over all S samples as a single segment
+    // (term_eps = 0: nothing is ever frozen), whose work units are the whole rounds' 32-ray tiles at one sample per step AND the
+    // remaining tiles at eight samples of a ray per step (chain_plan), all on one tile queue.  In a lone round a SIMD's older
+    // wavefront is through its tile after ~2.7 ms and the younger after ~4.0 ms: the short remainder units fill exactly that
+    // gap, where a second launch had to wait for the first to drain.  73 689-ray frame: 4.58 -> 4.36 ms.  (Several whole rounds:
+    // the plain kernel's loop is ~2 % faster than the segmented form's, two launches win: 576x576x64 17.08 against 17.46 ms.)
+    if (remainder && tiles < 2 * slots && !out.samples_done) p.shape = Shape::REMAINDER_UNITS;
+    else if (chains) {
+        p.shape = Shape::CHAINED;
+        p.g = Geometry{GPNERF_MAX_WAVES, 1};
+        p.grid = full_grid(tiles, n_cus);
+    } else if (remainder) {
+        p.shape = Shape::QUEUE_REMAINDER;
+        p.main_rays = (tiles - rem_tiles) * RAYS_PER_WAVE;
+    } else p.shape = persistent ? Shape::QUEUE : Shape::STATIC;
+    // the head: the queue's counters are cleared for every persistent geometry (the chained launches take theirs from the chain
+    // block's control words, whose first segment's are these)
+    if (persistent) p.queue = Region{0, QUEUE_BYTES};
+    if (p.g.split > 1) p.part = Region{QUEUE_BYTES, part_bytes(n_rays, p.g.split)};
+    if (p.shape == Shape::CHAINED) p.chain = Region{0, chain};
+    // every form defers the colour branch sample by sample (render_tile) unless the exits are off or `raw` wants every rgb
+    const bool deferred = !(flags & GPNERF_FLAG_NO_EXITS) && !out.raw;
+    const bool lists = deferred && (p.shape == Shape::CHAINED ? list_fits(chain) : can_list && p.shape != Shape::STATIC);
+    // The unified form unless a remainder launch follows (with both launches unified -- the second's tickets starting where the
+    // first's list ends -- 576 squared measured 12.67 -> 12.89 ms, 370 squared 5.70 -> 6.01) or the launches are chained (every
+    // segment launch evaluating what is listed so far, the next launch's tickets starting at the list's end, measured 6.95 ->
+    // 7.86 ms on configs[2]: every 16-step visit pads its last unit and six launches each wait for their lists):
+    // 300 / 320 / 340 / 384 squared: 4.42 / 5.04 / 5.13 / 6.15 ms with the second kernel, 4.17 / 4.51 / 5.00 / 5.62 unified
+    const bool unified = lists && !(flags & GPNERF_FLAG_SHARED_DEVICE) && (p.shape == Shape::QUEUE || p.shape == Shape::REMAINDER_UNITS);
+    p.colour = !deferred ? Colour::STEP : (!lists ? Colour::WAVE : (unified ? Colour::UNIFIED : Colour::LIST));
+    if (lists) p.list = Region{p.shape == Shape::CHAINED ? align256(chain) : QUEUE_BYTES, list_bytes};
+    return p;
+}
+
+// One launch of the segmented form over all S samples as a single segment (term_eps = 0: nothing is ever frozen): launch slots
+// [first, first + items) on `grid` workgroups, its own tile queue
+KArgs one_segment(const KArgs& ka, long first, long items, unsigned* queue, unsigned grid) {
+    KArgs k = ka;
+    k.n_rays = first + items; k.split = 1; k.part = nullptr; k.dynamic = 1; k.queue = queue;
+    k.chain = k.S; k.seg = 0; k.term_eps = 0.f; k.k_begin = 0; k.k_end = k.S;
+    k.first_slot = first; k.first_items = items;
+    k.p_cap = (long)grid * GPNERF_MAX_WAVES * RAYS_PER_WAVE;
+    return k;
+}
+
+// One launch of the fused kernel: which arithmetic (`sel`), where the colour branch runs, and the sample loop (chained segments /
+// culled) as template arguments.  Dynamic LDS = the form's head image (+ the split form's guard slots) + the wavefronts' colour
+// queues.
+// Every form defers the colour branch (round 6; rounds 1-5 kept it in the step for the split-precision forms).  Round 5 built the
+// split forms' deferral (bench frame 7.3 -> 6.4 ms) and did not ship it: ONE build's unguarded instantiation gave colour passes
+// 10-30 % off, the same wrong values on every box, cured by any change that moved the schedule (an opaque copy of the regathered
+// inputs, `volatile` on lo_pair's asm, lo_pair written without asm) and not by waits around the pass.  The mechanism class is
+// now demonstrated on the hardware (tools/micro/asm_producer_hazards.hip, profiles/r06/i_asm_producer_hazards.txt): gfx950 does
+// not interlock a VALU write of a VGPR with an MFMA that reads it as a source operand in the next issue slot -- the MFMA gets the
+// register's previous contents, in every lane alike -- LLVM pads the producers it can see, and lo_pair's v_fma_mixlo/hi_f16 are
+// inline assembly it cannot: whether one lands directly in front of its MFMA is the scheduler's accident, which is exactly how
+// the failure came and went with unrelated edits.  (That build itself can no longer be reproduced -- revision c9a579c without the
+// opaque copy compiles to a schedule with one instruction in between and is bit-exact today, profiles/r06/i_split_defer_rebuild.txt
+// -- so the instance stays inferred; the class is measured.)  Since round 6 every fragment that becomes an MFMA operand passes
+// through settle_operand(), which carries the wait state itself, and tools/isa_mfma_hazards.py fails the CPU suite on any
+// inline-asm producer closer to its MFMA than the measured requirement (tests/test_abi.py).
+template <int FORM, bool CHAIN, bool CULL>
+void launch_form(Colour colour, dim3 grid, dim3 block, size_t lds, hipStream_t stream, const KArgs& ka) {
+    if constexpr ((FORM == FORM_F32 || FORM == FORM_F32_FOLD) && !CULL) {
+        // (the unified form's wavefronts wait for each other -- every one reports before any leaves -- which assumes the grid becomes
+        //  resident without depending on another tenant that waits the same way: GPNERF_FLAG_SHARED_DEVICE selects the second kernel.
+        //  As a cooperative launch, which guarantees residency, it cost 0.04 ms per call and, with the next frame's producers on a
+        //  second stream, the whole overlap of the pipelined evaluation loop: 7.0 -> 8.5 ms per frame)
+        if (colour == Colour::UNIFIED) { hipLaunchKernelGGL((render_fused_kernel<FORM, CHAIN, false, true, true, true>), grid, block, lds, stream, ka); return; }
+        if (colour == Colour::LIST) { hipLaunchKernelGGL((render_fused_kernel<FORM, CHAIN, false, true, true>), grid, block, lds, stream, ka); return; }
     }
-    return best;
+    if (colour != Colour::STEP) { hipLaunchKernelGGL((render_fused_kernel<FORM, CHAIN, CULL, true>), grid, block, lds, stream, ka); return; }
+    hipLaunchKernelGGL((render_fused_kernel<FORM, CHAIN, CULL, false>), grid, block, lds, stream, ka);
+}
+template <bool CHAIN, bool CULL>
+void launch_render(int sel, Colour colour, dim3 grid, dim3 block, hipStream_t stream, const KArgs& ka) {
+    const size_t f32 = sizeof(float) * gpl::BLOB_FLOATS + DEFER_LDS_BYTES, split = sizeof(unsigned) * gph::BLOB_WORDS + DEFER_LDS_BYTES;
+    switch (sel) {
+        case SEL_GUARD: launch_form<FORM_SPLIT_GUARD, CHAIN, CULL>(colour, grid, block, split + GUARD_LDS_SLOTS * 8, stream, ka); break;
+        case SEL_SPLIT: launch_form<FORM_SPLIT, CHAIN, CULL>(colour, grid, block, split, stream, ka); break;
+        case SEL_FOLD:  launch_form<FORM_F32_FOLD, CHAIN, CULL>(colour, grid, block, f32, stream, ka); break;
+        default:        launch_form<FORM_F32, CHAIN, CULL>(colour, grid, block, f32, stream, ka); break;
+    }
 }
 
 hipStream_t S_(void* s) { return reinterpret_cast<hipStream_t>(s); }
@@ -3775,28 +3927,11 @@ int gpnerf_render_fused(const GpnerfFrame* f, const float* rays, int64_t n_rays,
     FrameK k;
     if (!to_framek(f, k, true, true)) return GPNERF_E_ARG;
     if (n_rays >= ((int64_t)1 << 31)) return GPNERF_E_ARG;      // output rows are 32-bit values inside the kernel
-    const int64_t tiles = (n_rays + RAYS_PER_WAVE - 1) / RAYS_PER_WAVE;
-    const size_t lds_bytes = sizeof(float) * gpl::BLOB_FLOATS + DEFER_LDS_BYTES;       // head image + the wavefronts' colour queues (render_tile)
-    const bool split16 = (flags & GPNERF_FLAG_SPLIT_F16) != 0;
-    // the fp32 form: reference order (FORM_F32, head_blob_ref) unless the frame carries folded volumes and the caller did not ask
-    // for the reference's order; the guarded split form's fix-up launch is the reference-order form too
-    const bool folded = !split16 && k.vol_fold[GPNERF_LEVELS - 1] != nullptr && !(flags & GPNERF_FLAG_REF_ORDER);
-    if (split16 && !f->head_blob_split) return GPNERF_E_ARG;
-    if (!split16 && !folded && !f->head_blob_ref) return GPNERF_E_ARG;
-    if (folded && !f->head_blob) return GPNERF_E_ARG;
-    if (split16 && (flags & GPNERF_FLAG_SPLIT_GUARD) && !f->head_blob_ref) return GPNERF_E_ARG;
-    // GPNERF_FLAG_SPLIT_GUARD: the split form records the tiles in which an MFMA operand reached the f16 range, and a second
-    // launch renders exactly those again in the fp32 form (it returns at once when there are none).  The flags live in the
-    // last guard_bytes() of the workspace.
-    const bool guard = split16 && (flags & GPNERF_FLAG_SPLIT_GUARD) != 0;
-    unsigned* guard_words = nullptr;
-    if (guard) {
-        const size_t gb = guard_bytes(n_rays);
-        if (!workspace || workspace_bytes < QUEUE_BYTES + gb) return GPNERF_E_ARG;
-        workspace_bytes = (workspace_bytes - gb) & ~(size_t)255;
-        guard_words = reinterpret_cast<unsigned*>(static_cast<char*>(workspace) + workspace_bytes);
-        if (!zero_async(guard_words, gb, stream)) return GPNERF_E_LAUNCH;
-    }
+    const int sel = render_sel(flags, k);
+    if ((sel == SEL_SPLIT || sel == SEL_GUARD) && !f->head_blob_split) return GPNERF_E_ARG;
+    if ((sel == SEL_REF || sel == SEL_GUARD) && !f->head_blob_ref) return GPNERF_E_ARG;
+    if (sel == SEL_FOLD && !f->head_blob) return GPNERF_E_ARG;
+    if (sel == SEL_GUARD && (!workspace || workspace_bytes < QUEUE_BYTES + guard_bytes(n_rays))) return GPNERF_E_ARG;
     int n_cus = 0;
     if (device_ready(&n_cus) != GPNERF_OK) return GPNERF_E_DEVICE;
     {   // GPNERF_FLAG_RESERVE_CUS(n): plan the launch for n fewer compute units (whole XCD rounds of 8, at least 8 stay), so that
@@ -3805,254 +3940,133 @@ int gpnerf_render_fused(const GpnerfFrame* f, const float* rays, int64_t n_rays,
         if (reserve > 0) n_cus = n_cus - reserve >= 8 ? n_cus - reserve : (n_cus >= 8 ? 8 : n_cus);
         flags &= 0x00ffffffu;
     }
-    const bool culling = (flags & GPNERF_FLAG_OCC_CULL) != 0 && f->occ != nullptr;
     if (flags & GPNERF_FLAG_OCC_CULL) k.voxel[0] = k.voxel[1] = k.voxel[2] = 0.005f;   // demo_render.py:91 `xyz / 0.005`
-    // occupancy culling: the keep bits of every sample in one pass before the launch (occupancy_mask_kernel), in the last
-    // cull_mask_bytes() of the workspace (before the guard's block); outputs that need every step written keep the in-loop test
-    unsigned long long* cull_mask = nullptr;
-    if (culling && workspace && n_samples <= 128 && !out->weights && !out->raw && workspace_bytes >= QUEUE_BYTES + cull_mask_bytes(n_rays)) {
-        workspace_bytes = (workspace_bytes - cull_mask_bytes(n_rays)) & ~(size_t)255;
-        cull_mask = reinterpret_cast<unsigned long long*>(static_cast<char*>(workspace) + workspace_bytes);
-    }
-    // workspace layout: [0, QUEUE_BYTES) the tile queue's counters, then the per-segment partial composites
-    const size_t seg_bytes = workspace && workspace_bytes > QUEUE_BYTES ? workspace_bytes - QUEUE_BYTES : 0;
-    float* const seg_part = seg_bytes ? reinterpret_cast<float*>(static_cast<char*>(workspace) + QUEUE_BYTES) : nullptr;
-    // A frame of more than ~1.25 rounds of wavefronts whose launch can list its colour work (frame-level deferral, below) keeps whole
-    // tiles on the queue: the sample loop's tiles then cost the same and the listed colour work is balanced by construction, which
-    // is what splitting a tile's samples bought (384 x 384 x 64: 7.06 ms split in two, 6.17 ms whole; 300 / 320 / 448: the same
-    // either way; 272 x 272, 1.13 rounds, still gains from the split: 3.86 against 4.24) -- and the maps stay bit-identical to the
-    // same rays' in any other launch.
-    // (decided by the frame and the workspace alone -- not by GPNERF_FLAG_NO_EXITS or a `raw` output, whose launches list nothing: a
-    //  launch and its diagnostic twin must cut the frame the same way to be compared bit for bit)
-    const bool can_list = workspace && !split16 && !(flags & (GPNERF_FLAG_OCC_CULL | GPNERF_FLAG_EARLY_TERM)) &&
-                          gdef_fits(n_rays, n_samples) && workspace_bytes >= QUEUE_BYTES + gdef_bytes(n_rays, n_samples);
-    const bool may_split = seg_bytes && !(flags & GPNERF_FLAG_EARLY_TERM) && !out->samples_done &&
-                           !(can_list && tiles * 4 >= (int64_t)n_cus * GPNERF_MAX_WAVES * 5);
-    Geometry g = choose_geometry(tiles, n_samples, may_split, seg_bytes, n_rays, n_cus);
-    // whole rounds of full workgroups + the remainder's units (below) when the frame is that shape
-    const int64_t slots = (int64_t)n_cus * GPNERF_MAX_WAVES;
-    const int64_t rem_tiles = tiles % slots;
-    const bool remainder = workspace && workspace_bytes >= QUEUE_BYTES && !(flags & (GPNERF_FLAG_EARLY_TERM | GPNERF_FLAG_OCC_CULL)) &&
-                           n_cus >= 8 && tiles > slots && rem_tiles > 0 && rem_tiles * 8 <= slots && n_samples >= 8;
-    if (remainder) { g.waves = GPNERF_MAX_WAVES; g.split = 1; }
-    int64_t blocks = (tiles * g.split + g.waves - 1) / g.waves;
-    // more than one round of workgroups and nothing split: persistent workgroups + tile queue (see render_fused_kernel), whose
-    // units are whole tiles -- every dynamic launch has split == 1
-    const bool dynamic = workspace && workspace_bytes >= QUEUE_BYTES && g.split == 1 && blocks > n_cus;
-    if (dynamic) {
-        if (!zero_async(workspace, QUEUE_BYTES, stream)) return GPNERF_E_LAUNCH;
-        blocks = n_cus;
-    }
-    const bool do_remainder = remainder && dynamic;
+    const RenderPlan p = plan_render(n_rays, n_samples, flags, n_cus, *out, k, workspace ? workspace_bytes : 0);
+
+    char* const ws = static_cast<char*>(workspace);
+    auto at = [ws](const Region& r, size_t inner = 0) -> char* { return r.bytes ? ws + r.off + inner : nullptr; };
+    const ListLayout gl = list_layout(n_rays, n_samples);
+    // the counters the launch sequence starts from, in this order
+    const Region clear[] = {p.guard, p.queue, Region{p.chain.off, p.chain.bytes ? chain_layout(n_rays, n_samples).ctrl : 0},
+                            Region{p.list.off, p.list.bytes ? GDEF_HEAD_BYTES : 0},
+                            Region{p.list.off + gl.flag, p.colour == Colour::UNIFIED ? gl.ent - gl.flag : 0}};
+    for (const Region& r : clear)
+        if (r.bytes && !zero_async(ws + r.off, r.bytes, stream)) return GPNERF_E_LAUNCH;
+
     const OutK ok = to_outk(out, ray_order);
     KArgs ka;
     memset(&ka, 0, sizeof(ka));
-    ka.fr = k; ka.rays = rays; ka.n_rays = (long)n_rays; ka.S = (int)n_samples; ka.flags = (unsigned)flags; ka.term_eps = term_eps;
-    ka.out = ok; ka.split = g.split; ka.part = seg_part;
-    ka.dynamic = dynamic ? 1 : 0; ka.queue = static_cast<unsigned*>(workspace);
-    ka.guard = guard_words;
-    const dim3 full_block(GPNERF_MAX_WAVES * 64);
-    // the fp32 form over the tiles the guarded split form flagged: persistent workgroups on a queue of their own
-    auto fixup = [&]() -> int {
-        if (!guard) return launch_status();
-        if (hipGetLastError() != hipSuccess) return GPNERF_E_LAUNCH;
-        KArgs kf = ka;
-        kf.flags = (unsigned)flags & ~(GPNERF_FLAG_SPLIT_F16 | GPNERF_FLAG_SPLIT_GUARD);
-        kf.split = 1; kf.part = nullptr; kf.dynamic = 1; kf.queue = guard_words + 8;
-        kf.chain = 0; kf.seg = 0; kf.list_in = nullptr; kf.count_in = nullptr; kf.list_out = nullptr; kf.count_out = nullptr;
-        const int64_t wg = (tiles + GPNERF_MAX_WAVES - 1) / GPNERF_MAX_WAVES;
-        if (kf.cull_mask)
-            hipLaunchKernelGGL((render_fused_kernel<FORM_F32_FIXUP, false, true>), dim3((unsigned)(wg < n_cus ? wg : n_cus)), full_block, lds_bytes,
-                               S_(stream), kf);
-        else
-            hipLaunchKernelGGL((render_fused_kernel<FORM_F32_FIXUP, false>), dim3((unsigned)(wg < n_cus ? wg : n_cus)), full_block, lds_bytes,
-                               S_(stream), kf);
-        return launch_status();
-    };
+    ka.fr = k; ka.rays = rays; ka.n_rays = (long)p.main_rays; ka.S = (int)n_samples; ka.flags = (unsigned)flags; ka.term_eps = term_eps;
+    ka.out = ok; ka.split = p.g.split; ka.part = reinterpret_cast<float*>(at(p.part));
+    ka.dynamic = p.shape != Shape::STATIC ? 1 : 0; ka.queue = reinterpret_cast<unsigned*>(at(p.queue));
     ka.skip = (flags & GPNERF_FLAG_NO_EXITS) ? 0 : 3;
-    // every form defers the colour branch sample by sample (render_tile) unless the exits are off or `raw` wants every rgb
-    const bool deferred = (ka.skip & 2) && !out->raw;
-    const int sel = guard ? SEL_GUARD : (split16 ? SEL_SPLIT : (folded ? SEL_FOLD : SEL_REF));
-    // Frame-level deferral (fp32 forms, persistent launches of whole tiles): the sample loop only LISTS the samples whose weight is
-    // not zero; the list is evaluated by the launch's own wavefronts (`unify`, below) or by colour_units_kernel, and
-    // colour_accumulate_kernel adds every ray's terms in order (see there).
-    const bool gdef_ok = deferred && !culling && !cull_mask && (sel == SEL_REF || sel == SEL_FOLD) && !(flags & GPNERF_FLAG_OCC_CULL) &&
-                         gdef_fits(n_rays, n_samples) && workspace != nullptr;
-    unsigned* gd_flags = nullptr;
-    // the block sits behind what the launch's own form keeps in the workspace (`behind` bytes); false: no room, the wavefronts keep their passes
-    auto gdef_setup = [&](KArgs& kx, size_t behind) -> bool {
-        behind = align256(behind);
-        if (!gdef_ok || workspace_bytes < behind + gdef_bytes(n_rays, n_samples)) return false;
-        char* const b = static_cast<char*>(workspace) + behind;
-        if (!zero_async(b, GDEF_HEAD_BYTES, stream)) return false;
-        const size_t cnt_bytes = align256((size_t)n_rays * sizeof(int)), flag_bytes = gdef_flag_bytes(n_rays, n_samples);
-        kx.gd_ctrl = reinterpret_cast<unsigned*>(b);
-        kx.gd_cnt = reinterpret_cast<int*>(b + GDEF_HEAD_BYTES);
-        gd_flags = reinterpret_cast<unsigned*>(b + GDEF_HEAD_BYTES + cnt_bytes);
-        kx.gd_ent = reinterpret_cast<uint4*>(b + GDEF_HEAD_BYTES + cnt_bytes + flag_bytes);
-        kx.gd_rgbw = reinterpret_cast<f32x4*>(b + GDEF_HEAD_BYTES + cnt_bytes + flag_bytes + gdef_entries(n_rays, n_samples) * sizeof(uint4));
-        return true;
-    };
-    // unified form: the listing launch's own wavefronts evaluate the list once they have no tile left (render_fused_kernel, UNI),
-    // which is what fills the end of a launch whose tiles differ in cost
-    auto unify = [&](KArgs& kx, long waves) -> bool {
-        if (!kx.gd_ent || !gd_flags || (flags & GPNERF_FLAG_SHARED_DEVICE)) return false;
-        if (!zero_async(gd_flags, gdef_flag_bytes(n_rays, n_samples), stream)) return false;
-        kx.gd_flag = gd_flags;
-        kx.gd_waves = (int)waves;
-        return true;
-    };
-    // the list's evaluation and the colour map of launch slots [0, n_slots) (behind the launches that listed the entries)
-    auto colour_phase = [&](const KArgs& kx, long n_slots) -> bool {
-        if (hipGetLastError() != hipSuccess) return false;
-        if (kx.gd_flag) {       // unified form: the launch has evaluated its list itself
-            hipLaunchKernelGGL(colour_accumulate_kernel, dim3((unsigned)((n_slots + 255) / 256)), dim3(256), 0, S_(stream), (const int*)kx.gd_cnt,
-                               (const f32x4*)kx.gd_rgbw, n_slots, (int)n_samples, ok.order, ok.rgb);
-            return hipGetLastError() == hipSuccess;
-        }
-        KArgs kc = kx;
-        kc.chunk = 64;                  // units per chunk of the unit queue
-        if (sel == SEL_FOLD) hipLaunchKernelGGL((colour_units_kernel<FORM_F32_FOLD>), dim3((unsigned)n_cus), dim3(64 * UNIT_WAVES), lds_bytes, S_(stream), kc);
-        else hipLaunchKernelGGL((colour_units_kernel<FORM_F32>), dim3((unsigned)n_cus), dim3(64 * UNIT_WAVES), lds_bytes, S_(stream), kc);
-        if (hipGetLastError() != hipSuccess) return false;
-        hipLaunchKernelGGL(colour_accumulate_kernel, dim3((unsigned)((n_slots + 255) / 256)), dim3(256), 0, S_(stream), (const int*)kx.gd_cnt,
-                           (const f32x4*)kx.gd_rgbw, n_slots, (int)n_samples, ok.order, ok.rgb);
-        return hipGetLastError() == hipSuccess;
-    };
-    ka.chunk = 64;                      // tiles per chunk of the XCD queues
+    ka.chunk = 64;                      // tiles per chunk of the XCD queues (colour_units_kernel: units per chunk of its queue)
     ka.tail_p = 2;                      // samples per step of the units the last whole round is cut into (chain_plan)
-    // ONE launch for a frame of whole rounds + a few tiles: the segmented form's kernel over all S samples as a single segment
-    // (term_eps = 0: nothing is ever frozen), whose work units are the whole rounds' 32-ray tiles at one sample per step AND the
-    // remaining tiles at eight samples of a ray per step (chain_plan), all on one tile queue.  In a lone round a SIMD's older
-    // wavefront is through its tile after ~2.7 ms and the younger after ~4.0 ms: the short remainder units fill exactly that
-    // gap, where a second launch had to wait for the first to drain.  73 689-ray frame: 4.58 -> 4.36 ms.
-    if (do_remainder && tiles < 2 * slots && !out->samples_done) {      // (several whole rounds: the plain kernel's loop is ~2 % faster than the segmented form's, two launches win: 576x576x64 17.08 against 17.46 ms)
-        KArgs ku = ka;
-        ku.split = 1; ku.dynamic = 1; ku.part = nullptr;
-        ku.chain = (int)n_samples; ku.seg = 0; ku.term_eps = 0.f;
-        ku.k_begin = 0; ku.k_end = (int)n_samples;
-        ku.first_slot = 0; ku.first_items = (long)n_rays;
-        ku.list_in = nullptr; ku.count_in = nullptr; ku.list_out = nullptr; ku.count_out = nullptr; ku.chunk_cnt = nullptr;
-        ku.p_cap = (long)(slots * RAYS_PER_WAVE);
-        const bool listed = gdef_setup(ku, QUEUE_BYTES);
-        if (listed) unify(ku, (long)n_cus * GPNERF_MAX_WAVES);
-        launch_render<true, false>(sel, deferred, dim3((unsigned)n_cus), full_block, S_(stream), ku);
-        if (listed && !colour_phase(ku, (long)n_rays)) return GPNERF_E_LAUNCH;
-        return fixup();
-    }
-    // Early termination on frames of at least one round of wavefronts: the samples are walked in segments of chain_len(), one
-    // persistent-queue launch per segment.  A ray that is opaque stops (per ray, not per tile); the rays that go on park 16
-    // floats and are appended to the next launch's list, so every launch packs the survivors 32 to a wavefront again: on the
-    // bench frame a ray needs 20 % of its samples, a fixed 32-ray tile 35-43 % (until its last ray is opaque).  The launches
-    // are enqueued unconditionally -- one that finds its list empty returns before it stages anything.
-    // (frames of less than one round of waves gain nothing from it, and every XCD's queue needs workgroups of its own)
-    const size_t need_chain = (flags & GPNERF_FLAG_EARLY_TERM) && !culling && tiles >= (int64_t)n_cus * GPNERF_MAX_WAVES && n_cus >= 8
-                                  ? chain_bytes(n_rays, n_samples) : 0;
-    if (need_chain && workspace && workspace_bytes >= need_chain) {
+    ka.cull_mask = reinterpret_cast<const unsigned long long*>(at(p.mask));
+    ka.guard = reinterpret_cast<unsigned*>(at(p.guard));
+    ka.gd_ctrl = reinterpret_cast<unsigned*>(at(p.list));
+    ka.gd_cnt = reinterpret_cast<int*>(at(p.list, gl.cnt));
+    ka.gd_ent = reinterpret_cast<uint4*>(at(p.list, gl.ent));
+    ka.gd_rgbw = reinterpret_cast<f32x4*>(at(p.list, gl.rgbw));
+    if (p.colour == Colour::UNIFIED) { ka.gd_flag = reinterpret_cast<unsigned*>(at(p.list, gl.flag)); ka.gd_waves = (int)p.grid * p.g.waves; }
+
+    const dim3 grid(p.grid), block(p.g.waves * 64);
+    if (p.shape == Shape::REMAINDER_UNITS) {
+        launch_render<true, false>(p.sel, p.colour, grid, block, S_(stream), one_segment(ka, 0, (long)n_rays, ka.queue, p.grid));
+    } else if (p.shape == Shape::CHAINED) {
+        // every segment's launch is enqueued -- one that finds its list empty returns before it stages anything
+        const ChainLayout cl = chain_layout(n_rays, n_samples);
         const int n_seg = chain_segs(n_samples);
-        char* const base = static_cast<char*>(workspace);
-        unsigned* const ctrl = reinterpret_cast<unsigned*>(base);      // [n_seg][8] queue counters, [n_seg] list lengths, [n_seg][chunks] survivor counters
-        const size_t list_bytes = align256((size_t)n_rays * sizeof(int)), ctrl_bytes = chain_ctrl_bytes(n_seg, n_rays);
         const size_t n_chunks = chain_chunks(n_rays);
-        int* const lists[2] = {reinterpret_cast<int*>(base + ctrl_bytes), reinterpret_cast<int*>(base + ctrl_bytes + list_bytes)};
-        int* const sparse = reinterpret_cast<int*>(base + ctrl_bytes + 2 * list_bytes);
-        if (!zero_async(base, ctrl_bytes, stream)) return GPNERF_E_LAUNCH;
-        ka.split = 1; ka.dynamic = 1; ka.chain = chain_len(n_samples);
-        ka.part = reinterpret_cast<float*>(base + ctrl_bytes + 3 * list_bytes);
-        const int64_t wg = (tiles + GPNERF_MAX_WAVES - 1) / GPNERF_MAX_WAVES;
-        const unsigned grid = (unsigned)(wg < n_cus ? wg : n_cus);
-        ka.p_cap = (long)grid * GPNERF_MAX_WAVES * RAYS_PER_WAVE;
-        ka.first_slot = 0; ka.first_items = (long)n_rays;
-        const bool listed = gdef_setup(ka, need_chain);
+        unsigned* const ctrl = reinterpret_cast<unsigned*>(at(p.chain));   // [n_seg][8] queue counters, [n_seg] list lengths, [n_seg][chunks] survivor counters
+        int* const lists[2] = {reinterpret_cast<int*>(at(p.chain, cl.ctrl)), reinterpret_cast<int*>(at(p.chain, cl.ctrl + cl.list))};
+        int* const sparse = reinterpret_cast<int*>(at(p.chain, cl.sparse));
+        KArgs kc = ka;
+        kc.chain = chain_len(n_samples);
+        kc.part = reinterpret_cast<float*>(at(p.chain, cl.part));
+        kc.p_cap = (long)p.grid * GPNERF_MAX_WAVES * RAYS_PER_WAVE;
+        kc.first_slot = 0; kc.first_items = (long)n_rays;
         int begins[CHAIN_MAX_SEGS + 2];
         const int n_launch = chain_schedule((int)n_samples, begins);
-        // (the unified form here -- every segment launch evaluating what is listed so far, the next launch's tickets starting at the
-        //  list's end -- measured 6.95 -> 7.86 ms on configs[2]: every 16-step visit pads its last unit and six launches each wait
-        //  for their lists.  The list is evaluated once, by colour_units_kernel behind the last launch.)
         for (int sg = 0; sg < n_launch; ++sg) {
-            ka.seg = sg;
-            ka.k_begin = begins[sg]; ka.k_end = begins[sg + 1];
-            ka.queue = ctrl + 8 * sg;
-            ka.list_in = sg ? lists[(sg - 1) & 1] : nullptr;
-            ka.count_in = sg ? ctrl + 8 * n_seg + (sg - 1) : nullptr;
+            kc.seg = sg;
+            kc.k_begin = begins[sg]; kc.k_end = begins[sg + 1];
+            kc.queue = ctrl + 8 * sg;
+            kc.list_in = sg ? lists[(sg - 1) & 1] : nullptr;
+            kc.count_in = sg ? ctrl + 8 * n_seg + (sg - 1) : nullptr;
             const bool last = sg + 1 == n_launch;
-            ka.list_out = last ? nullptr : sparse;
-            ka.count_out = ctrl + 8 * n_seg + sg;
-            ka.chunk_cnt = ctrl + 9 * n_seg + (size_t)sg * n_chunks;
-            launch_render<true, false>(sel, deferred, dim3(grid), full_block, S_(stream), ka);
+            kc.list_out = last ? nullptr : sparse;
+            kc.count_out = ctrl + 8 * n_seg + sg;
+            kc.chunk_cnt = ctrl + 9 * n_seg + (size_t)sg * n_chunks;
+            launch_render<true, false>(p.sel, p.colour, grid, block, S_(stream), kc);
             if (!last)     // close the gaps of the sparse list, in order: the next launch's dense input
                 hipLaunchKernelGGL(compact_list_kernel, dim3((unsigned)n_chunks), dim3(256), 0, S_(stream), (const int*)sparse,
-                                   (const unsigned*)ka.chunk_cnt, (const unsigned*)ka.count_in, ka.first_items, lists[sg & 1], ka.count_out);
+                                   (const unsigned*)kc.chunk_cnt, (const unsigned*)kc.count_in, kc.first_items, lists[sg & 1], kc.count_out);
             if (hipGetLastError() != hipSuccess) return GPNERF_E_LAUNCH;
         }
-        if (listed && !colour_phase(ka, (long)n_rays)) return GPNERF_E_LAUNCH;
-        return fixup();
-    }
-    // A frame of q whole rounds of wavefronts plus a FEW tiles (at most an eighth of a round) ends with those few running alone,
-    // S dependent steps at one wave per CU.  The persistent launch then takes the whole rounds, and the remainder goes to the
-    // segmented form's kernel as ONE segment of all S samples: its work units put 8 samples of a ray side by side (render_tile's
-    // P), S / 8 steps each, with the plain form's arithmetic per ray (term_eps = 0: nothing is ever frozen).  Bit-identical
-    // results; 576x576x64: 18.8 -> 18.0 ms.  (A larger remainder is better left to the queue: CUs with few waves step faster.)
-    if (do_remainder) ka.n_rays = (long)((tiles - rem_tiles) * RAYS_PER_WAVE);
-    const bool gdef = dynamic && !(flags & GPNERF_FLAG_EARLY_TERM) && gdef_setup(ka, QUEUE_BYTES);
-    // unified form, unless a remainder launch follows (with both launches unified -- the second's tickets starting where the first's
-    // list ends -- 576 squared measured 12.67 -> 12.89 ms, 370 squared 5.70 -> 6.01):
-    // 300 / 320 / 340 / 384 squared: 4.42 / 5.04 / 5.13 / 6.15 ms with the second kernel, 4.17 / 4.51 / 5.00 / 5.62 unified
-    if (gdef && !do_remainder && !cull_mask) unify(ka, (long)blocks * g.waves);
-    if (cull_mask) {
-        ka.cull_mask = cull_mask;
-        {
-            hipLaunchKernelGGL(occupancy_mask_kernel, dim3((unsigned)((tiles + 3) / 4)), dim3(256), 0, S_(stream), k, rays, ok.order, (long)n_rays,
-                               (int)n_samples, (flags & GPNERF_FLAG_FLIP_SAMPLES) ? 1 : 0, cull_mask);
+    } else {
+        if (p.mask.bytes) {
+            unsigned long long* const mask = reinterpret_cast<unsigned long long*>(at(p.mask));
+            hipLaunchKernelGGL(occupancy_mask_kernel, dim3((unsigned)((p.tiles + 3) / 4)), dim3(256), 0, S_(stream), k, rays, ok.order, (long)n_rays,
+                               (int)n_samples, (flags & GPNERF_FLAG_FLIP_SAMPLES) ? 1 : 0, mask);
             if (hipGetLastError() != hipSuccess) return GPNERF_E_LAUNCH;
-            if (dynamic) {      // longest tiles first (see tile_steps_kernel)
-                char* const after = reinterpret_cast<char*>(cull_mask) + align256((size_t)n_rays * 2 * sizeof(unsigned long long));
-                int* const steps = reinterpret_cast<int*>(after);
-                int* const order = reinterpret_cast<int*>(after + align256(cull_tiles(n_rays) * sizeof(int)));
-                hipLaunchKernelGGL(tile_steps_kernel, dim3((unsigned)((n_rays + 255) / 256)), dim3(256), 0, S_(stream), (const unsigned long long*)cull_mask,
+            if (p.shape != Shape::STATIC) {      // longest tiles first (see tile_steps_kernel)
+                const MaskLayout ml = mask_layout(n_rays);
+                int* const steps = reinterpret_cast<int*>(at(p.mask, ml.steps));
+                int* const order = reinterpret_cast<int*>(at(p.mask, ml.order));
+                hipLaunchKernelGGL(tile_steps_kernel, dim3((unsigned)((n_rays + 255) / 256)), dim3(256), 0, S_(stream), (const unsigned long long*)mask,
                                    (long)n_rays, steps);
-                hipLaunchKernelGGL(tile_sort_kernel, dim3(1), dim3(SORT_THREADS), 0, S_(stream), (const int*)steps, (int)tiles, (int)n_samples, order);
+                hipLaunchKernelGGL(tile_sort_kernel, dim3(1), dim3(SORT_THREADS), 0, S_(stream), (const int*)steps, (int)p.tiles, (int)n_samples, order);
                 if (hipGetLastError() != hipSuccess) return GPNERF_E_LAUNCH;
                 ka.tile_order = order;
             }
+            launch_render<false, true>(p.sel, p.colour, grid, block, S_(stream), ka);
+        } else
+            launch_render<false, false>(p.sel, p.colour, grid, block, S_(stream), ka);
+        if (p.shape == Shape::QUEUE_REMAINDER) {       // the remainder on the second set of queue counters
+            if (hipGetLastError() != hipSuccess) return GPNERF_E_LAUNCH;
+            launch_render<true, false>(p.sel, p.colour, grid, block, S_(stream),
+                                       one_segment(ka, (long)p.main_rays, (long)(n_rays - p.main_rays), ka.queue + 8, p.grid));
         }
-        launch_render<false, true>(sel, deferred, dim3((unsigned)blocks), dim3(g.waves * 64), S_(stream), ka);
-    } else
-        launch_render<false, false>(sel, deferred, dim3((unsigned)blocks), dim3(g.waves * 64), S_(stream), ka);
-    if (do_remainder) {
-        if (hipGetLastError() != hipSuccess) return GPNERF_E_LAUNCH;
-        KArgs kr = ka;
-        kr.n_rays = (long)n_rays;
-        kr.queue = static_cast<unsigned*>(workspace) + 8;             // the second set of queue counters of the QUEUE_BYTES block
-        kr.chain = (int)n_samples; kr.seg = 0; kr.term_eps = 0.f;
-        kr.k_begin = 0; kr.k_end = (int)n_samples;
-        kr.first_slot = ka.n_rays; kr.first_items = (long)n_rays - ka.n_rays;
-        kr.list_in = nullptr; kr.count_in = nullptr;
-        kr.list_out = nullptr;                                        // nothing goes on after segment 0 of 1
-        kr.count_out = nullptr; kr.chunk_cnt = nullptr;
-        kr.part = nullptr;
-        kr.p_cap = (long)(slots * RAYS_PER_WAVE);
-        launch_render<true, false>(sel, deferred, dim3((unsigned)n_cus), full_block, S_(stream), kr);
     }
-    if (gdef && !colour_phase(ka, (long)n_rays)) return GPNERF_E_LAUNCH;     // (the remainder launch lists into the same block)
-    if (g.split > 1) {
+    if (hipGetLastError() != hipSuccess) return GPNERF_E_LAUNCH;
+    const size_t lds_bytes = sizeof(float) * gpl::BLOB_FLOATS + DEFER_LDS_BYTES;       // head image + the wavefronts' colour queues (render_tile)
+    if (p.list.bytes) {         // the list's evaluation, unless the launch's own wavefronts have done it, then every ray's colour map
+        if (p.colour == Colour::LIST) {
+            if (p.sel == SEL_FOLD) hipLaunchKernelGGL((colour_units_kernel<FORM_F32_FOLD>), dim3((unsigned)n_cus), dim3(64 * UNIT_WAVES), lds_bytes, S_(stream), ka);
+            else hipLaunchKernelGGL((colour_units_kernel<FORM_F32>), dim3((unsigned)n_cus), dim3(64 * UNIT_WAVES), lds_bytes, S_(stream), ka);
+            if (hipGetLastError() != hipSuccess) return GPNERF_E_LAUNCH;
+        }
+        hipLaunchKernelGGL(colour_accumulate_kernel, dim3((unsigned)((n_rays + 255) / 256)), dim3(256), 0, S_(stream), (const int*)ka.gd_cnt,
+                           (const f32x4*)ka.gd_rgbw, (long)n_rays, (int)n_samples, ok.order, ok.rgb);
         if (hipGetLastError() != hipSuccess) return GPNERF_E_LAUNCH;
+    }
+    if (p.g.split > 1)
         hipLaunchKernelGGL(combine_segments_kernel, dim3((unsigned)((n_rays + 255) / 256)), dim3(256), 0, S_(stream),
-                           (const float*)seg_part, (long)n_rays, (int)n_samples, g.split, ok);
+                           (const float*)ka.part, (long)n_rays, (int)n_samples, p.g.split, ok);
+    if (p.guard.bytes) {        // the fp32 form over the tiles the guarded split form flagged: persistent workgroups on the guard's queue
+        if (hipGetLastError() != hipSuccess) return GPNERF_E_LAUNCH;
+        KArgs kf = ka;
+        kf.flags = (unsigned)flags & ~(GPNERF_FLAG_SPLIT_F16 | GPNERF_FLAG_SPLIT_GUARD);
+        kf.split = 1; kf.part = nullptr; kf.dynamic = 1; kf.queue = ka.guard + 8;
+        const dim3 fgrid(full_grid(p.tiles, n_cus)), fblock(GPNERF_MAX_WAVES * 64);
+        if (kf.cull_mask) hipLaunchKernelGGL((render_fused_kernel<FORM_F32_FIXUP, false, true>), fgrid, fblock, lds_bytes, S_(stream), kf);
+        else hipLaunchKernelGGL((render_fused_kernel<FORM_F32_FIXUP, false>), fgrid, fblock, lds_bytes, S_(stream), kf);
     }
-    return fixup();
+    return launch_status();
 }
 
 size_t gpnerf_render_workspace_bytes(int64_t n_rays, int32_t n_samples) {
     if (n_rays <= 0) return 0;
-    // the tile queue's counters, plus -- only for frames small enough to profit from splitting -- room for GPNERF_MAX_SPLIT
-    // sample segments per ray, 16 floats each; or what the chained segments of an early-terminating launch need
-    const size_t plain = QUEUE_BYTES + (n_rays <= 131072 ? (size_t)n_rays * GPNERF_MAX_SPLIT * 16 * sizeof(float) : 0);
+    // the head: the tile queue's counters, plus -- only for frames small enough to profit from splitting (two rounds of a 256-CU
+    // chip) -- room for GPNERF_MAX_SPLIT sample segments per ray; or the chain block of an early-terminating launch
+    const size_t plain = QUEUE_BYTES + (n_rays <= 131072 ? part_bytes(n_rays, GPNERF_MAX_SPLIT) : 0);
     const size_t chain = chain_bytes(n_rays, n_samples);
-    // + the keep bits of occupancy culling + the split form's range-guard flags
-    // + the entry list of the frame-level colour deferral, behind whichever of the two the launch uses
-    const size_t gdef = gdef_fits(n_rays, n_samples) && n_rays > 32 * 8 * 8 ? gdef_bytes(n_rays, n_samples) : 0;
-    return align256(plain > chain ? plain : chain) + gdef + cull_mask_bytes(n_rays) + guard_bytes(n_rays);
+    // + the colour list behind the head, for launches that can use the tile queue (more than a round of full workgroups on the
+    // 8 CUs GPNERF_FLAG_RESERVE_CUS leaves at least) + the keep bits of occupancy culling + the split form's range guard
+    const bool list = gdef_fits(n_rays, n_samples) && n_rays > (int64_t)RAYS_PER_WAVE * GPNERF_MAX_WAVES * 8;
+    return align256(plain > chain ? plain : chain) + (list ? list_layout(n_rays, n_samples).bytes : 0) + mask_layout(n_rays).bytes +
+           guard_bytes(n_rays);
 }
 
 size_t gpnerf_render_guard_bytes(int64_t n_rays) { return n_rays > 0 ? guard_bytes(n_rays) : 0; }
