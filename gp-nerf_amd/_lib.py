@@ -82,6 +82,36 @@ class GpnerfOutputs(C.Structure):
     ]
 
 
+PLAN_CLEARS = 5
+PLAN_WEIGHTS, PLAN_RAW, PLAN_SAMPLES_DONE, PLAN_FOLDED, PLAN_OCC = 1, 2, 4, 8, 16
+SEL_NAMES = ("REF", "FOLD", "SPLIT", "GUARD")
+COLOUR_NAMES = ("STEP", "WAVE", "LIST", "UNIFIED")
+SHAPE_NAMES = ("STATIC", "QUEUE", "QUEUE_REMAINDER", "REMAINDER_UNITS", "CHAINED")
+REGION_NAMES = ("queue", "part", "chain", "list", "mask", "guard")
+
+
+class GpnerfRegion(C.Structure):
+    _fields_ = [("off", C.c_uint64), ("bytes", C.c_uint64)]
+
+
+class GpnerfRenderPlan(C.Structure):
+    """include/gpnerf_hip.h: what gpnerf_render_fused would do with a call (gpnerf_render_plan)"""
+    _fields_ = ([("sel", C.c_int32), ("colour", C.c_int32), ("shape", C.c_int32), ("waves", C.c_int32), ("split", C.c_int32),
+                 ("grid", C.c_uint32), ("n_cus", C.c_int32), ("reserved_", C.c_int32), ("tiles", C.c_int64), ("main_rays", C.c_int64)]
+                + [(n, GpnerfRegion) for n in REGION_NAMES] + [("clear", GpnerfRegion * PLAN_CLEARS)])
+
+    def triple(self):
+        return SHAPE_NAMES[self.shape], COLOUR_NAMES[self.colour], SEL_NAMES[self.sel]
+
+    def regions(self):
+        """{name: (off, bytes)} of the regions the call uses"""
+        return {n: (int(getattr(self, n).off), int(getattr(self, n).bytes)) for n in REGION_NAMES if getattr(self, n).bytes}
+
+    def __str__(self):
+        return (f"{'/'.join(self.triple())} waves={self.waves} split={self.split} grid={self.grid} cus={self.n_cus} tiles={self.tiles} "
+                f"main_rays={self.main_rays} " + " ".join(f"{n}@{o}+{b}" for n, (o, b) in self.regions().items()))
+
+
 FLAG_NEG_RAY = 1
 FLAG_EARLY_TERM = 2
 FLAG_OCC_CULL = 4
@@ -106,6 +136,7 @@ SYMBOLS = {
     "gpnerf_fold_volumes": (C.c_int, [C.POINTER(GpnerfFrame), C.POINTER(C.c_void_p), C.c_void_p]),
     "gpnerf_render_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int32]),
     "gpnerf_render_guard_bytes": (C.c_size_t, [C.c_int64]),
+    "gpnerf_render_plan": (C.c_int, [C.c_int64, C.c_int32, C.c_uint32, C.c_int32, C.c_uint32, C.c_size_t, C.POINTER(GpnerfRenderPlan)]),
     "gpnerf_sample_points": (C.c_int, [C.POINTER(GpnerfFrame), C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_void_p]),
     "gpnerf_sample_volume": (C.c_int, [C.POINTER(GpnerfFrame), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),

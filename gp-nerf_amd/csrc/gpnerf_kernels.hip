@@ -3305,9 +3305,9 @@ MaskLayout mask_layout(int64_t n_rays) {
 // (FORM_F32, head_blob_ref) unless the frame carries folded volumes and the caller did not ask for the reference's order.  The
 // guarded split form's fix-up launch is the reference-order form too.
 enum { SEL_REF = 0, SEL_FOLD = 1, SEL_SPLIT = 2, SEL_GUARD = 3 };
-int render_sel(uint32_t flags, const FrameK& k) {
+int render_sel(uint32_t flags, bool folded) {
     if (flags & GPNERF_FLAG_SPLIT_F16) return (flags & GPNERF_FLAG_SPLIT_GUARD) ? SEL_GUARD : SEL_SPLIT;
-    return k.vol_fold[GPNERF_LEVELS - 1] && !(flags & GPNERF_FLAG_REF_ORDER) ? SEL_FOLD : SEL_REF;
+    return folded && !(flags & GPNERF_FLAG_REF_ORDER) ? SEL_FOLD : SEL_REF;
 }
 // Where a sample's colour branch runs: in the STEP (GPNERF_FLAG_NO_EXITS, a `raw` output); deferred to each WAVEfront's own queue
 // (render_tile); LISTed for the launch as a whole and evaluated by colour_units_kernel; or listed and evaluated by the listing
@@ -3328,13 +3328,15 @@ struct RenderPlan {
     int64_t tiles, main_rays;   // main_rays: the launch slots of the first launch (QUEUE_REMAINDER: the whole rounds)
     Region queue, part, chain, list, mask, guard;
 };
+// What the planner reads of a call besides its numbers: the outputs asked for and what the frame carries (GPNERF_PLAN_*)
+struct PlanFacts { bool weights, raw, samples_done, folded, occ; };
 
 // Every decision of gpnerf_render_fused (flags: without the RESERVE_CUS bits, which n_cus has taken off; ws_bytes: 0 without a
 // workspace).  A region is placed only where the bytes left hold it.  The split partials and the list share the bytes behind the
 // queue's counters: a split geometry is static, and only a launch on the tile queue lists.
-RenderPlan plan_render(int64_t n_rays, int S, uint32_t flags, int n_cus, const GpnerfOutputs& out, const FrameK& fr, size_t ws_bytes) {
+RenderPlan plan_render(int64_t n_rays, int S, uint32_t flags, int n_cus, const PlanFacts& call, size_t ws_bytes) {
     RenderPlan p;
-    p.sel = render_sel(flags, fr);
+    p.sel = render_sel(flags, call.folded);
     const bool split16 = p.sel == SEL_SPLIT || p.sel == SEL_GUARD, early = (flags & GPNERF_FLAG_EARLY_TERM) != 0;
     const int64_t tiles = (n_rays + RAYS_PER_WAVE - 1) / RAYS_PER_WAVE, slots = (int64_t)n_cus * GPNERF_MAX_WAVES;
     p.tiles = tiles;
@@ -3347,9 +3349,16 @@ RenderPlan plan_render(int64_t n_rays, int S, uint32_t flags, int n_cus, const G
     if (p.sel == SEL_GUARD) p.guard = tail(guard_bytes(n_rays));
     // occupancy culling: the keep bits of every sample in one pass before the launch (occupancy_mask_kernel); outputs that need
     // every step written keep the in-loop test
-    const bool culling = (flags & GPNERF_FLAG_OCC_CULL) != 0 && fr.occ != nullptr;
+    const bool culling = (flags & GPNERF_FLAG_OCC_CULL) != 0 && call.occ;
     const size_t mask_bytes = mask_layout(n_rays).bytes;
-    if (culling && S <= 128 && !out.weights && !out.raw && end >= QUEUE_BYTES + mask_bytes) p.mask = tail(mask_bytes);
+    // (the mask's bytes are set aside whether or not the outputs let the launch use it: a `weights` or `raw` twin of a culled launch
+    //  then finds the same bytes for split partials and cuts the frame the same way.  Until the planner's sweep compared the `raw`
+    //  twins, the bytes of a dropped mask went to the partials, and below the documented workspace size a culled launch and its
+    //  `raw` twin could differ in the split: 31 rays x 16 at a quarter of the size, 4 x 1 with a mask against 4 x 2 without.)
+    if (culling && S <= 128 && end >= QUEUE_BYTES + mask_bytes) {
+        const Region m = tail(mask_bytes);
+        if (!call.weights && !call.raw) p.mask = m;
+    }
     const size_t part_room = end > QUEUE_BYTES ? end - QUEUE_BYTES : 0;
     // Frame-level deferral (fp32 forms, persistent launches of whole tiles): the sample loop only LISTS the samples whose weight is
     // not zero; the list is evaluated by the launch's own wavefronts (Colour::UNIFIED) or by colour_units_kernel, and
@@ -3366,7 +3375,7 @@ RenderPlan plan_render(int64_t n_rays, int S, uint32_t flags, int n_cus, const G
     // (decided by the frame and the workspace alone -- not by GPNERF_FLAG_NO_EXITS or a `raw` output, whose launches list nothing: a
     //  launch and its diagnostic twin must cut the frame the same way to be compared bit for bit)
     const bool can_list = !early && list_fits(QUEUE_BYTES);
-    const bool may_split = part_room && !early && !out.samples_done && !(can_list && tiles * 4 >= slots * 5);
+    const bool may_split = part_room && !early && !call.samples_done && !(can_list && tiles * 4 >= slots * 5);
     Geometry g = choose_geometry(tiles, S, may_split, part_room, n_rays, n_cus);
     // A frame of q whole rounds of wavefronts plus a FEW tiles (at most an eighth of a round) ends with those few running alone,
     // S dependent steps at one wave per CU.  The persistent launch then takes the whole rounds, and the remainder goes to the
@@ -3396,7 +3405,7 @@ RenderPlan plan_render(int64_t n_rays, int S, uint32_t flags, int n_cus, const G
     // wavefront is through its tile after ~2.7 ms and the younger after ~4.0 ms: the short remainder units fill exactly that
     // gap, where a second launch had to wait for the first to drain.  73 689-ray frame: 4.58 -> 4.36 ms.  (Several whole rounds:
     // the plain kernel's loop is ~2 % faster than the segmented form's, two launches win: 576x576x64 17.08 against 17.46 ms.)
-    if (remainder && tiles < 2 * slots && !out.samples_done) p.shape = Shape::REMAINDER_UNITS;
+    if (remainder && tiles < 2 * slots && !call.samples_done) p.shape = Shape::REMAINDER_UNITS;
     else if (chains) {
         p.shape = Shape::CHAINED;
         p.g = Geometry{GPNERF_MAX_WAVES, 1};
@@ -3411,7 +3420,7 @@ RenderPlan plan_render(int64_t n_rays, int S, uint32_t flags, int n_cus, const G
     if (p.g.split > 1) p.part = Region{QUEUE_BYTES, part_bytes(n_rays, p.g.split)};
     if (p.shape == Shape::CHAINED) p.chain = Region{0, chain};
     // every form defers the colour branch sample by sample (render_tile) unless the exits are off or `raw` wants every rgb
-    const bool deferred = !(flags & GPNERF_FLAG_NO_EXITS) && !out.raw;
+    const bool deferred = !(flags & GPNERF_FLAG_NO_EXITS) && !call.raw;
     const bool lists = deferred && (p.shape == Shape::CHAINED ? list_fits(chain) : can_list && p.shape != Shape::STATIC);
     // The unified form unless a remainder launch follows (with both launches unified -- the second's tickets starting where the
     // first's list ends -- 576 squared measured 12.67 -> 12.89 ms, 370 squared 5.70 -> 6.01) or the launches are chained (every
@@ -3422,6 +3431,34 @@ RenderPlan plan_render(int64_t n_rays, int S, uint32_t flags, int n_cus, const G
     p.colour = !deferred ? Colour::STEP : (!lists ? Colour::WAVE : (unified ? Colour::UNIFIED : Colour::LIST));
     if (lists) p.list = Region{p.shape == Shape::CHAINED ? align256(chain) : QUEUE_BYTES, list_bytes};
     return p;
+}
+
+// What gpnerf_render_fused and gpnerf_render_plan do in front of the planner, each rule once.  ws_bytes: 0 without a workspace.
+// The checks of a call's numbers (before the device is asked for anything):
+bool plan_args_ok(int64_t n_rays, int32_t n_samples, uint32_t flags, const PlanFacts& facts, size_t ws_bytes) {
+    if (n_rays < 1 || n_samples < 1) return false;
+    if (n_rays >= ((int64_t)1 << 31)) return false;             // output rows are 32-bit values inside the kernel
+    return render_sel(flags, facts.folded) != SEL_GUARD || ws_bytes >= QUEUE_BYTES + guard_bytes(n_rays);
+}
+// ... and the plan for a device of n_cus compute units; flags and n_cus come back as the launches use them
+RenderPlan plan_call(int64_t n_rays, int32_t n_samples, uint32_t& flags, int& n_cus, const PlanFacts& facts, size_t ws_bytes) {
+    {   // GPNERF_FLAG_RESERVE_CUS(n): plan the launch for n fewer compute units (whole XCD rounds of 8, at least 8 stay), so that
+        // kernels of OTHER streams -- the next frame's encoder and volume builder -- find free CUs while the persistent workgroups run
+        const int reserve = (int)((flags >> 24) & 0xffu) & ~7;
+        if (reserve > 0) n_cus = n_cus - reserve >= 8 ? n_cus - reserve : (n_cus >= 8 ? 8 : n_cus);
+        flags &= 0x00ffffffu;
+    }
+    return plan_render(n_rays, n_samples, flags, n_cus, facts, ws_bytes);
+}
+// the counters the launch sequence starts from, in the order they are cleared
+constexpr int PLAN_CLEARS = 5;
+void plan_clears(const RenderPlan& p, int64_t n_rays, int32_t n_samples, Region* clear) {
+    const ListLayout gl = list_layout(n_rays, n_samples);
+    clear[0] = p.guard;
+    clear[1] = p.queue;
+    clear[2] = Region{p.chain.off, p.chain.bytes ? chain_layout(n_rays, n_samples).ctrl : 0};
+    clear[3] = Region{p.list.off, p.list.bytes ? GDEF_HEAD_BYTES : 0};
+    clear[4] = Region{p.list.off + gl.flag, p.colour == Colour::UNIFIED ? gl.ent - gl.flag : 0};
 }
 
 // One launch of the segmented form over all S samples as a single segment (term_eps = 0: nothing is ever frozen): launch slots
@@ -3922,34 +3959,27 @@ int gpnerf_render_fused(const GpnerfFrame* f, const float* rays, int64_t n_rays,
                         float term_eps, const int32_t* ray_order, const GpnerfOutputs* out, void* workspace,
                         size_t workspace_bytes, void* stream) {
     if (n_rays == 0) return GPNERF_OK;          // empty ray list: nothing to do (pointers may be null)
-    if (!f || !rays || !out || n_rays < 0 || n_samples < 1) return GPNERF_E_ARG;
+    if (!f || !rays || !out) return GPNERF_E_ARG;           // (n_rays, n_samples: plan_args_ok below)
     if (!out->rgb || !out->depth || !out->acc || !out->disp) return GPNERF_E_ARG;
     FrameK k;
     if (!to_framek(f, k, true, true)) return GPNERF_E_ARG;
-    if (n_rays >= ((int64_t)1 << 31)) return GPNERF_E_ARG;      // output rows are 32-bit values inside the kernel
-    const int sel = render_sel(flags, k);
+    const PlanFacts facts{out->weights != nullptr, out->raw != nullptr, out->samples_done != nullptr,
+                          k.vol_fold[GPNERF_LEVELS - 1] != nullptr, k.occ != nullptr};
+    const int sel = render_sel(flags, facts.folded);
     if ((sel == SEL_SPLIT || sel == SEL_GUARD) && !f->head_blob_split) return GPNERF_E_ARG;
     if ((sel == SEL_REF || sel == SEL_GUARD) && !f->head_blob_ref) return GPNERF_E_ARG;
     if (sel == SEL_FOLD && !f->head_blob) return GPNERF_E_ARG;
-    if (sel == SEL_GUARD && (!workspace || workspace_bytes < QUEUE_BYTES + guard_bytes(n_rays))) return GPNERF_E_ARG;
+    if (!plan_args_ok(n_rays, n_samples, flags, facts, workspace ? workspace_bytes : 0)) return GPNERF_E_ARG;
     int n_cus = 0;
     if (device_ready(&n_cus) != GPNERF_OK) return GPNERF_E_DEVICE;
-    {   // GPNERF_FLAG_RESERVE_CUS(n): plan the launch for n fewer compute units (whole XCD rounds of 8, at least 8 stay), so that
-        // kernels of OTHER streams -- the next frame's encoder and volume builder -- find free CUs while the persistent workgroups run
-        const int reserve = (int)((flags >> 24) & 0xffu) & ~7;
-        if (reserve > 0) n_cus = n_cus - reserve >= 8 ? n_cus - reserve : (n_cus >= 8 ? 8 : n_cus);
-        flags &= 0x00ffffffu;
-    }
+    const RenderPlan p = plan_call(n_rays, n_samples, flags, n_cus, facts, workspace ? workspace_bytes : 0);
     if (flags & GPNERF_FLAG_OCC_CULL) k.voxel[0] = k.voxel[1] = k.voxel[2] = 0.005f;   // demo_render.py:91 `xyz / 0.005`
-    const RenderPlan p = plan_render(n_rays, n_samples, flags, n_cus, *out, k, workspace ? workspace_bytes : 0);
 
     char* const ws = static_cast<char*>(workspace);
     auto at = [ws](const Region& r, size_t inner = 0) -> char* { return r.bytes ? ws + r.off + inner : nullptr; };
     const ListLayout gl = list_layout(n_rays, n_samples);
-    // the counters the launch sequence starts from, in this order
-    const Region clear[] = {p.guard, p.queue, Region{p.chain.off, p.chain.bytes ? chain_layout(n_rays, n_samples).ctrl : 0},
-                            Region{p.list.off, p.list.bytes ? GDEF_HEAD_BYTES : 0},
-                            Region{p.list.off + gl.flag, p.colour == Colour::UNIFIED ? gl.ent - gl.flag : 0}};
+    Region clear[PLAN_CLEARS];
+    plan_clears(p, n_rays, n_samples, clear);
     for (const Region& r : clear)
         if (r.bytes && !zero_async(ws + r.off, r.bytes, stream)) return GPNERF_E_LAUNCH;
 
@@ -4047,6 +4077,7 @@ int gpnerf_render_fused(const GpnerfFrame* f, const float* rays, int64_t n_rays,
     if (p.guard.bytes) {        // the fp32 form over the tiles the guarded split form flagged: persistent workgroups on the guard's queue
         if (hipGetLastError() != hipSuccess) return GPNERF_E_LAUNCH;
         KArgs kf = ka;
+        kf.n_rays = (long)n_rays;       // every tile of the call, whatever the render launches' cut into rounds and a remainder
         kf.flags = (unsigned)flags & ~(GPNERF_FLAG_SPLIT_F16 | GPNERF_FLAG_SPLIT_GUARD);
         kf.split = 1; kf.part = nullptr; kf.dynamic = 1; kf.queue = ka.guard + 8;
         const dim3 fgrid(full_grid(p.tiles, n_cus)), fblock(GPNERF_MAX_WAVES * 64);
@@ -4070,6 +4101,35 @@ size_t gpnerf_render_workspace_bytes(int64_t n_rays, int32_t n_samples) {
 }
 
 size_t gpnerf_render_guard_bytes(int64_t n_rays) { return n_rays > 0 ? guard_bytes(n_rays) : 0; }
+
+int gpnerf_render_plan(int64_t n_rays, int32_t n_samples, uint32_t flags, int32_t n_cus, uint32_t facts, size_t workspace_bytes,
+                       GpnerfRenderPlan* plan) {
+    if (!plan) return GPNERF_E_ARG;
+    memset(plan, 0, sizeof(*plan));
+    if (n_rays == 0) return GPNERF_OK;          // as the render call: nothing is launched
+    const PlanFacts pf{(facts & GPNERF_PLAN_WEIGHTS) != 0, (facts & GPNERF_PLAN_RAW) != 0, (facts & GPNERF_PLAN_SAMPLES_DONE) != 0,
+                       (facts & GPNERF_PLAN_FOLDED) != 0, (facts & GPNERF_PLAN_OCC) != 0};
+    if (n_cus < 1 || !plan_args_ok(n_rays, n_samples, flags, pf, workspace_bytes)) return GPNERF_E_ARG;
+    int cus = n_cus;
+    const RenderPlan p = plan_call(n_rays, n_samples, flags, cus, pf, workspace_bytes);
+    static_assert((int)Colour::STEP == GPNERF_COLOUR_STEP && (int)Colour::WAVE == GPNERF_COLOUR_WAVE &&
+                  (int)Colour::LIST == GPNERF_COLOUR_LIST && (int)Colour::UNIFIED == GPNERF_COLOUR_UNIFIED, "include/gpnerf_hip.h");
+    static_assert((int)Shape::STATIC == GPNERF_SHAPE_STATIC && (int)Shape::QUEUE == GPNERF_SHAPE_QUEUE &&
+                  (int)Shape::QUEUE_REMAINDER == GPNERF_SHAPE_QUEUE_REMAINDER && (int)Shape::REMAINDER_UNITS == GPNERF_SHAPE_REMAINDER_UNITS &&
+                  (int)Shape::CHAINED == GPNERF_SHAPE_CHAINED, "include/gpnerf_hip.h");
+    static_assert(SEL_REF == GPNERF_SEL_REF && SEL_FOLD == GPNERF_SEL_FOLD && SEL_SPLIT == GPNERF_SEL_SPLIT && SEL_GUARD == GPNERF_SEL_GUARD &&
+                  PLAN_CLEARS == GPNERF_PLAN_CLEARS, "include/gpnerf_hip.h");
+    plan->sel = p.sel; plan->colour = (int32_t)p.colour; plan->shape = (int32_t)p.shape;
+    plan->waves = p.g.waves; plan->split = p.g.split; plan->grid = p.grid; plan->n_cus = cus;
+    plan->tiles = p.tiles; plan->main_rays = p.main_rays;
+    auto pub = [](const Region& r) { return GpnerfRegion{r.bytes ? (uint64_t)r.off : 0, (uint64_t)r.bytes}; };
+    plan->queue = pub(p.queue); plan->part = pub(p.part); plan->chain = pub(p.chain);
+    plan->list = pub(p.list); plan->mask = pub(p.mask); plan->guard = pub(p.guard);
+    Region clear[PLAN_CLEARS];
+    plan_clears(p, n_rays, n_samples, clear);
+    for (int i = 0; i < PLAN_CLEARS; ++i) plan->clear[i] = pub(clear[i]);
+    return GPNERF_OK;
+}
 
 int gpnerf_sample_points(const GpnerfFrame* f, const float* rays, int64_t n_rays, int32_t n_samples, float* pts,
                          float* z_vals, float* grid, void* stream) {

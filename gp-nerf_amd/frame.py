@@ -321,6 +321,84 @@ def patch_order_rays(mask, H, W, n, patch_w=32, patch_h=8):
     return order
 
 
+def _prepare_call(frame, N, S, want, neg_ray, early_term, ray_order, occ_cull, load_balance, split_f16, flip, subset, guard, fold,
+                  reserve_cus, exits, workspace_cap, shared_device, touch=True):
+    """What render_fused and render_plan derive from their keyword arguments, in one place: the flags word, the launch's ray count,
+    the bytes of workspace lent, and the GPNERF_PLAN_* facts of the call.  touch=True (the render) also brings the frame into the
+    state the flags ask for (occupancy volume built, coarse levels folded or not); touch=False only says what that state would be."""
+    lib = L.lib()
+    if flip is None:
+        flip = bool(neg_ray) and not occ_cull
+    flags = (L.FLAG_NEG_RAY if neg_ray else 0) | (L.FLAG_FLIP_SAMPLES if flip else 0) | (L.FLAG_EARLY_TERM if early_term else 0)
+    flags |= (int(reserve_cus) & 0xff) << 24
+    if not exits:
+        flags |= L.FLAG_NO_EXITS
+    if shared_device:
+        flags |= L.FLAG_SHARED_DEVICE
+    if split_f16:
+        if frame is not None and not frame.c.head_blob_split:
+            raise L.GpnerfError("split_f16 needs the f16 hi/lo head image (build the frame from pack_head()'s tensor)")
+        flags |= L.FLAG_SPLIT_F16
+        if guard is None:
+            guard = bool(load_balance)
+        if guard:
+            if not load_balance:
+                raise L.GpnerfError("the split form's range guard keeps its flags in the workspace (load_balance=True)")
+            flags |= L.FLAG_SPLIT_GUARD
+    if occ_cull:
+        if touch and not frame.c.occ:
+            frame.build_occupancy()
+        flags |= L.FLAG_OCC_CULL
+    if ray_order is not None:
+        _require_gpu(ray_order, "ray_order")
+        if ray_order.dtype != torch.int32 or not ray_order.is_contiguous() or (ray_order.numel() != N and not subset):
+            raise L.GpnerfError("ray_order must be a contiguous int32 tensor with one entry per ray")
+    n_launch = int(ray_order.numel()) if subset else N
+    refold = fold is True
+    fold = bool(fold)
+    folded = fold and not split_f16
+    if touch:
+        if folded:
+            if refold or not getattr(frame, "_folded_valid", False):
+                frame.fold_volumes()
+            for l in range(L.FOLD_FIRST_LEVEL, L.LEVELS):
+                frame.c.vol_folded[l] = frame.vols_folded[l].data_ptr()
+        else:
+            for l in range(L.LEVELS):
+                frame.c.vol_folded[l] = None
+    if subset and any(k in want for k in ("weights", "z_vals", "raw")):
+        raise L.GpnerfError("subset launches return the per-ray maps only")
+    ws_bytes = int(lib.gpnerf_render_workspace_bytes(n_launch, S)) if load_balance else 0
+    if workspace_cap is not None:       # lend less than the launch could use (it then keeps to the forms that fit: include/gpnerf_hip.h `workspace`)
+        ws_bytes = min(ws_bytes, int(workspace_cap))
+    facts = ((L.PLAN_WEIGHTS if "weights" in want else 0) | (L.PLAN_RAW if "raw" in want else 0) |
+             (L.PLAN_SAMPLES_DONE if "samples_done" in want else 0) | (L.PLAN_FOLDED if folded else 0) |
+             (L.PLAN_OCC if occ_cull or (frame is not None and frame.c.occ) else 0))
+    return flags, n_launch, ws_bytes, facts
+
+
+def render_plan(frame, rays, n_samples, neg_ray=False, early_term=False, term_eps=1e-5,
+                want=("weights", "z_vals", "rgb_in", "ray_mask"), ray_order=None, occ_cull=False, load_balance=True,
+                split_f16=False, flip=None, subset=False, guard=None, fold=None, reserve_cus=0, exits=True, workspace_cap=None, shared_device=False,
+                n_cus=None):
+    """What render_fused(frame, rays, n_samples, ...) with the same keyword arguments would launch: the GpnerfRenderPlan of
+    gpnerf_render_plan (arithmetic, colour mode, launch shape, grid, workspace regions).  Host arithmetic only: nothing is launched
+    and the frame is left as it is.  rays: the tensor, or just its row count; frame may be None (a frame's state only matters for
+    occ_cull=False on a frame that already carries an occupancy volume).  fold=True is taken as folded volumes the render call
+    accepts (include/gpnerf_hip.h GPNERF_PLAN_FOLDED: it ignores levels beyond 32-bit byte offsets).  n_cus: the device's compute units (default: the current
+    device's)."""
+    N = int(rays) if isinstance(rays, int) else int(rays.shape[0])
+    flags, n_launch, ws_bytes, facts = _prepare_call(frame, N, int(n_samples), want, neg_ray=neg_ray, early_term=early_term, ray_order=ray_order,
+                                                     occ_cull=occ_cull, load_balance=load_balance, split_f16=split_f16, flip=flip, subset=subset,
+                                                     guard=guard, fold=fold, reserve_cus=reserve_cus, exits=exits, workspace_cap=workspace_cap,
+                                                     shared_device=shared_device, touch=False)
+    if n_cus is None:
+        n_cus = torch.cuda.get_device_properties(torch.cuda.current_device()).multi_processor_count
+    plan = L.GpnerfRenderPlan()
+    L.check(L.lib().gpnerf_render_plan(n_launch, int(n_samples), flags, int(n_cus), facts, ws_bytes, C.byref(plan)), "gpnerf_render_plan")
+    return plan
+
+
 def render_fused(frame, rays, n_samples, neg_ray=False, early_term=False, term_eps=1e-5,
                  want=("weights", "z_vals", "rgb_in", "ray_mask"), ray_order=None, occ_cull=False, load_balance=True,
                  split_f16=False, flip=None, subset=False, guard=None, fold=None, reserve_cus=0, exits=True, workspace_cap=None, shared_device=False):
@@ -392,48 +470,13 @@ def render_fused(frame, rays, n_samples, neg_ray=False, early_term=False, term_e
     if "samples_done" in want:
         res["samples_done"] = torch.empty((N,), device=dev, dtype=torch.int32)
         o.samples_done = res["samples_done"].data_ptr()
-    if flip is None:
-        flip = bool(neg_ray) and not occ_cull
-    flags = (L.FLAG_NEG_RAY if neg_ray else 0) | (L.FLAG_FLIP_SAMPLES if flip else 0) | (L.FLAG_EARLY_TERM if early_term else 0)
-    flags |= (int(reserve_cus) & 0xff) << 24
-    if not exits:
-        flags |= L.FLAG_NO_EXITS
-    if shared_device:
-        flags |= L.FLAG_SHARED_DEVICE
-    if split_f16:
-        if not frame.c.head_blob_split:
-            raise L.GpnerfError("split_f16 needs the f16 hi/lo head image (build the frame from pack_head()'s tensor)")
-        flags |= L.FLAG_SPLIT_F16
-        if guard is None:
-            guard = bool(load_balance)
-        if guard:
-            if not load_balance:
-                raise L.GpnerfError("the split form's range guard keeps its flags in the workspace (load_balance=True)")
-            flags |= L.FLAG_SPLIT_GUARD
-    if occ_cull:
-        if not frame.c.occ:
-            frame.build_occupancy()
-        flags |= L.FLAG_OCC_CULL
-    if ray_order is not None:
-        _require_gpu(ray_order, "ray_order")
-        if ray_order.dtype != torch.int32 or not ray_order.is_contiguous() or (ray_order.numel() != N and not subset):
-            raise L.GpnerfError("ray_order must be a contiguous int32 tensor with one entry per ray")
-    n_launch = int(ray_order.numel()) if subset else N
-    refold = fold is True
-    fold = bool(fold)
-    if fold and not split_f16:
-        if refold or not getattr(frame, "_folded_valid", False):
-            frame.fold_volumes()
-        for l in range(L.FOLD_FIRST_LEVEL, L.LEVELS):
-            frame.c.vol_folded[l] = frame.vols_folded[l].data_ptr()
-    else:
-        for l in range(L.LEVELS):
-            frame.c.vol_folded[l] = None
-    if subset and any(k in want for k in ("weights", "z_vals", "raw")):
-        raise L.GpnerfError("subset launches return the per-ray maps only")
-    ws_bytes = int(lib.gpnerf_render_workspace_bytes(n_launch, S)) if load_balance else 0
-    if workspace_cap is not None:       # lend less than the launch could use (it then keeps to the forms that fit: include/gpnerf_hip.h `workspace`)
-        ws_bytes = min(ws_bytes, int(workspace_cap))
+    flags, n_launch, ws_bytes, facts = _prepare_call(frame, N, S, want, neg_ray=neg_ray, early_term=early_term, ray_order=ray_order, occ_cull=occ_cull,
+                                                 load_balance=load_balance, split_f16=split_f16, flip=flip, subset=subset, guard=guard, fold=fold,
+                                                 reserve_cus=reserve_cus, exits=exits, workspace_cap=workspace_cap, shared_device=shared_device)
+    if N:       # the facts render_plan passes for this call are the pointers set above (an empty tensor has none; nothing is launched)
+        assert facts & (L.PLAN_WEIGHTS | L.PLAN_RAW | L.PLAN_SAMPLES_DONE) == ((L.PLAN_WEIGHTS if o.weights else 0) | (L.PLAN_RAW if o.raw else 0) |
+                                                                                (L.PLAN_SAMPLES_DONE if o.samples_done else 0))
+        assert bool(facts & L.PLAN_FOLDED) == bool(frame.c.vol_folded[L.LEVELS - 1]) and (not flags & L.FLAG_OCC_CULL or bool(frame.c.occ))
     ws = _workspace(dev, ws_bytes) if ws_bytes else None
     L.check(lib.gpnerf_render_fused(C.byref(frame.c), rays.data_ptr(), n_launch, S, flags, float(term_eps),
                                     ray_order.data_ptr() if ray_order is not None else None, C.byref(o),

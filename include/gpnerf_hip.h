@@ -235,6 +235,54 @@ size_t gpnerf_render_workspace_bytes(int64_t n_rays, int32_t n_samples);
  * to 256): word 0 = number of flagged tiles once the stream has passed the call, words 64.. = one flag per 32-ray tile. */
 size_t gpnerf_render_guard_bytes(int64_t n_rays);
 
+/* What gpnerf_render_fused would do with a call, without touching a device: the launch plan and the workspace layout it derives
+ * from the call's numbers alone.  A caller can ask what a workspace size buys before allocating it (does a 48 MB cap still list
+ * the colour work?  does the frame take a remainder launch?), and the tests pin every plan down through it.  Host arithmetic only;
+ * the same planner, argument checks and GPNERF_FLAG_RESERVE_CUS handling as the render call.
+ *   n_rays, n_samples, flags, workspace_bytes: as for gpnerf_render_fused (workspace_bytes 0 = no workspace)
+ *   n_cus: the device's compute units (hipDeviceProp_t::multiProcessorCount) BEFORE GPNERF_FLAG_RESERVE_CUS is taken off
+ *   facts: GPNERF_PLAN_* bits -- the optional outputs the call asks for and what its frame carries
+ * Returns GPNERF_E_ARG where the render call would (n_samples < 1, n_rays < 0 or >= 2^31, a guarded call without room for the
+ * guard), and for n_cus < 1 or plan == NULL; n_rays == 0 gives an all-zero plan (nothing is launched). */
+#define GPNERF_PLAN_WEIGHTS 1u        /* GpnerfOutputs.weights != NULL */
+#define GPNERF_PLAN_RAW 2u            /* GpnerfOutputs.raw != NULL */
+#define GPNERF_PLAN_SAMPLES_DONE 4u   /* GpnerfOutputs.samples_done != NULL */
+#define GPNERF_PLAN_FOLDED 8u         /* the frame carries folded volumes that the render call accepts: GpnerfFrame.vol_folded set for
+                                         all coarse levels, each below 2^32 bytes (256 per voxel) with x-rows below 2^24 bytes
+                                         -- the render call ignores folded volumes beyond that and runs the reference-order form */
+#define GPNERF_PLAN_OCC 16u           /* the frame carries an occupancy volume (GpnerfFrame.occ) */
+/* sel: the arithmetic of the call */
+#define GPNERF_SEL_REF 0              /* fp32, the reference's summation order */
+#define GPNERF_SEL_FOLD 1             /* fp32, coarse levels folded */
+#define GPNERF_SEL_SPLIT 2            /* GPNERF_FLAG_SPLIT_F16 */
+#define GPNERF_SEL_GUARD 3            /* GPNERF_FLAG_SPLIT_F16 | GPNERF_FLAG_SPLIT_GUARD: the split form + the fp32 fix-up launch */
+/* colour: where a sample's colour branch runs */
+#define GPNERF_COLOUR_STEP 0          /* in the sample loop's step (GPNERF_FLAG_NO_EXITS, a `raw` output) */
+#define GPNERF_COLOUR_WAVE 1          /* deferred to a queue per wavefront */
+#define GPNERF_COLOUR_LIST 2          /* listed for the whole launch, evaluated by a second kernel */
+#define GPNERF_COLOUR_UNIFIED 3       /* listed, evaluated by the listing launch's own wavefronts */
+/* shape: the render launches */
+#define GPNERF_SHAPE_STATIC 0           /* one launch, one unit per wavefront (`split` wavefronts share a tile's samples) */
+#define GPNERF_SHAPE_QUEUE 1            /* persistent workgroups on the tile queue */
+#define GPNERF_SHAPE_QUEUE_REMAINDER 2  /* the same over the first main_rays rays (whole rounds) + one launch over the rest */
+#define GPNERF_SHAPE_REMAINDER_UNITS 3  /* one launch whose units are the whole round's tiles and the remainder's */
+#define GPNERF_SHAPE_CHAINED 4          /* early termination: one launch per segment of samples */
+#define GPNERF_PLAN_CLEARS 5
+typedef struct GpnerfRegion { uint64_t off, bytes; } GpnerfRegion;   /* of the workspace; bytes == 0: not used by the call */
+typedef struct GpnerfRenderPlan {
+    int32_t sel, colour, shape;             /* GPNERF_SEL_* / GPNERF_COLOUR_* / GPNERF_SHAPE_* */
+    int32_t waves, split;                   /* wavefronts per workgroup; wavefronts that share one tile's samples */
+    uint32_t grid;                          /* workgroups of every render launch */
+    int32_t n_cus, reserved_;               /* the compute units planned for (n_cus less GPNERF_FLAG_RESERVE_CUS) */
+    int64_t tiles, main_rays;               /* 32-ray tiles of the call; launch slots of the first render launch */
+    GpnerfRegion queue, part, chain, list, mask, guard;  /* tile-queue counters, split partials, early termination's chain block
+                                               (its first control words are the queue's counters: the one overlap), colour list,
+                                               cull mask + tile order, range guard */
+    GpnerfRegion clear[GPNERF_PLAN_CLEARS]; /* what the call zeroes before its first launch */
+} GpnerfRenderPlan;
+int gpnerf_render_plan(int64_t n_rays, int32_t n_samples, uint32_t flags, int32_t n_cus, uint32_t facts, size_t workspace_bytes,
+                       GpnerfRenderPlan* plan);
+
 /* Stage entry points (the same device code as the fused kernel, one reference function per launch).
  *
  * get_sampling_points + pts_to_can_pts + get_grid_coords (libs/renders/BaseRender.py:35-73), jitter off:

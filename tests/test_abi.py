@@ -74,6 +74,9 @@ int main(void) {
          offsetof(GpnerfFrame, proj), offsetof(GpnerfFrame, out_sh), offsetof(GpnerfFrame, head_blob), offsetof(GpnerfFrame, imgs));
   printf("%zu %zu\n", offsetof(GpnerfFrame, occ), offsetof(GpnerfFrame, head_blob_split));
   printf("%zu %zu\n", sizeof(GpnerfHeadParams), sizeof(GpnerfOutputs));
+  printf("%zu %zu %zu %zu %zu %zu %zu %zu %zu\n", sizeof(GpnerfRenderPlan), sizeof(GpnerfRegion), offsetof(GpnerfRenderPlan, grid),
+         offsetof(GpnerfRenderPlan, n_cus), offsetof(GpnerfRenderPlan, tiles), offsetof(GpnerfRenderPlan, main_rays),
+         offsetof(GpnerfRenderPlan, queue), offsetof(GpnerfRenderPlan, guard), offsetof(GpnerfRenderPlan, clear));
   return 0;
 }'''
     with tempfile.TemporaryDirectory() as d:
@@ -81,13 +84,21 @@ int main(void) {
         open(c, "w").write(src)
         exe = os.path.join(d, "t")
         subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), c, "-o", exe])
-        a, occ_off, b = subprocess.check_output([exe]).decode().strip().split("\n")
+        a, occ_off, b, plan = subprocess.check_output([exe]).decode().strip().split("\n")
     L = pkg._lib
     F = L.GpnerfFrame
     assert [int(x) for x in a.split()] == [C.sizeof(F), F.vol_dhw.offset, F.featmaps.offset, F.proj.offset, F.out_sh.offset,
                                            F.head_blob.offset, F.imgs.offset]
     assert [int(x) for x in occ_off.split()] == [F.occ.offset, F.head_blob_split.offset]
     assert [int(x) for x in b.split()] == [C.sizeof(L.GpnerfHeadParams), C.sizeof(L.GpnerfOutputs)]
+    P = L.GpnerfRenderPlan
+    assert [int(x) for x in plan.split()] == [C.sizeof(P), C.sizeof(L.GpnerfRegion), P.grid.offset, P.n_cus.offset, P.tiles.offset,
+                                              P.main_rays.offset, P.queue.offset, P.guard.offset, P.clear.offset]
+    hdr = open(HEADER).read()
+    for names, prefix in ((L.SEL_NAMES, "SEL"), (L.COLOUR_NAMES, "COLOUR"), (L.SHAPE_NAMES, "SHAPE")):
+        for i, n in enumerate(names):
+            assert re.search(rf"#define GPNERF_{prefix}_{n} {i}\b", hdr), (prefix, n)
+    assert f"#define GPNERF_PLAN_CLEARS {L.PLAN_CLEARS}" in hdr
 
 
 def test_host_only_entry_points_run_without_a_gpu(pkg):
@@ -101,6 +112,10 @@ def test_host_only_entry_points_run_without_a_gpu(pkg):
     t = (C.c_int32 * 48)()
     assert lib.gpnerf_head_layout(t) == 0
     assert t[0] == 64 and t[1] == 2 and t[2] == 0
+    plan = pkg._lib.GpnerfRenderPlan()
+    assert lib.gpnerf_render_plan(512 * 512, 64, 0, 256, 0, lib.gpnerf_render_workspace_bytes(512 * 512, 64), C.byref(plan)) == 0
+    assert plan.triple() == ("QUEUE", "UNIFIED", "REF") and plan.grid == 256 and plan.tiles == 8192
+    assert lib.gpnerf_render_plan(512 * 512, 0, 0, 256, 0, 0, C.byref(plan)) == -1
 
 
 def test_the_workspace_covers_the_colour_list_at_its_worst(pkg):

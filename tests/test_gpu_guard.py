@@ -179,6 +179,16 @@ def test_a_frames_last_partial_round_runs_several_samples_per_step(n_rays, S, sp
     base = rays_of(sc)
     rays = base[torch.arange(n_rays, device=base.device) % base.shape[0]].contiguous()
     want = ("weights", "z_vals", "rgb_in", "ray_mask", "raw", "samples_done")
+    # which launches this is (not a comment's word for it): whole rounds + at most an eighth of a round take the remainder launch
+    # -- two launches, because samples_done is asked for -- and nothing else does
+    plan = fm.render_plan(fr, rays, S, want=want, split_f16=split_f16, guard=False)
+    print(f"\n  plan: n_rays={n_rays} S={S} split_f16={split_f16} -> {plan}")
+    slots = plan.n_cus * 8
+    few = plan.tiles > slots and 0 < plan.tiles % slots <= slots // 8
+    assert (plan.triple()[0] == "QUEUE_REMAINDER") == few and (plan.tiles <= slots or plan.triple()[0] in ("QUEUE_REMAINDER", "QUEUE")), str(plan)
+    assert plan.triple()[1:] == ("STEP", "SPLIT" if split_f16 else "REF") and (not few or 0 < n_rays - plan.main_rays <= slots * 4), str(plan)
+    if plan.n_cus == 256:
+        assert few == (n_rays != 65536 + 1000 * 32), (n_rays, str(plan))
     a = fm.render_fused(fr, rays, S, want=want, split_f16=split_f16, guard=False)
     b = fm.render_fused(fr, rays, S, want=want, split_f16=split_f16, guard=False, load_balance=False)
     for k in a:
@@ -188,6 +198,8 @@ def test_a_frames_last_partial_round_runs_several_samples_per_step(n_rays, S, sp
         assert torch.equal(x, y), k
     g = fm.render_fused(fr, rays, S, want=want + ("guard_tiles",), split_f16=split_f16, guard=True) if split_f16 else None
     if g is not None:
+        gp = fm.render_plan(fr, rays, S, want=want + ("guard_tiles",), split_f16=split_f16, guard=True)
+        assert gp.triple() == (plan.triple()[0], "STEP", "GUARD") and gp.main_rays == plan.main_rays, str(gp)
         assert int(g["guard_tiles"]) == 0 and torch.equal(g["rgb_map"], a["rgb_map"])
 
 
@@ -228,6 +240,14 @@ def test_a_calls_launch_sequence_captures_into_a_hip_graph(kw, fm, syn):
     base = rays_of(sc)
     for n_rays in (131072, 70000):
         rays = base[torch.arange(n_rays, device=base.device) % base.shape[0]].contiguous()
+        plan = fm.render_plan(fr, rays, 48, **kw)
+        print(f"\n  plan: n_rays={n_rays} S=48 {kw} -> {plan}")
+        slots = plan.n_cus * 8
+        if plan.tiles >= slots:         # at least a round of wavefronts: persistent launches (the chained ones under early termination)
+            assert plan.triple()[0] != "STATIC" and (plan.triple()[0] == "CHAINED") == bool(kw.get("early_term")), str(plan)
+        assert plan.triple()[2] == ("GUARD" if kw.get("split_f16") else "REF") and bool(plan.regions().get("guard")) == bool(kw.get("split_f16"))
+        if plan.n_cus == 256:           # two whole rounds on the queue; one round and a few tiles: the remainder's units in the same launch
+            assert plan.triple()[0] == ("CHAINED" if kw.get("early_term") else "QUEUE" if n_rays == 131072 else "REMAINDER_UNITS"), str(plan)
         ref = fm.render_fused(fr, rays, 48, **kw)
         torch.cuda.synchronize()
         s = torch.cuda.Stream()

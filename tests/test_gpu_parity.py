@@ -547,6 +547,11 @@ def test_frame_level_deferral_is_the_wavefront_level_one_bit_for_bit(form, fm, s
                     continue
                 if S == 128 and not kw.get("early_term"):
                     continue        # (1.4 rounds: with the small workspace this frame splits its tiles' samples -- another association of T)
+                pa = fm.render_plan(fr, rays, S, want=want + ("step_stats",), **dict(fkw, **kw))
+                pb = fm.render_plan(fr, rays, S, want=want + ("step_stats",), workspace_cap=small, **dict(fkw, **kw))
+                for pl in (pa, pb):
+                    assert ("list" in pl.regions()) == (pl.triple()[1] in ("LIST", "UNIFIED")) and pl.triple()[2] == ("FOLD" if fkw else "REF"), str(pl)
+                assert "list" in pa.regions() or "list" not in pb.regions()         # less workspace never lists where more does not
                 a = fm.render_fused(fr, rays, S, want=want + ("step_stats",), **dict(fkw, **kw))
                 b = fm.render_fused(fr, rays, S, want=want + ("step_stats",), workspace_cap=small, **dict(fkw, **kw))
                 sa, sb = a.pop("step_stats").cpu().numpy().astype(np.int64), b.pop("step_stats").cpu().numpy().astype(np.int64)
@@ -559,8 +564,14 @@ def test_frame_level_deferral_is_the_wavefront_level_one_bit_for_bit(form, fm, s
                 assert sa[0] == sb[0] and sa[3] == sb[3] and sa[1] >= sb[1] and sa[4] >= sb[4], (sa, sb)
                 assert sa[5] <= sb[5] and sa[2] == sa[0] - sa[5], (sa, sb)
                 units = (int((a["weights"] != 0).sum()) + 31) // 32
+                if "list" not in pa.regions():      # no list, no packed evaluation: the launches counted below are the ones planned to list
+                    assert sa[5] == sb[5], (size, S, n, tuple(kw), str(pa), sa, sb)
+                if n == rays_all.shape[0]:
+                    pc = fm.render_plan(fr, rays, S, want=want, shared_device=True, **dict(fkw, **kw))
+                    assert pc.triple()[1] != "UNIFIED" and ("list" in pc.regions()) == ("list" in pa.regions()), str(pc)
                 if sa[5] < sb[5]:
                     listed += 1
+                    assert "list" in pa.regions() and "list" not in pb.regions() and pa.triple()[0] != "STATIC", (size, S, n, tuple(kw), str(pa), str(pb))
                     # a packed list: exactly `units` evaluations where a second kernel walks it; where the launch's own wavefronts do
                     # (plain launches on the tile queue, the one-launch ZJU-sized shape) every tile pads its last unit
                     assert units <= sa[5], (size, S, n, tuple(kw), sa, units)
@@ -589,7 +600,17 @@ def test_reserved_cus_render_the_same_frame(fm, syn):
     rays = rays_of(sc)
     for kw in ({}, {"early_term": True, "term_eps": 1e-5}):
         base = fm.render_fused(fr, rays, 48, want=("weights", "rgb_in"), **kw)
+        full = fm.render_plan(fr, rays, 48, want=("weights", "rgb_in"), **kw)
         for reserve in (8, 64, 200, 255):
+            plan = fm.render_plan(fr, rays, 48, want=("weights", "rgb_in"), reserve_cus=reserve, **kw)
+            # planned for the smaller chip (whole XCD rounds of 8, at least 8 stay): the plan is the one that chip itself gets
+            assert plan.n_cus == max(full.n_cus - (reserve & ~7), min(full.n_cus, 8))
+            assert plan.triple()[0] == "STATIC" or plan.grid <= plan.n_cus, str(plan)
+            small_chip = fm.render_plan(fr, rays, 48, want=("weights", "rgb_in"), n_cus=plan.n_cus, **kw)
+            assert (plan.triple(), plan.waves, plan.split, plan.grid, plan.regions()) == (small_chip.triple(), small_chip.waves, small_chip.split,
+                                                                                         small_chip.grid, small_chip.regions())
+            if kw:          # one wavefront per whole tile: why the bits below are the same
+                assert plan.split == 1 and full.split == 1, (str(full), str(plan))
             got = fm.render_fused(fr, rays, 48, want=("weights", "rgb_in"), reserve_cus=reserve, **kw)
             for k in base:
                 a, b = torch.nan_to_num(base[k]), torch.nan_to_num(got[k])
@@ -598,6 +619,8 @@ def test_reserved_cus_render_the_same_frame(fm, syn):
                 else:
                     assert float((a - b).abs().max()) <= 2e-6, (reserve, k)
     base = fm.render_fused(fr, rays, 48, want=("weights", "rgb_in"))
+    p0, p7 = (fm.render_plan(fr, rays, 48, want=("weights", "rgb_in"), reserve_cus=r) for r in (0, 7))
+    assert str(p0) == str(p7)
     same = fm.render_fused(fr, rays, 48, want=("weights", "rgb_in"), reserve_cus=7)          # rounded down to whole XCD rounds: nothing reserved
     assert all(torch.equal(torch.nan_to_num(base[k]), torch.nan_to_num(same[k])) for k in base)
 
