@@ -16,6 +16,7 @@
 
 #include <mutex>
 #include <type_traits>
+#include <utility>
 
 #include "../../include/gpnerf_hip.h"
 #include "head_layout.h"
@@ -1266,7 +1267,7 @@ struct KArgs {            // the fused kernel's only argument (see render_fused_
     float* part;
     int dynamic;              // 1: persistent workgroups pulling tiles from `queue`
     unsigned* queue;          // 8 counters (one per XCD), zero at launch
-    // chained sample segments (early termination, render_fused_kernel<., true>): this launch walks samples
+    // chained sample segments (early termination, Loop::CHAINED): this launch walks samples
     // [seg * chain, (seg + 1) * chain) of the rays listed in `list_in` (nullptr: every ray, segment 0), 32 list entries per
     // wavefront, and appends the rays that are neither finished nor opaque to `list_out` for the next launch
     int chain, seg;
@@ -1288,7 +1289,7 @@ struct KArgs {            // the fused kernel's only argument (see render_fused_
     // range guard of the split form: guard[0] = number of flagged tiles, guard[64 + tile] = 1 when an MFMA operand of the tile
     // reached the f16 range; the fix-up launch (FORM_F32_FIXUP) renders exactly the flagged tiles again in the fp32 form
     unsigned* guard;
-    // frame-level deferral of the colour branch (render_fused_kernel<., ., ., true, true> + colour_units_kernel +
+    // frame-level deferral of the colour branch (Colour::LIST / Colour::UNIFIED: the listing launch + colour_units_kernel +
     // colour_accumulate_kernel): gd_ctrl = a zeroed 256-byte block (GD_COUNT: entries appended so far; GD_QUEUE..+7: the unit queue's
     // counters), gd_ent[n] = (launch slot, sample | rank << 8, weight bits, 0), gd_rgbw[slot * S + rank] = (r, g, b, weight),
     // gd_cnt[slot] = entries of the ray
@@ -1303,7 +1304,27 @@ constexpr int GD_QUEUE = 0, GD_COUNT = 8, GD_TICKET = 9, GD_DONE = 10;      // w
 // (GD_COUNT counts ENTRIES in the two-launch form and 32-entry UNITS in the unified one, where GD_TICKET hands the units out)
 
 // the forms of the fused kernel
-constexpr int FORM_F32 = 0, FORM_SPLIT = 1, FORM_SPLIT_GUARD = 2, FORM_F32_FIXUP = 3, FORM_F32_FOLD = 4;
+constexpr int FORM_F32 = 0, FORM_SPLIT = 1, FORM_SPLIT_GUARD = 2, FORM_F32_FIXUP = 3, FORM_F32_FOLD = 4, N_FORMS = 5, N_LOOPS = 3, N_COLOURS = 4;
+// Its sample loop: PLAIN; the CHAINED segment launches of early termination, which walk the samples [k_begin, k_end) of the rays a
+// list names; CULLED, which walks the keep bits occupancy_mask_kernel computed before the launch.
+enum class Loop { PLAIN, CHAINED, CULLED };
+// Where a sample's colour branch runs: in the STEP (GPNERF_FLAG_NO_EXITS, a `raw` output); deferred to each WAVEfront's own queue
+// (render_tile); LISTed for the launch as a whole and evaluated by colour_units_kernel; or listed and evaluated by the listing
+// launch's own wavefronts once they have no tile left (UNIFIED).
+enum class Colour { STEP, WAVE, LIST, UNIFIED };
+constexpr bool defers(Colour c) { return c != Colour::STEP; }                           // the colour branch is not the step's
+constexpr bool lists(Colour c) { return c == Colour::LIST || c == Colour::UNIFIED; }    // ... nor the wavefront's: frame-level deferral
+constexpr bool unified(Colour c) { return c == Colour::UNIFIED; }
+// The colour of a chained launch's units of P > 1 samples per step (render_tile): the colour passes of a wavefront's own queue take
+// one sample per step, so under WAVE these units keep the colour branch in the STEP; the launch's list takes entries from any unit.
+constexpr Colour group_colour(Colour c) { return c == Colour::WAVE ? Colour::STEP : c; }
+// The variants of the fused kernel that exist (render_variant() builds exactly these): keep bits are walked with the colour branch
+// in the step or the wavefront's queue; the launch's list is the fp32 forms'; the fix-up launch evaluates everything, tile by tile.
+constexpr bool variant_ok(int form, Loop loop, Colour colour) {
+    if (form == FORM_F32_FIXUP) return colour == Colour::STEP && loop != Loop::CHAINED;
+    if (lists(colour)) return (form == FORM_F32 || form == FORM_F32_FOLD) && loop != Loop::CULLED;
+    return true;
+}
 constexpr int GUARD_HEADER_WORDS = 64;
 
 // bijective XCD-aware remap: blocks b and b+8 share an XCD (round-robin dispatch), give each XCD a
@@ -1513,12 +1534,9 @@ DEV float gather_views(const __attribute__((address_space(4))) FrameK& fr, float
 }
 
 DEV void agent_store(unsigned* p, unsigned v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-template <int FORM, bool CHAIN, int P = 1, bool CULL = false, bool DEFER = false, bool GDEF = false, bool UNI = false>
+template <int FORM, Loop LOOP, int P, Colour COLOUR>
 DEV bool render_tile(float* lds, const int lane, const long tile, const int seg, const long entry_base = 0) {
-    static_assert(!UNI || GDEF, "unified form: a listing sample loop");
-    static_assert(!CULL || (!CHAIN && P == 1), "occupancy culling: plain form only");
-    static_assert(!GDEF || (DEFER && !CULL), "frame-level deferral: a deferred sample loop without culling");
-    static_assert(P == 1 || CHAIN, "several samples per step: chained form only");
+    static_assert(P == 1 || LOOP == Loop::CHAINED, "several samples per step: chained form only");
     constexpr int RAYS = RAYS_PER_WAVE / P;             // rays per wavefront
     constexpr bool SPLIT = FORM == FORM_SPLIT || FORM == FORM_SPLIT_GUARD;
     // tag: the split form's helpers check their operands' range (FORM_SPLIT_GUARD) or do not
@@ -1546,18 +1564,18 @@ DEV bool render_tile(float* lds, const int lane, const long tile, const int seg,
     const long ray0 = entry_base + tile * RAYS;      // (entry_base: where the launch's remainder units start in the ray list)
     // the chained form renders the launch slots listed in list_in (the rays the previous segment left alive, in no particular
     // order), 32 / P list entries per wavefront; everything else renders 32 consecutive slots
-    const long n_items = CHAIN ? chain_items(k0) : n_rays;
+    const long n_items = LOOP == Loop::CHAINED ? chain_items(k0) : n_rays;
     if (ray0 >= n_items) return false;
     const bool active = (ray0 + rn) < n_items;
     long slot = active ? ray0 + rn : n_items - 1;
-    if constexpr (CHAIN) slot = k0->list_in ? (long)k0->list_in[slot] : k0->first_slot + slot;
+    if constexpr (LOOP == Loop::CHAINED) slot = k0->list_in ? (long)k0->list_in[slot] : k0->first_slot + slot;
     const int ray = k0->out.order ? k0->out.order[slot] : (int)slot;
     const bool neg = (flags & GPNERF_FLAG_NEG_RAY) != 0;             // Projector front test
     const bool flip = (flags & GPNERF_FLAG_FLIP_SAMPLES) != 0;       // raw2outputs(neg=True)
     const bool early = (flags & GPNERF_FLAG_EARLY_TERM) != 0;
-    // occupancy culling: CULL = the form that walks keep bits computed before the launch (its own instantiation); without them
+    // occupancy culling: Loop::CULLED = the form that walks keep bits computed before the launch (its own instantiation); without them
     // (outputs that need every step written, no workspace) the plain instantiation tests sample by sample
-    const bool cull = !CULL && (flags & GPNERF_FLAG_OCC_CULL) != 0 && k0->fr.occ != nullptr;
+    const bool cull = LOOP != Loop::CULLED && (flags & GPNERF_FLAG_OCC_CULL) != 0 && k0->fr.occ != nullptr;
 
     const f32x4 r0 = *reinterpret_cast<const f32x4*>(k0->rays + (size_t)ray * 8);
     const f32x4 r1 = *reinterpret_cast<const f32x4*>(k0->rays + (size_t)ray * 8 + 4);
@@ -1573,14 +1591,14 @@ DEV bool render_tile(float* lds, const int lane, const long tile, const int seg,
     const bool writer = active && (half == 0) && (sub == 0);
 
     // the chained form is its own instantiation: the plain sample loop stays as it was
-    const int k_end = CHAIN ? min(k0->k_end, S) : (int)(((long)S * (seg + 1)) / split);
-    int k = CHAIN ? k0->k_begin : (int)(((long)S * seg) / split);
+    const int k_end = LOOP == Loop::CHAINED ? min(k0->k_end, S) : (int)(((long)S * (seg + 1)) / split);
+    int k = LOOP == Loop::CHAINED ? k0->k_begin : (int)(((long)S * seg) / split);
     const int k_begin = k;
-    if (CHAIN && k > 0) {       // resume: what the previous segment of this ray left behind (the 16 floats of a split segment)
+    if (LOOP == Loop::CHAINED && k > 0) {       // resume: what the previous segment of this ray left behind (the 16 floats of a split segment)
         const f32x4* p = reinterpret_cast<const f32x4*>(k0->part + (size_t)slot * 16);
         const f32x4 a = p[0], b = p[1], c = p[2], d = p[3];
         c_r = a[0]; c_g = a[1]; c_b = a[2]; depth = a[3];
-        if constexpr (GDEF) { n_q = __builtin_bit_cast(int, a[0]); c_r = 0.f; }      // (the colour map is not the sample loop's: its slot carries the rank)
+        if constexpr (lists(COLOUR)) { n_q = __builtin_bit_cast(int, a[0]); c_r = 0.f; }      // (the colour map is not the sample loop's: its slot carries the rank)
         acc = b[0]; T = b[1]; rin[0] = b[3];
         const int packed = (int)b[2];
         n_two = packed & 4095; n_done = packed >> 12;
@@ -1591,8 +1609,7 @@ DEV bool render_tile(float* lds, const int lane, const long tile, const int seg,
     // which one of its rays keeps its sample; a skipped step costs nothing (tested as it goes, it cost ~12 % of a full step:
     // sample position, grid coordinates, eight occupancy taps, a ballot -- 3.4 ms for a frame that evaluates 14.5 % of its steps)
     unsigned long long my_keep[2] = {0ull, 0ull}, any_keep[2] = {0ull, 0ull};
-    constexpr bool masked = CULL;
-    if (masked) {
+    if constexpr (LOOP == Loop::CULLED) {
 #pragma unroll
         for (int w = 0; w < 2; ++w) {
             my_keep[w] = active ? k0->cull_mask[(size_t)slot * 2 + w] : 0ull;
@@ -1611,15 +1628,14 @@ DEV bool render_tile(float* lds, const int lane, const long tile, const int seg,
     // everything but the colour; rays with a non-zero weight append (ray lane, sample, weight) to a 64-entry queue of the wavefront in
     // LDS; when 32 are waiting, one colour pass evaluates them -- lane i regathers item i's views (the same loads, minutes-old in L2)
     // -- and every ray takes its own results back in sample order, so c accumulates in exactly the order of the plain loop.  Same bits.
-    static_assert(!DEFER || P == 1 || GDEF, "colour passes of the wavefront: one sample per step");
-    constexpr bool CAN_DEFER = DEFER, defer = DEFER;
+    static_assert(COLOUR != Colour::WAVE || P == 1, "colour passes of the wavefront: one sample per step (group_colour)");
     unsigned long long mine = 0ull;             // bit j: the queue entry j places behind the head is one of this ray's
     int q_head = 0, q_cnt = 0;                  // (uniform)
     uint2* dq = nullptr;
     // behind the head image (split form: and behind the range guard's slots): the wavefronts' queues, then their tallies
     constexpr int QUEUE_AT = SPLIT ? gph::BLOB_WORDS + (FORM == FORM_SPLIT_GUARD ? 2 * GUARD_LDS_SLOTS : 0) : gpl::BLOB_FLOATS;
     const int wave_in_wg = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    if constexpr (CAN_DEFER) dq = reinterpret_cast<uint2*>(lds + QUEUE_AT) + wave_in_wg * DEFER_QUEUE;
+    if constexpr (defers(COLOUR)) dq = reinterpret_cast<uint2*>(lds + QUEUE_AT) + wave_in_wg * DEFER_QUEUE;
     // step_stats (the diagnostic launch only): the tile counts in LDS (T_*) and adds them to the launch's counters once, at its
     // end (one global atomic per step and counter made the counting launch 40 % slower than the launches it describes)
     unsigned* const tl = reinterpret_cast<unsigned*>(lds) + QUEUE_AT + GPNERF_MAX_WAVES * DEFER_QUEUE * 2 + wave_in_wg * TALLY_WORDS;
@@ -1628,10 +1644,10 @@ DEV bool render_tile(float* lds, const int lane, const long tile, const int seg,
     int k_lim = k_end;                          // (early termination of the tile as a whole moves it to where the loop stopped)
     int opaque_from = -1;                       // (first step behind the one at which every ray's transmittance was exactly 0)
     for (;; k += P) {
-        if constexpr (GDEF) {
+        if constexpr (lists(COLOUR)) {
             // Frame-level deferral: the samples waiting for their colour branch leave the wavefront altogether -- 32 at a time (what
             // is left at the tile's end) they are appended to the launch's entry list, which is evaluated 32 entries per wavefront
-            // step, whichever tiles they came from (by this launch's own wavefronts once they have no tile left: UNI; by
+            // step, whichever tiles they came from (by this launch's own wavefronts once they have no tile left: Colour::UNIFIED; by
             // colour_units_kernel otherwise); colour_accumulate_kernel then adds every ray's terms in sample order.  The same arithmetic
             // on the same operands in the same order as the passes below: the same bits.
             if (q_cnt >= 32 || (q_cnt > 0 && !(k < k_lim))) {
@@ -1640,7 +1656,7 @@ DEV bool render_tile(float* lds, const int lane, const long tile, const int seg,
                 const int sl = __shfl((int)slot, (int)(e.x & 31u));
                 kargs_ptr kb = (kargs_ptr)__builtin_amdgcn_kernarg_segment_ptr();
                 asm volatile("" : "+s"(kb));
-                if constexpr (UNI) {
+                if constexpr (unified(COLOUR)) {
                     // unified form: whole units (what is left at the tile's end padded with null entries), written through to the
                     // device's coherence point and acknowledged (vmcnt) before the unit's flag says so -- wavefronts of other CUs
                     // evaluate it while this launch is still running (see render_fused_kernel)
@@ -1663,8 +1679,8 @@ DEV bool render_tile(float* lds, const int lane, const long tile, const int seg,
                 continue;
             }
         } else
-        if constexpr (CAN_DEFER) {
-            if (defer && (q_cnt >= 32 || (q_cnt > 0 && !(k < k_lim)))) {
+        if constexpr (defers(COLOUR)) {
+            if (q_cnt >= 32 || (q_cnt > 0 && !(k < k_lim))) {
                 const int nb = min(q_cnt, 32);
                 const uint2 e = dq[(q_head + (n < nb ? n : 0)) & (DEFER_QUEUE - 1)];        // lanes beyond the last entry redo entry 0
                 const int r = (int)(e.x & 31u), kk = (int)(e.x >> 5);
@@ -1703,12 +1719,12 @@ DEV bool render_tile(float* lds, const int lane, const long tile, const int seg,
             }
         }
         if (!(k < k_lim)) break;
-        if (masked) {                           // the next step >= k at which the tile has anything to do
+        if constexpr (LOOP == Loop::CULLED) {         // the next step >= k at which the tile has anything to do
             const unsigned long long w0 = k < 64 ? (any_keep[0] >> k) << k : 0ull;
             const unsigned long long w1 = k < 64 ? any_keep[1] : (k < 128 ? (any_keep[1] >> (k - 64)) << (k - 64) : 0ull);
             k = w0 ? __builtin_ctzll(w0) : (w1 ? 64 + __builtin_ctzll(w1) : k_end);
             if (k >= k_end) {
-                if (CAN_DEFER && q_cnt > 0) { k_lim = k; k -= P; continue; }       // (the colour passes still waiting, then out)
+                if (defers(COLOUR) && q_cnt > 0) { k_lim = k; k -= P; continue; }       // (the colour passes still waiting, then out)
                 break;
             }
         }
@@ -1732,7 +1748,7 @@ DEV bool render_tile(float* lds, const int lane, const long tile, const int seg,
         // progressive culling (demo_render.py:270-283): evaluate only samples whose occupancy interpolates to > 0;
         // a tile whose 32 samples are all culled skips its gathers and the MLP (alpha = 0 for all of them)
         bool keep = true;
-        if constexpr (masked) {
+        if constexpr (LOOP == Loop::CULLED) {
             keep = ((k < 64 ? my_keep[0] >> k : my_keep[1] >> (k - 64)) & 1ull) != 0ull;
         } else if (cull) {
             keep = sample_occupancy(fr.occ, fr.vol_dhw[0][0], fr.vol_dhw[0][1], fr.vol_dhw[0][2], gx, gy, gz) > 0.f;
@@ -1748,7 +1764,7 @@ DEV bool render_tile(float* lds, const int lane, const long tile, const int seg,
 
         // chained form: a ray that is opaque stops HERE, whatever the other rays of its wavefront do (its result is a function
         // of the ray alone, so it does not matter which rays are packed together); the plain form stops a tile as a whole
-        const bool dead = CHAIN && P == 1 && T < term_eps;     // (P > 1: decided sample by sample in the composite below)
+        const bool dead = LOOP == Loop::CHAINED && P == 1 && T < term_eps;     // (P > 1: decided sample by sample in the composite below)
         if constexpr (P == 1) n_done += dead ? 0 : 1;
         float sf[32];
         Frag sff[4];
@@ -1779,7 +1795,7 @@ DEV bool render_tile(float* lds, const int lane, const long tile, const int seg,
             }
             elus_n<16>(g0, sf);
             elus_n<16>(g1, sf + 16);
-        } else if constexpr (FORM == FORM_F32 && DEFER) {
+        } else if constexpr (FORM == FORM_F32 && defers(COLOUR)) {
             // SparseConvNet.forward sampling (:113-122) and the sigma feature layer, level by level: level l's 16 k-steps (32 MFMAs,
             // ~2 000 cycles: about one L2 round trip) run while level l + 1's 32 loads are in flight, so three of the step's four
             // volume round trips hide behind the wavefront's OWN matrix work -- with the colour branch out of the step the other
@@ -1834,7 +1850,7 @@ DEV bool render_tile(float* lds, const int lane, const long tile, const int seg,
 #pragma unroll
             for (int l = 0; l < GPNERF_LEVELS; ++l)
             {
-                if constexpr (DEFER) {
+                if constexpr (defers(COLOUR)) {
                     gather_volume_batched<!SPLIT>(fr.vol[l], fr.vol_dhw[l][0], fr.vol_dhw[l][1], fr.vol_dhw[l][2], gx, gy, gz, half, fv + 16 * l);
                     continue;
                 }
@@ -1878,7 +1894,7 @@ DEV bool render_tile(float* lds, const int lane, const long tile, const int seg,
         float sigma, rgb[3];
         // (the zero-density exit in the reference-order form only: built into the folded and split forms too, the early return
         // cost their sample loops their register allocation -- 13.3 -> 15.1 ms and 7.5 -> 10.3 ms on the bench frame)
-        if constexpr (DEFER) {
+        if constexpr (defers(COLOUR)) {
             if constexpr (SPLIT) {
                 Frag mvf[6];
                 mean_var_s(gmax, x, mvf);
@@ -1903,7 +1919,7 @@ DEV bool render_tile(float* lds, const int lane, const long tile, const int seg,
         }
         else { mlp_eval(lds, lane, sf, x, nvalid, sigma, rgb, st); if (tally && lane == 0) tl[T_PASS] += 1u; }
         if (tally && lane == 0) tl[T_STEPS] += 1u;
-        if (CULL || cull) {
+        if (LOOP == Loop::CULLED || cull) {
             if (!keep) sigma = 0.f;                     // hold_alpha stays 0 for culled samples (demo_render.py:337-341)
             if (!(1.f - fast_exp(-sigma) > 1e-14f)) { rgb[0] = 0.f; rgb[1] = 0.f; rgb[2] = 0.f; }   // valid1 (:317)
         }
@@ -1950,19 +1966,17 @@ DEV bool render_tile(float* lds, const int lane, const long tile, const int seg,
             if (writer) {
                 if (out.weights) out.weights[(size_t)ray * S + k] = wgt;
             }
-            if constexpr (CAN_DEFER) {
-                if (defer) {
-                    // (culled samples and, under culling, samples with alpha <= 1e-14 carry rgb = 0: nothing to add either)
-                    const bool need = active && wgt != 0.f && !((CULL || cull) && !(alpha > 1e-14f));
-                    const unsigned m = (unsigned)__ballot(need);            // (both lane halves hold the ray: the low word has it all)
-                    const int pos = q_cnt + __popc(m & ((1u << n) - 1u));
-                    if (need) {
-                        if constexpr (!GDEF) mine |= 1ull << pos;
-                        if (half == 0) dq[(q_head + pos) & (DEFER_QUEUE - 1)] = uint2{(unsigned)n | ((unsigned)k << 5) | (GDEF ? (unsigned)n_q << 13 : 0u), __builtin_bit_cast(unsigned, wgt)};
-                        ++n_q;
-                    }
-                    q_cnt += __popc(m);
+            if constexpr (defers(COLOUR)) {
+                // (culled samples and, under culling, samples with alpha <= 1e-14 carry rgb = 0: nothing to add either)
+                const bool need = active && wgt != 0.f && !((LOOP == Loop::CULLED || cull) && !(alpha > 1e-14f));
+                const unsigned m = (unsigned)__ballot(need);            // (both lane halves hold the ray: the low word has it all)
+                const int pos = q_cnt + __popc(m & ((1u << n) - 1u));
+                if (need) {
+                    if constexpr (!lists(COLOUR)) mine |= 1ull << pos;
+                    if (half == 0) dq[(q_head + pos) & (DEFER_QUEUE - 1)] = uint2{(unsigned)n | ((unsigned)k << 5) | (lists(COLOUR) ? (unsigned)n_q << 13 : 0u), __builtin_bit_cast(unsigned, wgt)};
+                    ++n_q;
                 }
+                q_cnt += __popc(m);
             }
         } else {
             // the group's P samples in order, in every lane of the group alike: sample j's values come from lane (group base + j)
@@ -1988,10 +2002,10 @@ DEV bool render_tile(float* lds, const int lane, const long tile, const int seg,
                 n_done += live ? 1 : 0;
                 n_two += (live && __shfl((int)(two_views ? 1 : 0), src) != 0) ? 1 : 0;
                 if (j == sub) { my_wgt = wgt; my_rank = n_q; }
-                if constexpr (GDEF) n_q += wgt != 0.f ? 1 : 0;
+                if constexpr (lists(COLOUR)) n_q += wgt != 0.f ? 1 : 0;
             }
             if (active && half == 0 && in_seg && out.weights) out.weights[(size_t)ray * S + kl] = my_wgt;
-            if constexpr (GDEF) {               // this lane's sample joins the launch's entry list (see the top of the loop)
+            if constexpr (lists(COLOUR)) {      // this lane's sample joins the launch's entry list (see the top of the loop)
                 const bool need = active && in_seg && my_wgt != 0.f;
                 const unsigned m = (unsigned)__ballot(need);
                 const int pos = q_cnt + __popc(m & ((1u << n) - 1u));
@@ -2003,7 +2017,7 @@ DEV bool render_tile(float* lds, const int lane, const long tile, const int seg,
         STAMP(st, 6);
         // wavefront-level early termination (not in the reference): every ray of the tile is opaque
         if (early && __all(T < term_eps)) {
-            if constexpr (DEFER) k_lim = k + P;         // (the colour passes still waiting, then out)
+            if constexpr (defers(COLOUR)) k_lim = k + P;         // (the colour passes still waiting, then out)
             else { k += P; break; }
         }
         // Exactly opaque (plain deferred loop): once the transmittance of all 32 rays has underflowed to 0 -- a few samples behind
@@ -2011,11 +2025,11 @@ DEV bool render_tile(float* lds, const int lane, const long tile, const int seg,
         // can change any more (fma(0, x, m) = m for finite x).  The sample loop ends here; what the rest of the segment still owes
         // the outputs -- zero weights, and ray_mask's count of the samples two views see -- is settled behind it without a gather
         // or an MFMA.  Bit-exact like the other exits (kp->skip; never while culling, whose count depends on the occupancy).
-        if constexpr (DEFER && !CULL && P == 1) {      // (chained form too: its launches without early termination are whole rays)
+        if constexpr (defers(COLOUR) && LOOP != Loop::CULLED && P == 1) {      // (chained form too: its launches without early termination are whole rays)
             if ((kp->skip & 2) && !cull && !early && __all(T == 0.f)) { k_lim = k + P; opaque_from = k + P; }
         }
     }
-    if constexpr (DEFER && !CULL && P == 1) {      // (chained form too: its launches without early termination are whole rays)
+    if constexpr (defers(COLOUR) && LOOP != Loop::CULLED && P == 1) {      // (chained form too: its launches without early termination are whole rays)
         if (opaque_from >= 0) {
             kargs_ptr ko = (kargs_ptr)__builtin_amdgcn_kernarg_segment_ptr();
             asm volatile("" : "+s"(ko));
@@ -2047,14 +2061,14 @@ DEV bool render_tile(float* lds, const int lane, const long tile, const int seg,
             unsigned* const gd = kp->guard;
             // the fix-up launch re-renders 32 consecutive launch slots at a time: flag the tile of every ray of this wavefront
             // (the chained form packs rays of many tiles together)
-            const bool mine = CHAIN ? writer : lane == 0;
-            if (mine && atomicExch(gd + GUARD_HEADER_WORDS + (CHAIN ? slot / RAYS_PER_WAVE : tile), 1u) == 0u) atomicAdd(gd, 1u);
+            const bool mine = LOOP == Loop::CHAINED ? writer : lane == 0;
+            if (mine && atomicExch(gd + GUARD_HEADER_WORDS + (LOOP == Loop::CHAINED ? slot / RAYS_PER_WAVE : tile), 1u) == 0u) atomicAdd(gd, 1u);
             *gs = 0u;
         }
     }
     const __attribute__((address_space(4))) OutK& out = kp->out;
     float* const part = kp->part;
-    if constexpr (CHAIN) {
+    if constexpr (LOOP == Loop::CHAINED) {
         // z_vals is a function of (near, far, k): segment 0 writes every row completely
         if (out.z_vals && seg == 0)
             write_z_vals(out.z_vals, lane, (int)ray, near, far, (int)min((long)RAYS, n_items - ray0), S, step, 0, S, P);
@@ -2073,7 +2087,7 @@ DEV bool render_tile(float* lds, const int lane, const long tile, const int seg,
         if (goes_on) {
             f32x4* p = reinterpret_cast<f32x4*>(part + (size_t)slot * 16);
             f32x4 a, b, c, d;
-            a[0] = GDEF ? __builtin_bit_cast(float, n_q) : c_r; a[1] = c_g; a[2] = c_b; a[3] = depth;
+            a[0] = lists(COLOUR) ? __builtin_bit_cast(float, n_q) : c_r; a[1] = c_g; a[2] = c_b; a[3] = depth;
             b[0] = acc; b[1] = T; b[2] = (float)(n_two + 4096 * n_done); b[3] = rin[0];
             c[0] = rin[1]; c[1] = rin[2]; c[2] = rin[3]; c[3] = rin[4];
             d[0] = rin[5]; d[1] = rin[6]; d[2] = rin[7]; d[3] = rin[8];
@@ -2101,7 +2115,7 @@ DEV bool render_tile(float* lds, const int lane, const long tile, const int seg,
         for (k = min(k, k_end); k < S; ++k) {
             if (out.weights) out.weights[(size_t)ray * S + k] = 0.f;
         }
-        if constexpr (GDEF) kp->gd_cnt[slot] = n_q;          // (the colour map is colour_accumulate_kernel's)
+        if constexpr (lists(COLOUR)) kp->gd_cnt[slot] = n_q;          // (the colour map is colour_accumulate_kernel's)
         else { out.rgb[(size_t)ray * 3 + 0] = c_r; out.rgb[(size_t)ray * 3 + 1] = c_g; out.rgb[(size_t)ray * 3 + 2] = c_b; }
         out.depth[ray] = depth;
         out.acc[ray] = acc;
@@ -2124,7 +2138,7 @@ DEV bool render_tile(float* lds, const int lane, const long tile, const int seg,
 // 8-wave workgroup resident per CU a static grid holds the CU until its slowest tile is done -- the queue hands the next
 // tile to whichever wave is free.  Static launches (one unit per wave, XCD-aware remap) remain for frames smaller than
 // one round and for the sample-split geometry.
-// Unified form (render_fused_kernel<., false, false, true, true, true>): the launch's wavefronts evaluate the list themselves
+// Unified form (Colour::UNIFIED): the launch's wavefronts evaluate the list themselves
 // once the tile queue has nothing left for them.  `pending` = the unit this wavefront holds a ticket for (-1:
 // none).  Takes tickets UNI_BATCH at a time, evaluates the next unit if its flag is up, returns whether it did.
 // One 32-entry unit of the colour list: lane i (both halves) evaluates entry i exactly as render_tile's colour pass does -- sample_point
@@ -2185,18 +2199,17 @@ DEV bool consume_unit(float* lds, const int lane, long& pending, long& pending_e
     return true;
 }
 
-template <int FORM, bool CHAIN, bool CULL = false, bool DEFER = false, bool GDEF = false, bool UNI = false>     // DEFER: the colour branch sample by sample; GDEF: for the launch as a whole (render_tile); UNI: ... and evaluated by this launch's own wavefronts
+template <int FORM, Loop LOOP, Colour COLOUR>
 __global__ void __launch_bounds__(64 * GPNERF_MAX_WAVES, GPNERF_MAX_WAVES / 4)
 render_fused_kernel(const KArgs ka) {
-    static_assert(!DEFER || FORM != FORM_F32_FIXUP, "the fix-up launch evaluates everything");
-    static_assert(!UNI || (GDEF && !CULL && (FORM == FORM_F32 || FORM == FORM_F32_FOLD)), "unified form: a listing launch of the fp32 forms");
+    static_assert(variant_ok(FORM, LOOP, COLOUR), "not a variant of the fused kernel (see variant_ok)");
     constexpr bool SPLIT = FORM == FORM_SPLIT || FORM == FORM_SPLIT_GUARD;
     extern __shared__ __attribute__((aligned(16))) float lds[];
     WT(0);
     if constexpr (FORM == FORM_F32_FIXUP) {
         if (__hip_atomic_load(ka.guard, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u) return;     // nothing was flagged
     }
-    if constexpr (CHAIN) {
+    if constexpr (LOOP == Loop::CHAINED) {
         if (ka.list_in && *ka.count_in == 0u) return;               // no ray is left for this segment
     }
     {
@@ -2221,7 +2234,7 @@ render_fused_kernel(const KArgs ka) {
         asm volatile("" : "+s"(kq));            // re-read per tile rather than held across render_tile (see there)
         long tile = 0;
         int seg = 0;
-        bool have_tile = !(UNI && dry >= 8);
+        bool have_tile = !(unified(COLOUR) && dry >= 8);
         if (!kq->dynamic) {                     // static launch: exactly one unit per wave
             if (dry) return;
             const long unit = (long)xcd_remap(blockIdx.x, gridDim.x) * (blockDim.x >> 6) + wave;
@@ -2232,25 +2245,25 @@ render_fused_kernel(const KArgs ka) {
             // every tile of the launch (32 consecutive slots; chained form: the units of chain_plan())
             long n_tiles = (kq->n_rays + RAYS_PER_WAVE - 1) / RAYS_PER_WAVE;
             ChainPlan plan;
-            if constexpr (CHAIN) { plan = chain_plan(kq); n_tiles = plan.bulk_tiles + plan.rem_tiles; }
+            if constexpr (LOOP == Loop::CHAINED) { plan = chain_plan(kq); n_tiles = plan.bulk_tiles + plan.rem_tiles; }
             // fewer tiles than waves: deal them evenly, so that every CU runs the same few waves (each then steps faster) rather
             // than the first workgroups to arrive running eight and the rest none
             const long share = (n_tiles + gridDim.x - 1) / gridDim.x;
-            if (wave >= share) { if constexpr (UNI) { have_tile = false; dry = 8; } else return; }
+            if (wave >= share) { if constexpr (unified(COLOUR)) { have_tile = false; dry = 8; } else return; }
             STAMP_T0();
             if (have_tile) {
             const unsigned t = wave_add(kq->queue + qx, 1u, lane);
             STAMP_ADD(9, lane);
             if ((long)t >= queue_len(n_tiles, kq->chunk, qx)) {     // this XCD's queue is dry: move on to the next one
                 qx = (qx + 1) & 7;
-                if (++dry == 8) { if constexpr (!UNI) return; }
-                if (!UNI || dry < 8) continue;
+                if (++dry == 8) { if constexpr (!unified(COLOUR)) return; }
+                if (!unified(COLOUR) || dry < 8) continue;
                 have_tile = false;
             } else
             tile = queue_tile(kq->chunk, qx, t);
             }
-            if constexpr (CULL) { if (kq->tile_order) tile = kq->tile_order[tile]; }
-            if constexpr (CHAIN) {
+            if constexpr (LOOP == Loop::CULLED) { if (kq->tile_order) tile = kq->tile_order[tile]; }
+            if constexpr (LOOP == Loop::CHAINED) {
                 seg = kq->seg;
                 samples_per_step = 1; entry_base = 0;
                 if (tile >= plan.bulk_tiles) { samples_per_step = plan.rem_p; entry_base = plan.bulk_tiles * RAYS_PER_WAVE; tile -= plan.bulk_tiles; }
@@ -2262,19 +2275,19 @@ render_fused_kernel(const KArgs ka) {
         constexpr int F = FORM == FORM_F32_FIXUP ? FORM_F32 : FORM;
         STAMP_T0();
         if (have_tile) {
-        if constexpr (CHAIN) {
-            if (samples_per_step == 8) render_tile<F, true, 8, false, GDEF, GDEF, UNI>(lds, lane, tile, seg, entry_base);
-            else if (samples_per_step == 4) render_tile<F, true, 4, false, GDEF, GDEF, UNI>(lds, lane, tile, seg, entry_base);
-            else if (samples_per_step == 2) render_tile<F, true, 2, false, GDEF, GDEF, UNI>(lds, lane, tile, seg, entry_base);
-            else render_tile<F, true, 1, false, DEFER, GDEF, UNI>(lds, lane, tile, seg, entry_base);
+        if constexpr (LOOP == Loop::CHAINED) {
+            if (samples_per_step == 8) render_tile<F, LOOP, 8, group_colour(COLOUR)>(lds, lane, tile, seg, entry_base);
+            else if (samples_per_step == 4) render_tile<F, LOOP, 4, group_colour(COLOUR)>(lds, lane, tile, seg, entry_base);
+            else if (samples_per_step == 2) render_tile<F, LOOP, 2, group_colour(COLOUR)>(lds, lane, tile, seg, entry_base);
+            else render_tile<F, LOOP, 1, COLOUR>(lds, lane, tile, seg, entry_base);
         } else {
-            render_tile<F, false, 1, CULL, DEFER, GDEF, UNI>(lds, lane, tile, seg);
+            render_tile<F, LOOP, 1, COLOUR>(lds, lane, tile, seg);
         }
         STAMP_ADD(8, lane);
         WT(3);
         WT_COUNT();
         }
-        if constexpr (UNI) {
+        if constexpr (unified(COLOUR)) {
             // no tile left: report done once, then drain -- evaluate units until every wavefront has listed its last entry
             // (render_tile flushes at every tile's end) and this one's ticket lies beyond the list.  ONE consume_unit site (the
             // colour branch's code is 28 KB of the instruction cache).
@@ -2298,7 +2311,7 @@ render_fused_kernel(const KArgs ka) {
 }
 
 
-// Frame-level deferral, second launch: the colour branch of the entries render_fused_kernel<., ., ., true, true> appended, 32 per
+// Frame-level deferral, second launch: the colour branch of the entries a Colour::LIST launch appended, 32 per
 // wavefront step, by persistent workgroups on a unit queue (unit = 32 consecutive entries: neighbouring tiles' samples, dealt to the
 // XCDs in chunks like the tiles).  A unit costs the same whichever rays its entries belong to, so the launch ends with every
 // wavefront within one ~15 us unit of the others -- where the tile-level passes left a frame's end to whichever wavefronts had
@@ -3303,16 +3316,12 @@ MaskLayout mask_layout(int64_t n_rays) {
 
 // The arithmetic of a call: the split-precision forms under GPNERF_FLAG_SPLIT_F16; otherwise the fp32 form in reference order
 // (FORM_F32, head_blob_ref) unless the frame carries folded volumes and the caller did not ask for the reference's order.  The
-// guarded split form's fix-up launch is the reference-order form too.
-enum { SEL_REF = 0, SEL_FOLD = 1, SEL_SPLIT = 2, SEL_GUARD = 3 };
+// guarded split form's fix-up launch is the reference-order form too (SEL_FIXUP: launch_render's name for it, never a plan's).
+enum { SEL_REF = 0, SEL_FOLD = 1, SEL_SPLIT = 2, SEL_GUARD = 3, SEL_FIXUP = 4 };
 int render_sel(uint32_t flags, bool folded) {
     if (flags & GPNERF_FLAG_SPLIT_F16) return (flags & GPNERF_FLAG_SPLIT_GUARD) ? SEL_GUARD : SEL_SPLIT;
     return folded && !(flags & GPNERF_FLAG_REF_ORDER) ? SEL_FOLD : SEL_REF;
 }
-// Where a sample's colour branch runs: in the STEP (GPNERF_FLAG_NO_EXITS, a `raw` output); deferred to each WAVEfront's own queue
-// (render_tile); LISTed for the launch as a whole and evaluated by colour_units_kernel; or listed and evaluated by the listing
-// launch's own wavefronts once they have no tile left (UNIFIED).
-enum class Colour { STEP, WAVE, LIST, UNIFIED };
 // The render launches of a call: STATIC, one unit per wave (a split tile's segment, perhaps); persistent workgroups on the tile
 // QUEUE; the same over the whole rounds and a launch of the segmented form over the remaining tiles (QUEUE_REMAINDER); ONE launch
 // of the segmented form whose units are the whole rounds' tiles and the remainder's (REMAINDER_UNITS); early termination's
@@ -3472,9 +3481,40 @@ KArgs one_segment(const KArgs& ka, long first, long items, unsigned* queue, unsi
     return k;
 }
 
-// One launch of the fused kernel: which arithmetic (`sel`), where the colour branch runs, and the sample loop (chained segments /
-// culled) as template arguments.  Dynamic LDS = the form's head image (+ the split form's guard slots) + the wavefronts' colour
-// queues.
+// Dynamic LDS of a launch of the fused kernel: the form's head image (+ the guarded split form's slots and dummy words) + the
+// wavefronts' colour queues and tallies (render_tile's QUEUE_AT)
+constexpr size_t render_lds_bytes(int form) {
+    return (form == FORM_SPLIT || form == FORM_SPLIT_GUARD ? sizeof(unsigned) * gph::BLOB_WORDS : sizeof(float) * gpl::BLOB_FLOATS) +
+           (form == FORM_SPLIT_GUARD ? GUARD_LDS_SLOTS * 8 : 0) + DEFER_LDS_BYTES;
+}
+// The evaluation of a Colour::LIST launch's entries.  (In front of the variant table on purpose, see there.)
+void launch_colour_units(int sel, int n_cus, hipStream_t stream, const KArgs& ka) {
+    if (sel != SEL_FOLD) hipLaunchKernelGGL((colour_units_kernel<FORM_F32>), dim3((unsigned)n_cus), dim3(64 * UNIT_WAVES), render_lds_bytes(FORM_F32), stream, ka);
+    else hipLaunchKernelGGL((colour_units_kernel<FORM_F32_FOLD>), dim3((unsigned)n_cus), dim3(64 * UNIT_WAVES), render_lds_bytes(FORM_F32_FOLD), stream, ka);
+}
+// The variants of the fused kernel, by (form, loop, colour): null where variant_ok() says there is none.  The ONE place that
+// instantiates render_fused_kernel, so what launch_render() can pick and what device_ready() opts in to its LDS are the same list.
+// The ORDER of instantiation is part of the build: with colour_units_kernel behind these kernels, or the forms in numeric order
+// (the split forms before FORM_F32_FOLD), hipcc allocates the registers of <FORM_SPLIT_GUARD, CHAINED, WAVE> and <FORM_F32_FIXUP,
+// CULLED, STEP> differently (tools/isa_diff.sh).  So the table is filled fp32 forms first and stands behind launch_colour_units().
+typedef void (*RenderKernel)(const KArgs);
+constexpr int N_VARIANTS = N_FORMS * N_LOOPS * N_COLOURS;
+constexpr int FILL_ORDER[N_FORMS] = {FORM_F32, FORM_F32_FOLD, FORM_SPLIT, FORM_SPLIT_GUARD, FORM_F32_FIXUP};
+constexpr int variant_index(int form, Loop loop, Colour colour) { return (form * N_LOOPS + (int)loop) * N_COLOURS + (int)colour; }
+struct VariantTable { RenderKernel fn[N_VARIANTS]; };
+template <int I> constexpr void variant_entry(VariantTable& t) {
+    constexpr int form = FILL_ORDER[I / (N_LOOPS * N_COLOURS)];
+    constexpr Loop loop = (Loop)(I / N_COLOURS % N_LOOPS);
+    constexpr Colour colour = (Colour)(I % N_COLOURS);
+    if constexpr (variant_ok(form, loop, colour)) t.fn[variant_index(form, loop, colour)] = &render_fused_kernel<form, loop, colour>;
+}
+template <int... I>       // (a LEFT fold: entry 0 is instantiated first)
+constexpr VariantTable variant_table(std::integer_sequence<int, I...>) { VariantTable t{}; (..., variant_entry<I>(t)); return t; }
+constexpr VariantTable g_variants = variant_table(std::make_integer_sequence<int, N_VARIANTS>{});
+RenderKernel render_variant(int form, Loop loop, Colour colour) { return g_variants.fn[variant_index(form, loop, colour)]; }
+
+// One launch of the fused kernel: which arithmetic (`sel`), its sample loop and where the colour branch runs.  False, and nothing
+// enqueued, where the fused kernel has no such variant: a refused launch (GPNERF_E_LAUNCH), never another variant in its place.
 // Every form defers the colour branch (round 6; rounds 1-5 kept it in the step for the split-precision forms).  Round 5 built the
 // split forms' deferral (bench frame 7.3 -> 6.4 ms) and did not ship it: ONE build's unguarded instantiation gave colour passes
 // 10-30 % off, the same wrong values on every box, cured by any change that moved the schedule (an opaque copy of the regathered
@@ -3488,28 +3528,16 @@ KArgs one_segment(const KArgs& ka, long first, long items, unsigned* queue, unsi
 // -- so the instance stays inferred; the class is measured.)  Since round 6 every fragment that becomes an MFMA operand passes
 // through settle_operand(), which carries the wait state itself, and tools/isa_mfma_hazards.py fails the CPU suite on any
 // inline-asm producer closer to its MFMA than the measured requirement (tests/test_abi.py).
-template <int FORM, bool CHAIN, bool CULL>
-void launch_form(Colour colour, dim3 grid, dim3 block, size_t lds, hipStream_t stream, const KArgs& ka) {
-    if constexpr ((FORM == FORM_F32 || FORM == FORM_F32_FOLD) && !CULL) {
-        // (the unified form's wavefronts wait for each other -- every one reports before any leaves -- which assumes the grid becomes
-        //  resident without depending on another tenant that waits the same way: GPNERF_FLAG_SHARED_DEVICE selects the second kernel.
-        //  As a cooperative launch, which guarantees residency, it cost 0.04 ms per call and, with the next frame's producers on a
-        //  second stream, the whole overlap of the pipelined evaluation loop: 7.0 -> 8.5 ms per frame)
-        if (colour == Colour::UNIFIED) { hipLaunchKernelGGL((render_fused_kernel<FORM, CHAIN, false, true, true, true>), grid, block, lds, stream, ka); return; }
-        if (colour == Colour::LIST) { hipLaunchKernelGGL((render_fused_kernel<FORM, CHAIN, false, true, true>), grid, block, lds, stream, ka); return; }
-    }
-    if (colour != Colour::STEP) { hipLaunchKernelGGL((render_fused_kernel<FORM, CHAIN, CULL, true>), grid, block, lds, stream, ka); return; }
-    hipLaunchKernelGGL((render_fused_kernel<FORM, CHAIN, CULL, false>), grid, block, lds, stream, ka);
-}
-template <bool CHAIN, bool CULL>
-void launch_render(int sel, Colour colour, dim3 grid, dim3 block, hipStream_t stream, const KArgs& ka) {
-    const size_t f32 = sizeof(float) * gpl::BLOB_FLOATS + DEFER_LDS_BYTES, split = sizeof(unsigned) * gph::BLOB_WORDS + DEFER_LDS_BYTES;
-    switch (sel) {
-        case SEL_GUARD: launch_form<FORM_SPLIT_GUARD, CHAIN, CULL>(colour, grid, block, split + GUARD_LDS_SLOTS * 8, stream, ka); break;
-        case SEL_SPLIT: launch_form<FORM_SPLIT, CHAIN, CULL>(colour, grid, block, split, stream, ka); break;
-        case SEL_FOLD:  launch_form<FORM_F32_FOLD, CHAIN, CULL>(colour, grid, block, f32, stream, ka); break;
-        default:        launch_form<FORM_F32, CHAIN, CULL>(colour, grid, block, f32, stream, ka); break;
-    }
+bool launch_render(int sel, Loop loop, Colour colour, dim3 grid, dim3 block, hipStream_t stream, const KArgs& ka) {
+    const int form = sel == SEL_GUARD ? FORM_SPLIT_GUARD : sel == SEL_SPLIT ? FORM_SPLIT : sel == SEL_FOLD ? FORM_F32_FOLD : sel == SEL_FIXUP ? FORM_F32_FIXUP : FORM_F32;
+    const RenderKernel fn = render_variant(form, loop, colour);
+    if (!fn) return false;
+    // (the unified form's wavefronts wait for each other -- every one reports before any leaves -- which assumes the grid becomes
+    //  resident without depending on another tenant that waits the same way: GPNERF_FLAG_SHARED_DEVICE plans Colour::LIST instead.
+    //  As a cooperative launch, which guarantees residency, it cost 0.04 ms per call and, with the next frame's producers on a
+    //  second stream, the whole overlap of the pipelined evaluation loop: 7.0 -> 8.5 ms per frame)
+    hipLaunchKernelGGL(fn, grid, block, render_lds_bytes(form), stream, ka);
+    return true;
 }
 
 hipStream_t S_(void* s) { return reinterpret_cast<hipStream_t>(s); }
@@ -3554,50 +3582,24 @@ int device_ready(int* cus) {
         hipDeviceProp_t prop;
         if (hipGetDeviceProperties(&prop, dev) == hipSuccess && strncmp(prop.gcnArchName, "gfx950", 6) == 0) {
             d.cus = prop.multiProcessorCount;
-            const size_t lds_bytes = sizeof(float) * gpl::BLOB_FLOATS + DEFER_LDS_BYTES, lds_split = sizeof(unsigned) * gph::BLOB_WORDS;
             auto lds_ok = [](const void* fn, size_t bytes) {
                 return hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) == hipSuccess;
             };
             d.ok = true;
-            // every instantiation the launches below can pick: form x (plain, chained, culled) x (colour branch in the step, deferred)
-            auto all_of = [&](auto form_tag, size_t bytes) {
-                constexpr int F = decltype(form_tag)::value;
-                d.ok = d.ok && lds_ok(reinterpret_cast<const void*>(&render_fused_kernel<F, false, false, false>), bytes) &&
-                       lds_ok(reinterpret_cast<const void*>(&render_fused_kernel<F, true, false, false>), bytes) &&
-                       lds_ok(reinterpret_cast<const void*>(&render_fused_kernel<F, false, true, false>), bytes) &&
-                       lds_ok(reinterpret_cast<const void*>(&render_fused_kernel<F, false, false, true>), bytes) &&
-                       lds_ok(reinterpret_cast<const void*>(&render_fused_kernel<F, true, false, true>), bytes) &&
-                       lds_ok(reinterpret_cast<const void*>(&render_fused_kernel<F, false, true, true>), bytes);
+            for (int i = 0; i < N_VARIANTS; ++i)        // every variant a launch can pick
+                if (g_variants.fn[i]) d.ok = d.ok && lds_ok(reinterpret_cast<const void*>(g_variants.fn[i]), render_lds_bytes(i / (N_LOOPS * N_COLOURS)));
+            const size_t head_bytes = sizeof(float) * gpl::BLOB_FLOATS;
+            const struct { const void* fn; size_t bytes; } others[] = {
+                {reinterpret_cast<const void*>(&colour_units_kernel<FORM_F32>), render_lds_bytes(FORM_F32)},
+                {reinterpret_cast<const void*>(&colour_units_kernel<FORM_F32_FOLD>), render_lds_bytes(FORM_F32_FOLD)},
+                {reinterpret_cast<const void*>(&head_forward_kernel<FUSED_WAVES, 0>), render_lds_bytes(FORM_F32)},
+                {reinterpret_cast<const void*>(&head_forward_kernel<FUSED_WAVES, 1>), render_lds_bytes(FORM_F32)},
+                {reinterpret_cast<const void*>(&head_forward_kernel<FUSED_WAVES, 2>), render_lds_bytes(FORM_F32)},
+                {reinterpret_cast<const void*>(&density_lattice_kernel), head_bytes},
+                {reinterpret_cast<const void*>(&field_points_kernel<true>), head_bytes},
+                {reinterpret_cast<const void*>(&field_points_kernel<false>), head_bytes},
             };
-            all_of(std::integral_constant<int, FORM_F32>{}, lds_bytes);
-            all_of(std::integral_constant<int, FORM_F32_FOLD>{}, lds_bytes);
-            // frame-level deferral (fp32 forms)
-            d.ok = d.ok && lds_ok(reinterpret_cast<const void*>(&render_fused_kernel<FORM_F32, false, false, true, true>), lds_bytes) &&
-                   lds_ok(reinterpret_cast<const void*>(&render_fused_kernel<FORM_F32_FOLD, false, false, true, true>), lds_bytes) &&
-                   lds_ok(reinterpret_cast<const void*>(&render_fused_kernel<FORM_F32, false, false, true, true, true>), lds_bytes) &&
-                   lds_ok(reinterpret_cast<const void*>(&render_fused_kernel<FORM_F32_FOLD, false, false, true, true, true>), lds_bytes) &&
-                   lds_ok(reinterpret_cast<const void*>(&render_fused_kernel<FORM_F32, true, false, true, true, true>), lds_bytes) &&
-                   lds_ok(reinterpret_cast<const void*>(&render_fused_kernel<FORM_F32_FOLD, true, false, true, true, true>), lds_bytes) &&
-                   lds_ok(reinterpret_cast<const void*>(&render_fused_kernel<FORM_F32, true, false, true, true>), lds_bytes) &&
-                   lds_ok(reinterpret_cast<const void*>(&render_fused_kernel<FORM_F32_FOLD, true, false, true, true>), lds_bytes) &&
-                   lds_ok(reinterpret_cast<const void*>(&colour_units_kernel<FORM_F32>), lds_bytes) &&
-                   lds_ok(reinterpret_cast<const void*>(&colour_units_kernel<FORM_F32_FOLD>), lds_bytes);
-            all_of(std::integral_constant<int, FORM_SPLIT>{}, lds_split + DEFER_LDS_BYTES);
-            all_of(std::integral_constant<int, FORM_SPLIT_GUARD>{}, lds_split + GUARD_LDS_SLOTS * 8 + DEFER_LDS_BYTES);
-            d.ok = d.ok && lds_ok(reinterpret_cast<const void*>(&render_fused_kernel<FORM_F32_FIXUP, false>), lds_bytes) &&
-                   lds_ok(reinterpret_cast<const void*>(&render_fused_kernel<FORM_F32_FIXUP, false, true>), lds_bytes) &&
-                   hipFuncSetAttribute(reinterpret_cast<const void*>(&head_forward_kernel<FUSED_WAVES, 0>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes) == hipSuccess &&
-                   hipFuncSetAttribute(reinterpret_cast<const void*>(&head_forward_kernel<FUSED_WAVES, 1>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes) == hipSuccess &&
-                   hipFuncSetAttribute(reinterpret_cast<const void*>(&head_forward_kernel<FUSED_WAVES, 2>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes) == hipSuccess &&
-                   hipFuncSetAttribute(reinterpret_cast<const void*>(&density_lattice_kernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sizeof(float) * gpl::BLOB_FLOATS)) == hipSuccess &&
-                   hipFuncSetAttribute(reinterpret_cast<const void*>(&field_points_kernel<true>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sizeof(float) * gpl::BLOB_FLOATS)) == hipSuccess &&
-                   hipFuncSetAttribute(reinterpret_cast<const void*>(&field_points_kernel<false>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sizeof(float) * gpl::BLOB_FLOATS)) == hipSuccess;
+            for (const auto& o : others) d.ok = d.ok && lds_ok(o.fn, o.bytes);
         }
         (void)hipGetLastError();
     }
@@ -4002,7 +4004,7 @@ int gpnerf_render_fused(const GpnerfFrame* f, const float* rays, int64_t n_rays,
 
     const dim3 grid(p.grid), block(p.g.waves * 64);
     if (p.shape == Shape::REMAINDER_UNITS) {
-        launch_render<true, false>(p.sel, p.colour, grid, block, S_(stream), one_segment(ka, 0, (long)n_rays, ka.queue, p.grid));
+        if (!launch_render(p.sel, Loop::CHAINED, p.colour, grid, block, S_(stream), one_segment(ka, 0, (long)n_rays, ka.queue, p.grid))) return GPNERF_E_LAUNCH;
     } else if (p.shape == Shape::CHAINED) {
         // every segment's launch is enqueued -- one that finds its list empty returns before it stages anything
         const ChainLayout cl = chain_layout(n_rays, n_samples);
@@ -4028,7 +4030,7 @@ int gpnerf_render_fused(const GpnerfFrame* f, const float* rays, int64_t n_rays,
             kc.list_out = last ? nullptr : sparse;
             kc.count_out = ctrl + 8 * n_seg + sg;
             kc.chunk_cnt = ctrl + 9 * n_seg + (size_t)sg * n_chunks;
-            launch_render<true, false>(p.sel, p.colour, grid, block, S_(stream), kc);
+            if (!launch_render(p.sel, Loop::CHAINED, p.colour, grid, block, S_(stream), kc)) return GPNERF_E_LAUNCH;
             if (!last)     // close the gaps of the sparse list, in order: the next launch's dense input
                 hipLaunchKernelGGL(compact_list_kernel, dim3((unsigned)n_chunks), dim3(256), 0, S_(stream), (const int*)sparse,
                                    (const unsigned*)kc.chunk_cnt, (const unsigned*)kc.count_in, kc.first_items, lists[sg & 1], kc.count_out);
@@ -4050,21 +4052,18 @@ int gpnerf_render_fused(const GpnerfFrame* f, const float* rays, int64_t n_rays,
                 if (hipGetLastError() != hipSuccess) return GPNERF_E_LAUNCH;
                 ka.tile_order = order;
             }
-            launch_render<false, true>(p.sel, p.colour, grid, block, S_(stream), ka);
-        } else
-            launch_render<false, false>(p.sel, p.colour, grid, block, S_(stream), ka);
+        }
+        if (!launch_render(p.sel, p.mask.bytes ? Loop::CULLED : Loop::PLAIN, p.colour, grid, block, S_(stream), ka)) return GPNERF_E_LAUNCH;
         if (p.shape == Shape::QUEUE_REMAINDER) {       // the remainder on the second set of queue counters
             if (hipGetLastError() != hipSuccess) return GPNERF_E_LAUNCH;
-            launch_render<true, false>(p.sel, p.colour, grid, block, S_(stream),
-                                       one_segment(ka, (long)p.main_rays, (long)(n_rays - p.main_rays), ka.queue + 8, p.grid));
+            if (!launch_render(p.sel, Loop::CHAINED, p.colour, grid, block, S_(stream),
+                               one_segment(ka, (long)p.main_rays, (long)(n_rays - p.main_rays), ka.queue + 8, p.grid))) return GPNERF_E_LAUNCH;
         }
     }
     if (hipGetLastError() != hipSuccess) return GPNERF_E_LAUNCH;
-    const size_t lds_bytes = sizeof(float) * gpl::BLOB_FLOATS + DEFER_LDS_BYTES;       // head image + the wavefronts' colour queues (render_tile)
     if (p.list.bytes) {         // the list's evaluation, unless the launch's own wavefronts have done it, then every ray's colour map
         if (p.colour == Colour::LIST) {
-            if (p.sel == SEL_FOLD) hipLaunchKernelGGL((colour_units_kernel<FORM_F32_FOLD>), dim3((unsigned)n_cus), dim3(64 * UNIT_WAVES), lds_bytes, S_(stream), ka);
-            else hipLaunchKernelGGL((colour_units_kernel<FORM_F32>), dim3((unsigned)n_cus), dim3(64 * UNIT_WAVES), lds_bytes, S_(stream), ka);
+            launch_colour_units(p.sel, n_cus, S_(stream), ka);
             if (hipGetLastError() != hipSuccess) return GPNERF_E_LAUNCH;
         }
         hipLaunchKernelGGL(colour_accumulate_kernel, dim3((unsigned)((n_rays + 255) / 256)), dim3(256), 0, S_(stream), (const int*)ka.gd_cnt,
@@ -4081,8 +4080,7 @@ int gpnerf_render_fused(const GpnerfFrame* f, const float* rays, int64_t n_rays,
         kf.flags = (unsigned)flags & ~(GPNERF_FLAG_SPLIT_F16 | GPNERF_FLAG_SPLIT_GUARD);
         kf.split = 1; kf.part = nullptr; kf.dynamic = 1; kf.queue = ka.guard + 8;
         const dim3 fgrid(full_grid(p.tiles, n_cus)), fblock(GPNERF_MAX_WAVES * 64);
-        if (kf.cull_mask) hipLaunchKernelGGL((render_fused_kernel<FORM_F32_FIXUP, false, true>), fgrid, fblock, lds_bytes, S_(stream), kf);
-        else hipLaunchKernelGGL((render_fused_kernel<FORM_F32_FIXUP, false>), fgrid, fblock, lds_bytes, S_(stream), kf);
+        if (!launch_render(SEL_FIXUP, kf.cull_mask ? Loop::CULLED : Loop::PLAIN, Colour::STEP, fgrid, fblock, S_(stream), kf)) return GPNERF_E_LAUNCH;
     }
     return launch_status();
 }

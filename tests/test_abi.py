@@ -303,3 +303,49 @@ def test_the_ticket_checker_flags_an_unwaited_store():
     assert tool.check(rows(good)) == (1, [])
     assert len(tool.check(rows(late))[1]) == 1 and "not waited for" in tool.check(rows(late))[1][0][2]
     assert len(tool.check(rows(none))[1]) == 1 and "no s_barrier" in tool.check(rows(none))[1][0][2]
+
+
+def test_the_library_holds_exactly_the_fused_kernels_variants_the_rules_allow(tmp_path):
+    """render_fused_kernel<FORM, Loop, Colour> is instantiated in ONE place (gpnerf_kernels.hip's variant table, from variant_ok()),
+    which launch_render() picks from and device_ready() walks for the > 64 KB LDS opt-in.  A variant missing from the build shows as
+    a refused launch on a device only, an extra one only as compile time: the gfx950 code object must hold exactly the 34 written
+    out below -- 4 forms x {PLAIN, CHAINED, CULLED} x {STEP, WAVE}; the fp32 forms x {PLAIN, CHAINED} x {LIST, UNIFIED}; the
+    fix-up form x {PLAIN, CULLED} x STEP -- and the two colour_units_kernel."""
+    import glob
+    import shutil
+    objdump = shutil.which("llvm-objdump") or "/opt/rocm/lib/llvm/bin/llvm-objdump"
+    lib = str(tmp_path / "lib.so")
+    shutil.copy(os.path.join(ROOT, "gp-nerf_amd", "csrc", "libgpnerf_hip.so"), lib)
+    subprocess.run([objdump, "--offloading", lib], cwd=str(tmp_path), stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, check=True)
+    objects = sorted(glob.glob(lib + ".*gfx950*"))
+    assert objects, "no gfx950 code object in the library"
+    names = []
+    for co in objects:
+        for line in subprocess.run([objdump, "-t", co], capture_output=True, text=True, check=True).stdout.split("\n"):
+            cols = line.split()
+            if len(cols) >= 5 and cols[2] == "F" and cols[3] == ".text":      # functions (not their .kd descriptors, not the resource symbols)
+                names.append(cols[-1])
+    assert len(names) == len(set(names))
+    F32, SPLIT, SPLIT_GUARD, F32_FIXUP, F32_FOLD = range(5)
+    PLAIN, CHAINED, CULLED = range(3)
+    STEP, WAVE, LIST, UNIFIED = range(4)
+    expected = {
+        (F32, PLAIN, STEP), (F32, PLAIN, WAVE), (F32, CHAINED, STEP), (F32, CHAINED, WAVE), (F32, CULLED, STEP), (F32, CULLED, WAVE),
+        (SPLIT, PLAIN, STEP), (SPLIT, PLAIN, WAVE), (SPLIT, CHAINED, STEP), (SPLIT, CHAINED, WAVE), (SPLIT, CULLED, STEP), (SPLIT, CULLED, WAVE),
+        (SPLIT_GUARD, PLAIN, STEP), (SPLIT_GUARD, PLAIN, WAVE), (SPLIT_GUARD, CHAINED, STEP), (SPLIT_GUARD, CHAINED, WAVE),
+        (SPLIT_GUARD, CULLED, STEP), (SPLIT_GUARD, CULLED, WAVE),
+        (F32_FOLD, PLAIN, STEP), (F32_FOLD, PLAIN, WAVE), (F32_FOLD, CHAINED, STEP), (F32_FOLD, CHAINED, WAVE), (F32_FOLD, CULLED, STEP),
+        (F32_FOLD, CULLED, WAVE),
+        (F32, PLAIN, LIST), (F32, PLAIN, UNIFIED), (F32, CHAINED, LIST), (F32, CHAINED, UNIFIED),
+        (F32_FOLD, PLAIN, LIST), (F32_FOLD, PLAIN, UNIFIED), (F32_FOLD, CHAINED, LIST), (F32_FOLD, CHAINED, UNIFIED),
+        (F32_FIXUP, PLAIN, STEP), (F32_FIXUP, CULLED, STEP),
+    }
+    assert len(expected) == 34
+    fused = [n for n in names if "render_fused_kernel" in n]
+    # Itanium mangling of <int, Loop, Colour>: ILi<form>ELNS_4LoopE<loop>ELNS_6ColourE<colour>E
+    parsed = [re.search(r"19render_fused_kernelILi(\d+)ELNS_4LoopE(\d+)ELNS_6ColourE(\d+)EEEv", n) for n in fused]
+    assert all(parsed), [n for n, m in zip(fused, parsed) if not m]
+    got = [tuple(int(g) for g in m.groups()) for m in parsed]
+    assert len(got) == 34 and set(got) == expected, (sorted(set(got) - expected), sorted(expected - set(got)))
+    units = sorted(n for n in names if "colour_units_kernel" in n)
+    assert [re.search(r"19colour_units_kernelILi(\d+)EEEv", n).group(1) for n in units] == [str(F32), str(F32_FOLD)], units

@@ -179,7 +179,7 @@ def check(pt, rc, p, guard_bytes, lbytes):
         assert q_b == QUEUE_BYTES and S >= 8 and n_cus >= 8 and not early and not occ, (pt, p)       # (both launches' counters: words 0..15)
     if shape == CHAINED:
         assert early and n_cus >= 8 and tiles >= n_cus * 8, (pt, p)
-    # 5. the colour mode against what the kernels can do (render_fused_kernel's and launch_form's static_asserts)
+    # 5. the colour mode against what the kernels can do (variant_ok() in gpnerf_kernels.hip, which render_fused_kernel asserts and the variant table is built from)
     assert (colour == STEP) == bool(no_exits or out == OUT_RAW), (pt, p)
     assert (l_b > 0) == (colour in (LIST, UNIFIED)), (pt, p)
     if l_b:

@@ -16,6 +16,7 @@ def kernels(p):
     for l in open(p):
         m = re.match(r"^[0-9a-f]+ <(\S+)>:", l)
         if m: cur = m.group(1); out[cur] = []
+        elif "file format" in l or l.startswith("Disassembly of section"): cur = None     # the next code object's header (its path differs per run)
         elif cur is not None and l.strip(): out[cur].append(re.sub(r"^[0-9a-f]+:?\s*", "", l.strip()))
     return out
 a, b = kernels("/tmp/isa_a.txt"), kernels("/tmp/isa_b.txt")

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Collect rocprofv3 PMC counters for the fused kernel in separate passes (never combined with tracing).
-# usage: [PMC_KERNEL='render_fused_kernel<0, false, false, true>'] tools/pmc_passes.sh <tag> [bench args...]   -> gpurun_out/pmc_<tag>/passN/, summary.json
+# usage: [PMC_KERNEL='render_fused_kernel<0, ((anonymous namespace)::Loop)0, ((anonymous namespace)::Colour)3>'] tools/pmc_passes.sh <tag> [bench args...]   -> $out/passN/, $out/summary.json ($out: below)
 set -u
 tag=$1; shift
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"

@@ -2,9 +2,12 @@
 """Summarise rocprofv3 --pmc CSVs: per-counter mean over the dispatches of one kernel, or per CALL over the kernels of one call.
 usage: pmc_summary.py gpurun_out/pmc_<tag> [kernel-name substring[+substring...], default "render_fused"] [output file name, default summary.json]
 (bench.py launches several instantiations in one process -- the headline, the diagnostic step_stats launch of the same kernels, and
-the dense GPNERF_FLAG_NO_EXITS launch `render_fused_kernel<0, false, false, false, false>` -- so the caller names the one it wants.
-Since round 6 one gpnerf_render_fused call of the default path is several kernels -- the sample loop `render_fused_kernel<0, false,
-false, true, true>` (one launch per sample segment in the chained form), `colour_units_kernel<0>` and `colour_accumulate_kernel`.
+the dense GPNERF_FLAG_NO_EXITS launch, render_fused_kernel<FORM_F32, Loop::PLAIN, Colour::STEP> -- so the caller names the one it wants.
+Since round 6 one gpnerf_render_fused call of the default path is several kernels -- the sample loop render_fused_kernel<FORM_F32,
+Loop::PLAIN, Colour::UNIFIED> or, listing for `colour_units_kernel<0>`, <.., Colour::LIST> (one launch per sample segment under
+Loop::CHAINED), and `colour_accumulate_kernel`.  A name substring has to be what rocprofv3 prints, which is the enumerators' VALUES: the headline's
+sample loop is `render_fused_kernel<0, ((anonymous namespace)::Loop)0, ((anonymous namespace)::Colour)3>` (form, Loop 0..2 =
+PLAIN / CHAINED / CULLED, Colour 0..3 = STEP / WAVE / LIST / UNIFIED; taken from a --kernel-trace --stats run of bench.py).
 "a+b+c" gives counters per CALL: every dispatch of the named kernels added up, divided by the dispatches of the LAST name, which
 runs once per call; each part's own per-dispatch means are kept under "parts")"""
 import csv

@@ -80,9 +80,12 @@ def main():
                   "A spilled VGPR comes back as `scratch_load`, a spilled SGPR as `v_readlane`.  Per sample loop (the chained form has one copy of the loop",
                   "per samples-per-step variant P = 1, 2, 4, 8): instructions of one iteration, MFMAs, and the spill instructions among them; `outside`: the rest of the kernel.", "",
                   "| instantiation | loop | instructions | MFMAs | scratch_load | scratch_store | v_readlane | v_writelane |", "|---|---|---|---|---|---|---|---|"]
-        for inst, key in (("<FORM_F32_FOLD, plain> (headline)", "render_fused_kernelILi4ELb0ELb0E"), ("<FORM_F32, plain>", "render_fused_kernelILi0ELb0ELb0E"),
-                          ("<FORM_F32_FOLD, chained> (configs[2])", "render_fused_kernelILi4ELb1ELb0E"), ("<FORM_F32_FOLD, culled>", "render_fused_kernelILi4ELb0ELb1E"),
-                          ("<FORM_SPLIT_GUARD, plain>", "render_fused_kernelILi2ELb0ELb0E")):
+        # render_fused_kernel<FORM, Loop, Colour> mangles as ILi<form>ELNS_4LoopE<loop>ELNS_6ColourE<colour>E
+        for inst, key in (("<FORM_F32_FOLD, PLAIN, UNIFIED> (headline)", "render_fused_kernelILi4ELNS_4LoopE0ELNS_6ColourE3E"),
+                          ("<FORM_F32, PLAIN, UNIFIED>", "render_fused_kernelILi0ELNS_4LoopE0ELNS_6ColourE3E"),
+                          ("<FORM_F32_FOLD, CHAINED, UNIFIED> (configs[2])", "render_fused_kernelILi4ELNS_4LoopE1ELNS_6ColourE3E"),
+                          ("<FORM_F32_FOLD, CULLED, WAVE>", "render_fused_kernelILi4ELNS_4LoopE2ELNS_6ColourE1E"),
+                          ("<FORM_SPLIT_GUARD, PLAIN, WAVE>", "render_fused_kernelILi2ELNS_4LoopE0ELNS_6ColourE1E")):
             st, outside = loops(rows, key)
             for h, c in st.items():
                 lines.append(f"| {inst} | {h} | {c['n']} | {c['mfma']} | {c['scratch_load']} | {c['scratch_store']} | {c['v_readlane']} | {c['v_writelane']} |")
