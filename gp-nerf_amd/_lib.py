@@ -123,6 +123,8 @@ FLAG_NO_EXITS = 128
 FLAG_SHARED_DEVICE = 256
 FLAG_DENSITY_ONLY = 512
 FOLD_FIRST_LEVEL = 2
+# gpnerf_image_metrics' slot (include/gpnerf_hip.h GPNERF_METRICS_*)
+METRICS_MSE, METRICS_SSIM, METRICS_X, METRICS_Y, METRICS_W, METRICS_H, METRICS_POPULATION, METRICS_STATUS, METRICS_DOUBLES = range(9)
 
 # every symbol include/gpnerf_hip.h declares: (restype, argtypes)
 SYMBOLS = {
@@ -207,6 +209,9 @@ SYMBOLS = {
     "gpnerf_mesh_count": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_float, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "gpnerf_mesh_emit": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_float, C.c_void_p, C.c_size_t, C.c_int64, C.c_int64,
                                    C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gpnerf_metrics_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
+    "gpnerf_image_metrics": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_size_t,
+                                       C.c_void_p, C.c_void_p]),
     "gpnerf_head_layout": (C.c_int, [C.POINTER(C.c_int32)]),
     "gpnerf_strerror": (C.c_char_p, [C.c_int]),
     "gpnerf_rays_per_tile": (C.c_int32, []),

@@ -13,6 +13,10 @@ Image writing (cfg.test.save_imgs) is I/O and out of scope.
 `evaluate_loop` is the evaluation loop around it (libs/trainers/BaseTrainer.py:255-280 `Trainer.evaluate`): per frame
 `render.render(batch)` -> `Evaluator.evaluate`, the render time summed from `ret["rtime"]`, the means from `summarize()`;
 pinned to the reference's own loop over three frames (tests/golden/loop_demo_3frames.npz).
+
+`DeviceEvaluator` (opt-in: `evaluate_loop(device_metrics=True)` or GPNERF_DEVICE_METRICS=1) computes the same three numbers with
+gpnerf_image_metrics (csrc/gpnerf_metrics.hip): four kernel launches per frame into a device slot, no host synchronisation in
+`evaluate`; the host reads every frame's slot in one copy when `.mse` / `.psnr` / `.ssim` are first asked for.
 """
 import math
 import os
@@ -20,6 +24,8 @@ import os
 import numpy as np
 import torch
 import torch.nn.functional as F
+
+from . import _lib as L
 
 _WIN, _K1, _K2, _RANGE = 7, 0.01, 0.03, 2.0
 
@@ -106,7 +112,120 @@ class Evaluator:
         return metrics
 
 
-def evaluate_loop(render, eval_loader, cfg, device=None, quiet=False, pipeline=None):
+class DeviceEvaluator(Evaluator):
+    """`Evaluator` whose `evaluate` only enqueues: gpnerf_image_metrics on `torch.cuda.current_stream()` writes the frame's MSE, SSIM,
+    bounding rectangle, population and status into slot k of a results buffer (chunks of `CHUNK` slots; a full buffer grows by one
+    more chunk, nothing is copied), with one workspace per (stream, H, W): no allocation per frame after the first, no synchronisation.
+    `.mse`, `.psnr`, `.ssim` are read lazily: the first read after an `evaluate` waits for the stream(s), copies the filled slots
+    to the host once and turns them into the Python lists `Evaluator` keeps (PSNR by `psnr_metric`'s formula from the slot's MSE).
+    A frame whose status is not 0 raises at that read what the torch path raises at `evaluate` -- ValueError("win_size exceeds
+    image extent") for an empty mask or a bounding rectangle under 7 pixels, a ValueError naming the two counts where the mask's
+    population is not the number of pixels handed in -- once; the frame is dropped and the other frames keep their numbers.
+    Inputs are float32 CUDA tensors (CPU tensors are refused: there is no fallback); an output with `pred_img` (the progressive
+    renderer's host arrays) goes through the inherited torch path, in frame order.
+    Input lifetime: the kernels read `rgb_map`, `rgb` and the mask in stream order.  Renderer.render's outputs come from torch's
+    caching allocator, which hands a freed block to a later allocation of the SAME stream only -- behind the kernels when that is the
+    stream `evaluate` ran on; a tensor that belongs to another stream is held back by record_stream (a no-op on the tensor's own)."""
+    CHUNK = 1024
+
+    def __init__(self, cfg, seq_name):
+        self._lists = {"mse": [], "psnr": [], "ssim": []}
+        self._pending = []                # (index in the lists, chunk, slot, n) of the frames whose slots have not been read
+        self._chunks, self._filled = [], 0
+        self._workspaces, self._streams = {}, {}
+        super().__init__(cfg, seq_name)
+
+    def _get(name):
+        def get(self):
+            self._drain()
+            return self._lists[name]
+
+        def put(self, value):
+            self._lists[name] = value
+        return property(get, put)
+
+    mse, psnr, ssim = _get("mse"), _get("psnr"), _get("ssim")
+    del _get
+
+    def evaluate(self, output, batch):
+        if "pred_img" in output:
+            return super().evaluate(output, batch)                # (reads the lists: pending slots are drained first, the order holds)
+        rgb_pred = torch.as_tensor(output["rgb_map"][0]).detach()
+        rgb_gt = torch.as_tensor(batch["rgb"][0]).detach()
+        mask = torch.as_tensor(batch["mask_at_box"][0])
+        for name, t in (("rgb_map", rgb_pred), ("rgb", rgb_gt), ("mask_at_box", mask)):
+            if not t.is_cuda:
+                raise ValueError(f"DeviceEvaluator: {name} is a CPU tensor (no CPU fallback: use Evaluator)")
+        dev = rgb_pred.device
+        if rgb_gt.device != dev or mask.device != dev:
+            raise ValueError("DeviceEvaluator: rgb_map, rgb and mask_at_box are on different devices")
+        if rgb_pred.dtype != torch.float32 or rgb_gt.dtype != torch.float32:
+            raise ValueError(f"DeviceEvaluator: float32 colours expected, got {rgb_pred.dtype} and {rgb_gt.dtype}")
+        if rgb_pred.dim() != 2 or rgb_pred.shape[1] != 3 or rgb_gt.shape != rgb_pred.shape:
+            raise ValueError(f"expected two [n,3] colour lists, got {tuple(rgb_pred.shape)} and {tuple(rgb_gt.shape)}")
+        H, W = self._hw()
+        mask = mask.reshape(H * W)
+        mask = mask.view(torch.uint8) if mask.dtype == torch.bool else mask if mask.dtype == torch.uint8 else (mask != 0).view(torch.uint8)
+        rgb_pred, rgb_gt, mask = rgb_pred.contiguous(), rgb_gt.contiguous(), mask.contiguous()
+        n = int(rgb_pred.shape[0])
+        lib = L.lib()
+        stream = torch.cuda.current_stream(dev)
+        key = (stream.cuda_stream, H, W)                          # (a workspace serves one stream's calls, which run in order)
+        ws = self._workspaces.get(key)
+        if ws is None:
+            ws = self._workspaces[key] = torch.empty((int(lib.gpnerf_metrics_workspace_bytes(H, W)),), device=dev, dtype=torch.uint8)
+        chunk, slot = divmod(self._filled, self.CHUNK)
+        if chunk == len(self._chunks):
+            self._chunks.append(torch.empty((self.CHUNK, L.METRICS_DOUBLES), device=dev, dtype=torch.float64))
+        elif self._chunks[chunk].device != dev:
+            raise ValueError("DeviceEvaluator: one evaluator serves one device")
+        for t in (rgb_pred, rgb_gt, mask):
+            t.record_stream(stream)
+        out = self._chunks[chunk].data_ptr() + slot * L.METRICS_DOUBLES * 8
+        # (an empty tensor has no address; the entry point refuses null pointers, and with n = 0 it reads neither list)
+        L.check(lib.gpnerf_image_metrics(rgb_pred.data_ptr() or ws.data_ptr(), rgb_gt.data_ptr() or ws.data_ptr(), mask.data_ptr(), H, W, n,
+                                         ws.data_ptr(), ws.numel(), out, stream.cuda_stream), "gpnerf_image_metrics")
+        self._streams[stream.cuda_stream] = stream
+        self._pending.append((len(self._lists["mse"]), chunk, slot, n))
+        self._filled += 1
+        for v in self._lists.values():
+            v.append(None)
+
+    def _drain(self):
+        if not self._pending:
+            return
+        for s in self._streams.values():
+            s.synchronize()
+        full, rest = divmod(self._filled, self.CHUNK)
+        host = [c[:self.CHUNK if i < full else rest].cpu().numpy() for i, c in enumerate(self._chunks[:full + (1 if rest else 0)])]
+        pending, self._pending, self._filled, self._streams = self._pending, [], 0, {}
+        bad = []
+        for at, chunk, slot, n in pending:
+            r = host[chunk][slot]
+            status = int(r[L.METRICS_STATUS])
+            if status:
+                bad.append((at, status, int(r[L.METRICS_POPULATION]), n))
+                continue
+            mse = float(r[L.METRICS_MSE])
+            self._lists["mse"][at] = mse
+            self._lists["psnr"][at] = -10.0 * math.log(mse) / math.log(10.0) if mse > 0 else float("inf")
+            self._lists["ssim"][at] = float(r[L.METRICS_SSIM])
+        if bad:
+            for at, _, _, _ in reversed(bad):
+                for v in self._lists.values():
+                    del v[at]
+            at, status, pop, n = bad[0]
+            if status == 1:
+                raise ValueError(f"frame {at}: mask_at_box has {pop} pixels set, rgb_map has {n}")
+            raise ValueError("win_size exceeds image extent")
+
+
+def metrics_switch(device_metrics=None):
+    """evaluate_loop's `device_metrics`: None -> the environment's GPNERF_DEVICE_METRICS=1, anything else -> bool(...)"""
+    return os.environ.get("GPNERF_DEVICE_METRICS", "0") == "1" if device_metrics is None else bool(device_metrics)
+
+
+def evaluate_loop(render, eval_loader, cfg, device=None, quiet=False, pipeline=None, device_metrics=None):
     """`Trainer.evaluate` (libs/trainers/BaseTrainer.py:255-280) without its image writing: for every batch of `eval_loader`
     move it to `device` (`_read_inputs`, :89-97), `ret = render.render(batch)` (the reference calls `.module.render` on its
     DataParallel wrapper; a wrapped model is unwrapped here too), `Evaluator.evaluate(ret, batch)`, `total_time += ret["rtime"]`;
@@ -116,10 +235,13 @@ def evaluate_loop(render, eval_loader, cfg, device=None, quiet=False, pipeline=N
     pipeline (not in the reference, whose loop is strictly serial): frame t + 1 is fetched, moved to the device and PREFETCHED
     (Renderer.prefetch: encoder graph, volume builder, frame glue on a second stream) right after frame t's per-ray kernel has been
     enqueued, so the device goes from one frame's per-ray kernel straight into the next frame's producers while the host evaluates
-    frame t.  Default: on when the renderer offers `prefetch` and is neither progressive nor sharded.  Same bits per frame."""
+    frame t.  Default: on when the renderer offers `prefetch` and is neither progressive nor sharded.  Same bits per frame.
+    device_metrics (not in the reference): the frames' metrics by `DeviceEvaluator` -- enqueued behind each frame's per-ray kernel,
+    read once behind the last frame (inside `wall_time`).  Default (None): on with GPNERF_DEVICE_METRICS=1 in the environment,
+    otherwise off."""
     model = getattr(render, "module", render)
     model.eval()
-    evaluator = Evaluator(cfg, cfg.test.test_seq)
+    evaluator = (DeviceEvaluator if metrics_switch(device_metrics) else Evaluator)(cfg, cfg.test.test_seq)
     count, total_time = 0, 0.0
     if pipeline is None:
         pipeline = hasattr(model, "prefetch") and not getattr(model, "progressive", False) and getattr(model, "shard_group", None) is None
@@ -169,8 +291,8 @@ def evaluate_loop(render, eval_loader, cfg, device=None, quiet=False, pipeline=N
                 total_time += ret["rtime"]
                 count += 1
                 val = nxt
-    wall = _time.time() - t_loop
     per_frame = {"mse": list(evaluator.mse), "psnr": list(evaluator.psnr), "ssim": list(evaluator.ssim)}
+    wall = _time.time() - t_loop                              # (behind the lists: the device evaluator's one read belongs to the loop)
     if quiet:                                                 # (summarize() prints its three means, as the reference's does)
         import contextlib
         import io

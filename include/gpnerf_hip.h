@@ -420,6 +420,35 @@ int gpnerf_mesh_count(const float* cube, const int32_t* dims, float iso, void* w
 int gpnerf_mesh_emit(const float* cube, const int32_t* dims, float iso, const void* workspace, size_t workspace_bytes,
                      int64_t max_vertices, int64_t max_triangles, float* vertices, int32_t* faces, void* stream);
 
+/* The evaluator's metrics of one rendered view (gpnerf_metrics.hip; libs/evaluators/if_nerf.py:15-63), written into a slot of
+ * GPNERF_METRICS_DOUBLES doubles on the device: kernel launches only (four), nothing allocated, nothing waited for, no atomics --
+ * the slot is a function of the inputs alone, and the call captures into a HIP graph.
+ *   pred, gt: device float [n][3], the mask's pixels in raster order (the renderer's rgb_map and the batch's rgb);
+ *   mask: device uint8 [H][W], non-zero = pixel present (torch.bool bytes); workspace: gpnerf_metrics_workspace_bytes(H, W)
+ *   bytes on the device, its contents meaningless between calls (one workspace serves one stream's calls in order).
+ * The slot:
+ *   MSE: the mean over all 3n values of ((double)pred - (double)gt)^2 (PSNR = -10 log10 of it is the host's to take);
+ *   SSIM: skimage compare_ssim(multichannel=True)'s defaults on the two images that are zero outside the mask, cropped to the
+ *     mask's bounding rectangle: per channel over the (h-6)(w-6) valid 7x7 windows, uniform means of x, y, xx, yy, xy in double,
+ *     (co)variances x 49/48, c1 = (0.01 * 2)^2, c2 = (0.03 * 2)^2; the mean over windows, then over channels;
+ *   X, Y, W, H: the bounding rectangle of the mask's set pixels (cv2.boundingRect; 0,0,0,0 when empty); POPULATION: their number;
+ *   STATUS: 0 ok; 1 the population is not n (MSE and SSIM NaN, neither list is read through the mask); 2 the mask is empty (both NaN);
+ *     3 the rectangle is narrower or lower than the window (SSIM NaN, MSE valid).
+ * Returns GPNERF_E_ARG (before any device call) for a null pointer, H < 1, W < 1, H * W >= 2^31, n < 0, n > H * W or a workspace
+ * that is too small; gpnerf_metrics_workspace_bytes (host arithmetic only) returns 0 for dims the call refuses. */
+#define GPNERF_METRICS_MSE 0
+#define GPNERF_METRICS_SSIM 1
+#define GPNERF_METRICS_X 2
+#define GPNERF_METRICS_Y 3
+#define GPNERF_METRICS_W 4
+#define GPNERF_METRICS_H 5
+#define GPNERF_METRICS_POPULATION 6
+#define GPNERF_METRICS_STATUS 7
+#define GPNERF_METRICS_DOUBLES 8
+size_t gpnerf_metrics_workspace_bytes(int32_t H, int32_t W);
+int gpnerf_image_metrics(const float* pred, const float* gt, const uint8_t* mask, int32_t H, int32_t W, int64_t n, void* workspace,
+                         size_t workspace_bytes, double* out, void* stream);
+
 /* ---- per-frame sparse convolution pyramid (gpnerf_volume.hip), replacing the external spconv v1.2.1 calls of
  * libs/nerfheads/networks/SparseConvNet.py:22-111 (SubMConv3d / SparseConv3d + BatchNorm1d + ReLU, .dense()).
  * A sparse tensor is: features [M][C] fp32, coords [M][3] int32 (d,h,w), and a dense int32 index grid [D][H][W]
