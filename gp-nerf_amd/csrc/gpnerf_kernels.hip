@@ -897,6 +897,12 @@ DEV unsigned mad24(unsigned a, unsigned b, unsigned c) { return __umul24(a, b) +
 DEV const float* at_byte(const float* base, unsigned byte_off) {
     return reinterpret_cast<const float*>(reinterpret_cast<const char*>(base) + byte_off);
 }
+// A gather's tap offsets, each made a value in a VGPR of its own at this point: what is computed before stays before, and no
+// offset can be rematerialised behind a load.  Followed by a sched_barrier, the loads behind it issue back to back.
+DEV void pin_offsets(unsigned (&a)[4]) { asm volatile("" : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3])); }
+DEV void pin_offsets(unsigned (&a)[4], unsigned (&b)[4]) {
+    asm volatile("" : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3]), "+v"(b[0]), "+v"(b[1]), "+v"(b[2]), "+v"(b[3]));
+}
 
 // 16 channels of one tap: 8 v_pk_fma_f32 (the tap weight is broadcast by op_sel)
 DEV void fma16(const float* __restrict__ p, float w, float* f) {
@@ -1139,7 +1145,11 @@ DEV float view_valid(MP M, int ih, int iw, float px, float py, float pz, bool ne
 
 // Projector.compute for one view (libs/renders/BaseRender.py:301-324,296-299,283-294,352-362):
 // project p, bilinear RGB from imgs[v] (NHWC4) and 16 feature channels from featmaps[v] (NHWC32).
-template <bool BATCH = false, class MP>
+// How the eight taps are fetched.  WALK: one after the other, each reduced as it arrives (the split forms, whose sample loops
+// have no registers for more).  WALK_PINNED: the same with the image's four offsets final before its first load (the fp32 forms'
+// second look at the images for rgb_in_map).  BATCH: all 20 loads in flight before the first is used, one round trip per view.
+enum class Taps { WALK, WALK_PINNED, BATCH };
+template <Taps TAPS = Taps::WALK, class MP>
 DEV ViewSample gather_view(MP M, const float* __restrict__ img, int ih, int iw,
                            const float* __restrict__ fm, int fh, int fw, float px, float py, float pz, bool neg,
                            int half, float* f) {
@@ -1162,18 +1172,24 @@ DEV ViewSample gather_view(MP M, const float* __restrict__ img, int ih, int iw,
     // All eight taps of the view (4 image texels, 4 x 64 B of the feature map) are loaded before the first is used: 20 loads in
     // flight and one round trip per view, where the compiler on its own walks the taps one at a time (BATCH: the folded form,
     // which has no matrix work between its two gather phases to cover them).
-    if constexpr (BATCH) {
+    if constexpr (TAPS == Taps::BATCH) {
         const Axis ix = axis_taps(nx, iw), iy = axis_taps(ny, ih);
         const unsigned ir0 = __umul24(iy.i0, (unsigned)iw * 16u), ir1 = __umul24(iy.i1, (unsigned)iw * 16u);
         const unsigned ix0 = ix.i0 * 16u, ix1 = ix.i1 * 16u;
         const Axis ax = axis_taps(nx, fw), ay = axis_taps(ny, fh);
         const unsigned r0 = __umul24(ay.i0, (unsigned)fw * 128u), r1 = __umul24(ay.i1, (unsigned)fw * 128u);
         const unsigned x0 = ax.i0 * 128u + (unsigned)half * 64u, x1 = ax.i1 * 128u + (unsigned)half * 64u;
-        const f32x4 nw = *reinterpret_cast<const f32x4*>(at_byte(img, ir0 + ix0));
-        const f32x4 ne = *reinterpret_cast<const f32x4*>(at_byte(img, ir0 + ix1));
-        const f32x4 sw = *reinterpret_cast<const f32x4*>(at_byte(img, ir1 + ix0));
-        const f32x4 se = *reinterpret_cast<const f32x4*>(at_byte(img, ir1 + ix1));
-        const unsigned fo[4] = {r0 + x0, r0 + x1, r1 + x0, r1 + x1};
+        // Every tap's byte offset is final, in a register of its own, before the first load issues (pin_offsets): left to the
+        // register allocator, the later taps' address arithmetic lands in registers that the earlier loads are still writing, and
+        // the "one batch" runs as three dependent ones with an s_waitcnt vmcnt between them (tools/isa_gather_waits.py).
+        unsigned io[4] = {ir0 + ix0, ir0 + ix1, ir1 + ix0, ir1 + ix1};
+        unsigned fo[4] = {r0 + x0, r0 + x1, r1 + x0, r1 + x1};
+        pin_offsets(io, fo);
+        __builtin_amdgcn_sched_barrier(0);
+        const f32x4 nw = *reinterpret_cast<const f32x4*>(at_byte(img, io[0]));
+        const f32x4 ne = *reinterpret_cast<const f32x4*>(at_byte(img, io[1]));
+        const f32x4 sw = *reinterpret_cast<const f32x4*>(at_byte(img, io[2]));
+        const f32x4 se = *reinterpret_cast<const f32x4*>(at_byte(img, io[3]));
         const float fwt[4] = {ax.w0 * ay.w0, ax.w1 * ay.w0, ax.w0 * ay.w1, ax.w1 * ay.w1};
         f32x4 q[4][4];
 #pragma unroll
@@ -1204,10 +1220,12 @@ DEV ViewSample gather_view(MP M, const float* __restrict__ img, int ih, int iw,
             const Axis ax = axis_taps(nx, iw), ay = axis_taps(ny, ih);
             const unsigned r0 = __umul24(ay.i0, (unsigned)iw * 16u), r1 = __umul24(ay.i1, (unsigned)iw * 16u);
             const unsigned x0 = ax.i0 * 16u, x1 = ax.i1 * 16u;
-            const f32x4 nw = *reinterpret_cast<const f32x4*>(at_byte(img, r0 + x0));
-            const f32x4 ne = *reinterpret_cast<const f32x4*>(at_byte(img, r0 + x1));
-            const f32x4 sw = *reinterpret_cast<const f32x4*>(at_byte(img, r1 + x0));
-            const f32x4 se = *reinterpret_cast<const f32x4*>(at_byte(img, r1 + x1));
+            unsigned io[4] = {r0 + x0, r0 + x1, r1 + x0, r1 + x1};
+            if constexpr (TAPS == Taps::WALK_PINNED) pin_offsets(io);      // (the four texels in one round trip: see the batched form)
+            const f32x4 nw = *reinterpret_cast<const f32x4*>(at_byte(img, io[0]));
+            const f32x4 ne = *reinterpret_cast<const f32x4*>(at_byte(img, io[1]));
+            const f32x4 sw = *reinterpret_cast<const f32x4*>(at_byte(img, io[2]));
+            const f32x4 se = *reinterpret_cast<const f32x4*>(at_byte(img, io[3]));
             const float wnw = ax.w0 * ay.w0, wne = ax.w1 * ay.w0, wsw = ax.w0 * ay.w1, wse = ax.w1 * ay.w1;
 #pragma unroll
             for (int c = 0; c < 3; ++c) s.rgb[c] = fmaf(se[c], wse, fmaf(sw[c], wsw, fmaf(ne[c], wne, nw[c] * wnw)));
@@ -1291,7 +1309,7 @@ struct KArgs {            // the fused kernel's only argument (see render_fused_
     unsigned* guard;
     // frame-level deferral of the colour branch (Colour::LIST / Colour::UNIFIED: the listing launch + colour_units_kernel +
     // colour_accumulate_kernel): gd_ctrl = a zeroed 256-byte block (GD_COUNT: entries appended so far; GD_QUEUE..+7: the unit queue's
-    // counters), gd_ent[n] = (launch slot, sample | rank << 8, weight bits, 0), gd_rgbw[slot * S + rank] = (r, g, b, weight),
+    // counters), gd_ent[n] = (launch slot, sample | rank << 8, weight bits, the ray's row), gd_rgbw[slot * S + rank] = (r, g, b, weight),
     // gd_cnt[slot] = entries of the ray
     unsigned* gd_ctrl;
     unsigned* gd_flag;        // unified form: gd_flag[u] = 1 once unit u's 32 entries are written (zero at launch)
@@ -1512,7 +1530,7 @@ DEV float gather_views(const __attribute__((address_space(4))) FrameK& fr, float
     float nvalid = 0.f;
 #pragma unroll
     for (int v = 0; v < NV; ++v) {
-        const ViewSample s = gather_view<FORM == FORM_F32_FOLD || FORM == FORM_F32>(fr.proj[v], fr.imgs + (size_t)v * fr.img_h * fr.img_w * 4, fr.img_h, fr.img_w,
+        const ViewSample s = gather_view<(FORM == FORM_F32_FOLD || FORM == FORM_F32) ? Taps::BATCH : Taps::WALK>(fr.proj[v], fr.imgs + (size_t)v * fr.img_h * fr.img_w * 4, fr.img_h, fr.img_w,
                                          fr.featmaps + (size_t)v * fr.feat_h * fr.feat_w * 32, fr.feat_h, fr.feat_w,
                                          px, py, pz, neg, half, x[v]
                                          );
@@ -1654,6 +1672,7 @@ DEV bool render_tile(float* lds, const int lane, const long tile, const int seg,
                 const int nb = min(q_cnt, 32);
                 const uint2 e = dq[(q_head + (n < nb ? n : 0)) & (DEFER_QUEUE - 1)];
                 const int sl = __shfl((int)slot, (int)(e.x & 31u));
+                const int rw = __shfl(ray, (int)(e.x & 31u));      // the ray's row travels with the entry: the unit needs no order[slot] load
                 kargs_ptr kb = (kargs_ptr)__builtin_amdgcn_kernarg_segment_ptr();
                 asm volatile("" : "+s"(kb));
                 if constexpr (unified(COLOUR)) {
@@ -1666,12 +1685,13 @@ DEV bool render_tile(float* lds, const int lane, const long tile, const int seg,
                         agent_store(pe, lane < nb ? (unsigned)sl : 0xffffffffu);
                         agent_store(pe + 1, e.x >> 5);
                         agent_store(pe + 2, e.y);
+                        agent_store(pe + 3, lane < nb ? (unsigned)rw : 0u);
                     }
                     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                     if (lane == 0) agent_store(kb->gd_flag + u, 1u);
                 } else {
                 const unsigned base = wave_add(kb->gd_ctrl + GD_COUNT, (unsigned)nb, lane);
-                if (lane < nb) kb->gd_ent[(size_t)base + lane] = uint4{(unsigned)sl, e.x >> 5, e.y, 0u};
+                if (lane < nb) kb->gd_ent[(size_t)base + lane] = uint4{(unsigned)sl, e.x >> 5, e.y, (unsigned)rw};
                 }
                 q_head = (q_head + nb) & (DEFER_QUEUE - 1);
                 q_cnt -= nb;
@@ -1939,7 +1959,7 @@ DEV bool render_tile(float* lds, const int lane, const long tile, const int seg,
 #pragma unroll
             for (int v = 0; v < NV; ++v) {
                 float dump[16];
-                const ViewSample s2 = gather_view(fr.proj[v], fr.imgs + (size_t)v * fr.img_h * fr.img_w * 4, fr.img_h, fr.img_w,
+                const ViewSample s2 = gather_view<SPLIT ? Taps::WALK : Taps::WALK_PINNED>(fr.proj[v], fr.imgs + (size_t)v * fr.img_h * fr.img_w * 4, fr.img_h, fr.img_w,
                                                   fr.featmaps + (size_t)v * fr.feat_h * fr.feat_w * 32, fr.feat_h, fr.feat_w,
                                                   ax_, ay_, az_, neg, half, dump);
                 irgb[v][0] = s2.rgb[0]; irgb[v][1] = s2.rgb[1]; irgb[v][2] = s2.rgb[2];
@@ -2151,7 +2171,7 @@ DEV void colour_entries(float* lds, const int lane, const bool valid, const uint
     asm volatile("" : "+s"(kb));
     const int half = lane >> 5;
     const int slot = valid ? (int)e.x : 0, kk = (int)(e.y & 255u), rank = (int)(e.y >> 8);
-    const int ray = kb->out.order ? kb->out.order[slot] : slot;
+    const int ray = valid ? (int)e.w : 0;       // the listing wavefront's order[slot] (an invalid lane: row 0)
     const f32x4 r0 = *reinterpret_cast<const f32x4*>(kb->rays + (size_t)ray * 8);
     const f32x4 r1 = *reinterpret_cast<const f32x4*>(kb->rays + (size_t)ray * 8 + 4);
     const int S = kb->S;
@@ -2193,7 +2213,7 @@ DEV bool consume_unit(float* lds, const int lane, long& pending, long& pending_e
     if (wave_load(kb->gd_flag + pending, lane) == 0u) return false;         // (not written yet, or a ticket beyond the list so far)
     const unsigned* const pe = reinterpret_cast<const unsigned*>(kb->gd_ent + (size_t)pending * 32 + (lane & 31));
     uint4 e;
-    e.x = agent_load(pe); e.y = agent_load(pe + 1); e.z = agent_load(pe + 2); e.w = 0u;      // (written through by another CU: read past this one's caches)
+    e.x = agent_load(pe); e.y = agent_load(pe + 1); e.z = agent_load(pe + 2); e.w = agent_load(pe + 3);      // (written through by another CU: read past this one's caches)
     colour_entries<FORM>(lds, lane, e.x != 0xffffffffu, e);
     ++pending;
     return true;
