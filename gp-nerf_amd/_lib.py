@@ -123,6 +123,9 @@ FLAG_NO_EXITS = 128
 FLAG_SHARED_DEVICE = 256
 FLAG_DENSITY_ONLY = 512
 FOLD_FIRST_LEVEL = 2
+# gpnerf_cube_clean's flags and the names of its six stats (include/gpnerf_hip.h)
+CUBE_KEEP, CUBE_FILL = 1, 2
+CUBE_STATS = ("components", "inside_points", "components_kept", "inside_points_kept", "cavities_filled", "points_filled")
 # gpnerf_image_metrics' slot (include/gpnerf_hip.h GPNERF_METRICS_*)
 METRICS_MSE, METRICS_SSIM, METRICS_X, METRICS_Y, METRICS_W, METRICS_H, METRICS_POPULATION, METRICS_STATUS, METRICS_DOUBLES = range(9)
 
@@ -209,6 +212,10 @@ SYMBOLS = {
     "gpnerf_mesh_count": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_float, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "gpnerf_mesh_emit": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_float, C.c_void_p, C.c_size_t, C.c_int64, C.c_int64,
                                    C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gpnerf_cube_clean_workspace_bytes": (C.c_int64, [C.POINTER(C.c_int32)]),
+    "gpnerf_cube_clean": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_float, C.c_uint32, C.c_int64, C.c_void_p, C.c_size_t,
+                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gpnerf_mesh_normals": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_void_p, C.c_int64, FP, C.c_void_p, C.c_void_p]),
     "gpnerf_metrics_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
     "gpnerf_image_metrics": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_size_t,
                                        C.c_void_p, C.c_void_p]),

@@ -10,6 +10,10 @@
 //   2. emit_kernel: per point, its vertices at (its workgroup's offset + its local offset), and per cell its triangles in table
 //      order, each corner the vertex of the crossed edge (looked up the same way at the edge's owner).
 // The case tables below are written out from gp-nerf_amd/mesh.py:case_tables() (tests/test_mesh.py holds them equal).
+//
+// Behind marching cubes, the two calls that finish its input and output (specified in include/gpnerf_hip.h as well): gpnerf_cube_clean
+// (floaters and enclosed cavities, by connected components of the cube's points; integer atomics whose outcome does not depend on
+// their order) and gpnerf_mesh_normals (the cube's gradient at the vertices).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -251,6 +255,327 @@ __global__ void __launch_bounds__(256) mc_emit_kernel(const float* __restrict__ 
     }
 }
 
+// ---- gpnerf_cube_clean: connected components of the cube's points by a block-based union-find ----------------------------------
+// One templated kernel set serves both passes: <9 lower neighbours, inside> labels the solid under 18-connectivity, <3, below> the
+// outside under 6-connectivity.  Per pass:
+//   1. cc_local_kernel: a workgroup labels one brick of 4 x 8 x 32 points (z fastest: a wavefront reads two whole 128-B lines) in
+//      LDS and leaves parent[i] = the lowest point of i's component INSIDE the brick (-1 off the set) and, at those brick roots only,
+//      the component's size in the brick (and whether it touches a boundary face of the cube).  A uniform brick -- most of the padding
+//      and of the exterior -- skips the unions: one root, one count.
+//   2. cc_merge_kernel: unions across brick faces only, on the global parent array.
+//   3. cc_flatten_kernel: every point's parent becomes its set's root; every brick root adds its count to that root's.
+// The cost per point does not grow with the size or the diameter of its component: a find walks brick roots, not points, and the
+// merge compresses the paths it walks.
+// Within a brick the local order (x, y, z lexicographic) is the order of the linear indices, so "lowest local index" is "lowest point".
+constexpr int BX = 4, BY = 8, BZ = 32, BRICK = BX * BY * BZ, CC_THREADS = BY * BZ;     // a thread owns one (y, z) column of BX points
+constexpr unsigned CC_BOUNDARY = 0x80000000u, CC_COUNT = 0x1fffffffu;                   // count word: size (<= 2^28) | boundary bit
+__device__ constexpr int8_t c_lower[9][3] = {      // the neighbours of lower linear index; the first 3 are the 6-connected ones
+    {-1, 0, 0}, {0, -1, 0}, {0, 0, -1}, {-1, -1, 0}, {-1, 1, 0}, {-1, 0, -1}, {-1, 0, 1}, {0, -1, -1}, {0, -1, 1}};
+
+struct Bricks { int nbx, nby, nbz; };
+__host__ __device__ inline Bricks bricks_of(const Grid& g) { return {(g.nx + BX - 1) / BX, (g.ny + BY - 1) / BY, (g.nz + BZ - 1) / BZ}; }
+__device__ __forceinline__ void brick_origin(const Grid& g, int& x0, int& y0, int& z0) {
+    const Bricks b = bricks_of(g);
+    const int id = blockIdx.x;
+    z0 = (id % b.nbz) * BZ;
+    y0 = ((id / b.nbz) % b.nby) * BY;
+    x0 = (id / (b.nbz * b.nby)) * BX;
+}
+template <bool INSIDE> __device__ __forceinline__ bool in_set(float v, float iso) { return INSIDE ? !(v < iso) : (v < iso); }
+
+__device__ __forceinline__ int lds_find(const int* s, int i) {
+    int p = s[i];
+    while (p != i) { i = p; p = s[i]; }
+    return i;
+}
+// LDS atomicMin union: the larger root is linked below the smaller; a lost race retries from what the word held
+__device__ __forceinline__ void lds_union(int* s, int a, int b) {
+    while (true) {
+        a = lds_find(s, a); b = lds_find(s, b);
+        if (a == b) return;
+        if (a < b) { const int t = a; a = b; b = t; }
+        const int old = atomicMin(&s[a], b);
+        if (old == a) return;
+        a = old;
+    }
+}
+
+template <int NLOWER, bool INSIDE>
+__global__ void __launch_bounds__(CC_THREADS) cc_local_kernel(const float* __restrict__ cube, const Grid g, int* __restrict__ parent,
+                                                              unsigned* __restrict__ count, unsigned long long* __restrict__ best,
+                                                              int64_t* __restrict__ stats) {
+    __shared__ int s_par[BRICK];
+    __shared__ unsigned s_cnt[BRICK];
+    if (stats && blockIdx.x == 0 && threadIdx.x < 6) stats[threadIdx.x] = 0;
+    if (best && blockIdx.x == 0 && threadIdx.x == 0) *best = 0ull;
+    int x0, y0, z0;
+    brick_origin(g, x0, y0, z0);
+    const int t = threadIdx.x, lz = t % BZ, ly = t / BZ;
+    const int y = y0 + ly, z = z0 + lz;
+    const bool col = y < g.ny && z < g.nz;
+    bool in[BX], bnd[BX];
+    bool all = true, any = false, anyb = false;
+#pragma unroll
+    for (int lx = 0; lx < BX; ++lx) {
+        const int x = x0 + lx;
+        const bool ok = col && x < g.nx;
+        in[lx] = ok && in_set<INSIDE>(cube[((long)x * g.ny + y) * g.nz + z], g.iso);
+        bnd[lx] = in[lx] && (x == 0 || y == 0 || z == 0 || x == g.nx - 1 || y == g.ny - 1 || z == g.nz - 1);
+        all = all && (in[lx] || !ok);
+        any = any || in[lx];
+        anyb = anyb || bnd[lx];
+    }
+    const int uniform_in = __syncthreads_and(all), some = __syncthreads_or(any);
+    if (uniform_in || !some) {
+        // one node: the brick's first point (always in the cube) is the root of all its in-cube points, or nothing is in the set
+        const int touches = __syncthreads_or(anyb);
+        const int ex = min(BX, g.nx - x0), ey = min(BY, g.ny - y0), ez = min(BZ, g.nz - z0);
+        const long root = ((long)x0 * g.ny + y0) * g.nz + z0;
+#pragma unroll
+        for (int lx = 0; lx < BX; ++lx) {
+            if (!(col && x0 + lx < g.nx)) continue;
+            const long i = ((long)(x0 + lx) * g.ny + y) * g.nz + z;
+            parent[i] = some ? (int)root : -1;
+            count[i] = (some && i == root) ? (unsigned)(ex * ey * ez) | (touches ? CC_BOUNDARY : 0u) : 0u;
+        }
+        return;
+    }
+#pragma unroll
+    for (int lx = 0; lx < BX; ++lx) {
+        const int l = lx * CC_THREADS + t;               // (lx * BY + ly) * BZ + lz
+        s_par[l] = in[lx] ? l : -1;
+        s_cnt[l] = 0u;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int lx = 0; lx < BX; ++lx) {
+        if (!in[lx]) continue;
+        const int l = lx * CC_THREADS + t;
+#pragma unroll
+        for (int k = 0; k < NLOWER; ++k) {
+            const int qx = lx + c_lower[k][0], qy = ly + c_lower[k][1], qz = lz + c_lower[k][2];
+            if (qx < 0 || qy < 0 || qy >= BY || qz < 0 || qz >= BZ) continue;      // another brick's: cc_merge_kernel
+            const int q = (qx * BY + qy) * BZ + qz;
+            if (s_par[q] >= 0) lds_union(s_par, l, q);       // (-1 never changes; a point off the cube is -1)
+        }
+    }
+    __syncthreads();
+    int root[BX];
+#pragma unroll
+    for (int lx = 0; lx < BX; ++lx) root[lx] = in[lx] ? lds_find(s_par, lx * CC_THREADS + t) : -1;
+#pragma unroll
+    for (int lx = 0; lx < BX; ++lx) {
+        if (!in[lx]) continue;
+        atomicAdd(&s_cnt[root[lx]], 1u);
+        if (bnd[lx]) atomicOr(&s_cnt[root[lx]], CC_BOUNDARY);
+    }
+    __syncthreads();
+#pragma unroll
+    for (int lx = 0; lx < BX; ++lx) {
+        if (!(col && x0 + lx < g.nx)) continue;
+        const long i = ((long)(x0 + lx) * g.ny + y) * g.nz + z;
+        int r = -1;
+        if (in[lx]) {
+            const int rl = root[lx], rz = rl % BZ, ry = (rl / BZ) % BY, rx = rl / (BY * BZ);
+            r = (int)(((long)(x0 + rx) * g.ny + y0 + ry) * g.nz + z0 + rz);
+        }
+        parent[i] = r;
+        count[i] = s_cnt[lx * CC_THREADS + t];            // non-zero at the brick's roots only
+    }
+}
+
+// The global parent array inside cc_merge_kernel.  The eight XCDs' L2s are not coherent for plain loads within one kernel, so EVERY
+// access here is an agent-scope atomic: relaxed loads (they bypass the stale levels) and atomicMin.  A parent that is read late is
+// harmless all the same, and that is what the walk relies on between its load and its use: a word only ever decreases, from a
+// member of the set to a lower member of the same set, so an old value is still an ancestor-or-self on a path to the current root.
+__device__ __forceinline__ int g_load(int* p, long i) { return __hip_atomic_load(p + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ int g_find(int* p, int i) {
+    int q = g_load(p, i);
+    while (q != i) { i = q; q = g_load(p, i); }
+    return i;
+}
+// find, then point every word of the walked path at the root found (a lower member of the same set: the invariant above holds)
+__device__ __forceinline__ int g_find_compress(int* p, int i) {
+    const int r = g_find(p, i);
+    int q = g_load(p, i);
+    while (q > r) { atomicMin(&p[i], r); i = q; q = g_load(p, i); }
+    return r;
+}
+__device__ __forceinline__ void g_union(int* p, int a, int b) {
+    while (true) {
+        a = g_find_compress(p, a); b = g_find_compress(p, b);
+        if (a == b) return;
+        if (a < b) { const int t = a; a = b; b = t; }
+        const int old = atomicMin(&p[a], b);      // a was a root when read; if it still is, it now hangs below b
+        if (old == a) return;
+        a = old;                                   // somebody linked a first (to old < a): old and b still have to meet
+    }
+}
+
+template <int NLOWER>
+__global__ void __launch_bounds__(CC_THREADS) cc_merge_kernel(const Grid g, int* parent) {
+    int x0, y0, z0;
+    brick_origin(g, x0, y0, z0);
+    const int t = threadIdx.x, lz = t % BZ, ly = t / BZ, lane = t % 64;
+    const int y = y0 + ly, z = z0 + lz;
+    for (int lx = 0; lx < BX; ++lx) {
+        const int x = x0 + lx;
+        const bool ok = x < g.nx && y < g.ny && z < g.nz;
+        const long i = ((long)x * g.ny + y) * g.nz + z;
+#pragma unroll
+        for (int k = 0; k < NLOWER; ++k) {
+            const int dx = c_lower[k][0], dy = c_lower[k][1], dz = c_lower[k][2];
+            // wave-uniform skip: lx is uniform, and dx alone decides for the offsets that stay inside the brick in y and z
+            const int qx = lx + dx, qy = ly + dy, qz = lz + dz;
+            const bool crosses = qx < 0 || qy < 0 || qy >= BY || qz < 0 || qz >= BZ;
+            const int nx_ = x + dx, ny_ = y + dy, nz_ = z + dz;
+            bool todo = ok && crosses && nx_ >= 0 && ny_ >= 0 && ny_ < g.ny && nz_ >= 0 && nz_ < g.nz;
+            if (!__any(todo)) continue;
+            int pa = -1, pb = -1;
+            if (todo) {
+                pa = g_load(parent, i);
+                if (pa >= 0) pb = g_load(parent, ((long)nx_ * g.ny + ny_) * g.nz + nz_);
+                todo = pa >= 0 && pb >= 0;
+            }
+            // the same pair of brick roots as the lane one or one row before: that lane's union is this one's too.  (An
+            // optimisation only: a pair that differs just because a path was compressed meanwhile is united twice.)
+            const int pa1 = __shfl_up(pa, 1), pb1 = __shfl_up(pb, 1), pa32 = __shfl_up(pa, 32), pb32 = __shfl_up(pb, 32);
+            if (todo && (lane & 31) != 0 && pa1 == pa && pb1 == pb) todo = false;
+            if (todo && lane >= 32 && pa32 == pa && pb32 == pb) todo = false;
+            if (todo) g_union(parent, pa, pb);
+        }
+    }
+}
+
+// A kernel of its own, so the unions are complete and visible (kernel boundary).  Plain accesses: nothing is united here, every set's
+// root is fixed, and a word is only ever replaced by that root -- a reader on another XCD that still sees the old word walks a
+// longer path to the same root.  Each brick root (count != 0) that is not the set's root adds its count to the set's root: integer
+// add / or on disjoint bit fields, so the order does not matter; only roots are added to and only non-roots are read.
+__global__ void __launch_bounds__(256) cc_flatten_kernel(const long n, int* parent, unsigned* count) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    int q = parent[i];
+    if (q < 0 || q == (int)i) return;
+    int r = q;
+    for (int u = parent[r]; u != r; u = parent[r]) r = u;
+    if (r != q) parent[i] = r;
+    const unsigned c = count[i];
+    if (c) {
+        atomicAdd(&count[r], c & CC_COUNT);
+        if (c & CC_BOUNDARY) atomicOr(&count[r], CC_BOUNDARY);
+    }
+}
+
+__device__ __forceinline__ long wave_sum(long v) {
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) v += __shfl_down(v, d);
+    return v;
+}
+
+enum KeepMode { KEEP_ALL = 0, KEEP_MIN = 1, KEEP_LARGEST = 2 };
+// Over the solid's roots: stats[0..1] (components, inside points) and what is kept -- stats[2..3] for KEEP_ALL / KEEP_MIN, the packed
+// (size << 32 | ~label) maximum for KEEP_LARGEST (a total order: ties go to the lower label).  A wavefront sums before its atomics,
+// and a wavefront without a root (nearly all) issues none.
+__global__ void __launch_bounds__(256) cc_select_kernel(const long n, const int* __restrict__ parent, const unsigned* __restrict__ count,
+                                                        const int mode, const long min_points, unsigned long long* __restrict__ best,
+                                                        int64_t* __restrict__ stats) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    const bool root = i < n && parent[i] == (int)i;
+    if (!__any(root)) return;
+    const long size = root ? (long)(count[i] & CC_COUNT) : 0;
+    const bool kept = root && (mode == KEEP_ALL || (mode == KEEP_MIN && size >= min_points));
+    const long roots = wave_sum(root ? 1 : 0), points = wave_sum(size), kroots = wave_sum(kept ? 1 : 0), kpoints = wave_sum(kept ? size : 0);
+    unsigned long long key = root ? ((unsigned long long)size << 32) | (unsigned)~(unsigned)i : 0ull;
+    if (mode == KEEP_LARGEST) {
+#pragma unroll
+        for (int d = 32; d > 0; d >>= 1) { const unsigned long long o = __shfl_down(key, d); key = o > key ? o : key; }
+    }
+    if (threadIdx.x % 64 == 0) {
+        atomicAdd((unsigned long long*)&stats[0], (unsigned long long)roots);
+        atomicAdd((unsigned long long*)&stats[1], (unsigned long long)points);
+        if (kroots) { atomicAdd((unsigned long long*)&stats[2], (unsigned long long)kroots); atomicAdd((unsigned long long*)&stats[3], (unsigned long long)kpoints); }
+        if (mode == KEEP_LARGEST) atomicMax(best, key);
+    }
+}
+
+// out_cube = cube with the inside points of the components that are not kept written as 0; labels, if wanted
+__global__ void __launch_bounds__(256) cc_apply_keep_kernel(const float* __restrict__ cube, const long n, const int* __restrict__ parent,
+                                                            const unsigned* __restrict__ count, const int mode, const long min_points,
+                                                            const unsigned long long* __restrict__ best, float* __restrict__ out,
+                                                            int32_t* __restrict__ labels, int64_t* __restrict__ stats) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const unsigned long long b = mode == KEEP_LARGEST ? *best : 0ull;
+    if (mode == KEEP_LARGEST && i == 0) { stats[2] = b ? 1 : 0; stats[3] = (int64_t)(b >> 32); }
+    const int r = parent[i];
+    float v = cube[i];
+    if (r >= 0) {
+        bool kept = true;
+        if (mode == KEEP_MIN) kept = (long)(count[r] & CC_COUNT) >= min_points;
+        if (mode == KEEP_LARGEST) kept = (unsigned)r == ~(unsigned)b;
+        if (!kept) v = 0.0f;
+    }
+    out[i] = v;
+    if (labels) labels[i] = r;
+}
+
+// every below-iso point of a component that touches no boundary face becomes 1; stats[4..5]
+__global__ void __launch_bounds__(256) cc_apply_fill_kernel(const long n, const int* __restrict__ parent, const unsigned* __restrict__ count,
+                                                            float* __restrict__ out, int64_t* __restrict__ stats) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    const int r = i < n ? parent[i] : -1;
+    const bool fill = r >= 0 && !(count[r] & CC_BOUNDARY);
+    if (!__any(fill)) return;
+    if (fill) out[i] = 1.0f;
+    const long cav = wave_sum(fill && r == (int)i ? 1 : 0), pts = wave_sum(fill ? 1 : 0);
+    if (threadIdx.x % 64 == 0) {
+        if (cav) atomicAdd((unsigned long long*)&stats[4], (unsigned long long)cav);
+        atomicAdd((unsigned long long*)&stats[5], (unsigned long long)pts);
+    }
+}
+
+// ---- gpnerf_mesh_normals: one lane per vertex ---------------------------------------------------------------------------------
+struct Step3 { float v[3]; };
+__device__ __forceinline__ float central(const float* __restrict__ cube, const Grid& g, int x, int y, int z, int a, float inv) {
+    const int dim[3] = {g.nx, g.ny, g.nz};
+    int hi[3] = {x, y, z}, lo[3] = {x, y, z};
+    hi[a] = min(hi[a] + 1, dim[a] - 1);
+    lo[a] = max(lo[a] - 1, 0);
+    const float fh = cube[((long)hi[0] * g.ny + hi[1]) * g.nz + hi[2]], fl = cube[((long)lo[0] * g.ny + lo[1]) * g.nz + lo[2]];
+    return ((fh - fl) * 0.5f) * inv;
+}
+__device__ __forceinline__ float lerp_(float a, float b, float t) { return a + t * (b - a); }
+
+__global__ void __launch_bounds__(256) mesh_normals_kernel(const float* __restrict__ cube, const Grid g, const float* __restrict__ verts,
+                                                           const long n, const Step3 inv, float* __restrict__ normals) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int dim[3] = {g.nx, g.ny, g.nz};
+    int c[3];
+    float t[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        const float v = verts[3 * i + a];
+        float f = floorf(v);
+        f = fminf(fmaxf(f, 0.0f), (float)(dim[a] - 2));          // (NaN -> 0: the index stays in the cube whatever the vertex holds)
+        c[a] = (int)f;
+        t[a] = v - f;
+    }
+    float gr[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        float G[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) G[k] = central(cube, g, c[0] + (k >> 2), c[1] + ((k >> 1) & 1), c[2] + (k & 1), a, inv.v[a]);
+        const float z00 = lerp_(G[0], G[1], t[2]), z01 = lerp_(G[2], G[3], t[2]), z10 = lerp_(G[4], G[5], t[2]), z11 = lerp_(G[6], G[7], t[2]);
+        gr[a] = lerp_(lerp_(z00, z01, t[1]), lerp_(z10, z11, t[1]), t[0]);
+    }
+    const float len = sqrtf((gr[0] * gr[0] + gr[1] * gr[1]) + gr[2] * gr[2]);
+    const bool ok = len > 0.0f && len < __builtin_inff();
+#pragma unroll
+    for (int a = 0; a < 3; ++a) normals[3 * i + a] = ok ? -gr[a] / len : 0.0f;
+}
+
 bool grid_of(const int32_t* dims, float iso, Grid& g) {
     if (!dims || dims[0] < 2 || dims[1] < 2 || dims[2] < 2 || !(iso == iso)) return false;
     const int64_t p = (int64_t)dims[0] * dims[1] * dims[2];
@@ -268,6 +593,16 @@ WsLayout layout_of(const Grid& g) {
     w.bsum = align256(sizeof(int) * 2 * (size_t)g.p);
     w.boff = w.bsum + align256(sizeof(int) * 2 * (size_t)w.nb);
     w.total = w.boff + align256(sizeof(int) * 2 * (size_t)w.nb);
+    return w;
+}
+
+struct CleanLayout { size_t parent, count, best, total; };
+CleanLayout clean_layout_of(const Grid& g) {
+    CleanLayout w;
+    w.parent = 0;
+    w.count = align256(sizeof(int) * (size_t)g.p);
+    w.best = w.count + align256(sizeof(unsigned) * (size_t)g.p);
+    w.total = w.best + 256;
     return w;
 }
 
@@ -311,6 +646,62 @@ int gpnerf_mesh_emit(const float* cube, const int32_t* dims, float iso, const vo
     const int* boff = reinterpret_cast<const int*>(ws + w.boff);
     hipLaunchKernelGGL(mc_emit_kernel, dim3((unsigned)((g.p + 255) / 256)), dim3(256), 0, S_(stream), cube, g, loc, boff,
                        (long)max_vertices, (long)max_triangles, vertices, faces);
+    return launch_status();
+}
+
+int64_t gpnerf_cube_clean_workspace_bytes(const int32_t* dims) {
+    Grid g;
+    if (!grid_of(dims, 0.f, g)) return 0;
+    return (int64_t)clean_layout_of(g).total;
+}
+
+int gpnerf_cube_clean(const float* cube, const int32_t* dims, float iso, uint32_t flags, int64_t min_points, void* workspace,
+                      size_t workspace_bytes, float* out_cube, int32_t* labels, int64_t* stats, void* stream) {
+    Grid g;
+    if (!cube || !workspace || !out_cube || !stats || !grid_of(dims, iso, g)) return GPNERF_E_ARG;
+    if ((flags & ~(GPNERF_CUBE_KEEP | GPNERF_CUBE_FILL)) || min_points < 0) return GPNERF_E_ARG;
+    {   // out_cube must not alias cube (any overlap of the two arrays)
+        const uintptr_t a = (uintptr_t)cube, b = (uintptr_t)out_cube, bytes = sizeof(float) * (uintptr_t)g.p;
+        if (a < b + bytes && b < a + bytes) return GPNERF_E_ARG;
+    }
+    const CleanLayout w = clean_layout_of(g);
+    if (workspace_bytes < w.total) return GPNERF_E_ARG;
+    char* ws = static_cast<char*>(workspace);
+    int* parent = reinterpret_cast<int*>(ws + w.parent);
+    unsigned* count = reinterpret_cast<unsigned*>(ws + w.count);
+    unsigned long long* best = reinterpret_cast<unsigned long long*>(ws + w.best);
+    const Bricks b = bricks_of(g);
+    const dim3 bricks((unsigned)((long)b.nbx * b.nby * b.nbz)), points((unsigned)((g.p + 255) / 256));
+    const int mode = !(flags & GPNERF_CUBE_KEEP) ? KEEP_ALL : min_points > 0 ? KEEP_MIN : KEEP_LARGEST;
+    hipStream_t s = S_(stream);
+    // the solid: 18-connectivity over the inside points of cube
+    hipLaunchKernelGGL((cc_local_kernel<9, true>), bricks, dim3(CC_THREADS), 0, s, cube, g, parent, count, best, stats);
+    hipLaunchKernelGGL((cc_merge_kernel<9>), bricks, dim3(CC_THREADS), 0, s, g, parent);
+    hipLaunchKernelGGL(cc_flatten_kernel, points, dim3(256), 0, s, g.p, parent, count);
+    hipLaunchKernelGGL(cc_select_kernel, points, dim3(256), 0, s, g.p, parent, count, mode, (long)min_points, best, stats);
+    hipLaunchKernelGGL(cc_apply_keep_kernel, points, dim3(256), 0, s, cube, g.p, parent, count, mode, (long)min_points, best, out_cube,
+                       labels, stats);
+    if (flags & GPNERF_CUBE_FILL) {
+        // the outside: 6-connectivity over the below-iso points of out_cube (after the step above)
+        hipLaunchKernelGGL((cc_local_kernel<3, false>), bricks, dim3(CC_THREADS), 0, s, out_cube, g, parent, count,
+                           (unsigned long long*)nullptr, (int64_t*)nullptr);
+        hipLaunchKernelGGL((cc_merge_kernel<3>), bricks, dim3(CC_THREADS), 0, s, g, parent);
+        hipLaunchKernelGGL(cc_flatten_kernel, points, dim3(256), 0, s, g.p, parent, count);
+        hipLaunchKernelGGL(cc_apply_fill_kernel, points, dim3(256), 0, s, g.p, parent, count, out_cube, stats);
+    }
+    return launch_status();
+}
+
+int gpnerf_mesh_normals(const float* cube, const int32_t* dims, const float* vertices, int64_t n_vertices, const float* inv_step,
+                        float* normals, void* stream) {
+    Grid g;
+    if (!cube || !grid_of(dims, 0.f, g) || n_vertices < 0) return GPNERF_E_ARG;
+    if (n_vertices == 0) return GPNERF_OK;
+    if (!vertices || !normals || n_vertices > ((int64_t)1 << 31) * 255) return GPNERF_E_ARG;
+    Step3 inv = {{1.0f, 1.0f, 1.0f}};
+    if (inv_step) for (int a = 0; a < 3; ++a) inv.v[a] = inv_step[a];
+    hipLaunchKernelGGL(mesh_normals_kernel, dim3((unsigned)((n_vertices + 255) / 256)), dim3(256), 0, S_(stream), cube, g, vertices,
+                       (long)n_vertices, inv, normals);
     return launch_status();
 }
 

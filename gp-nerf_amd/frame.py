@@ -802,15 +802,90 @@ def marching_cubes(cube, iso=1.0 / 50.0):
     return verts, faces
 
 
-def extract_mesh(frame, voxel_size, bounds_min, Rh, Th, neg_ray=False, iso=1.0 / 50.0, host=None):
+def _cube_dims(cube, what):
+    _require_gpu(cube, "cube")
+    if cube.dim() != 3 or cube.dtype != torch.float32 or not cube.is_contiguous():
+        raise L.GpnerfError(f"{what}: expected a contiguous float32 [X,Y,Z] cube")
+    return (C.c_int32 * 3)(*cube.shape)
+
+
+def parse_keep(keep):
+    """cube_clean's `keep` -> (flags, min_points): None keeps every component, "largest" the largest one, an integer N >= 1 those of
+    at least N points."""
+    if keep is None:
+        return 0, 0
+    if isinstance(keep, str):
+        if keep != "largest":
+            raise L.GpnerfError(f"cube_clean: keep is None, 'largest' or a number of points, got {keep!r}")
+        return L.CUBE_KEEP, 0
+    if isinstance(keep, bool) or int(keep) != keep or int(keep) < 1:
+        raise L.GpnerfError(f"cube_clean: keep is None, 'largest' or a number of points >= 1, got {keep!r}")
+    return L.CUBE_KEEP, int(keep)
+
+
+def cube_clean(cube, iso=1.0 / 50.0, keep=None, fill_cavities=False, want_labels=False):
+    """gpnerf_cube_clean on a device float32 cube [X,Y,Z]: (out_cube, stats, labels or None), all on the device, nothing read back.
+    keep: None (every solid component stays), "largest", or N (components of at least N points stay); the inside points of the others
+    become 0.  fill_cavities: below-iso regions that reach no face of the cube (6-connectivity), after that step, become 1.  stats:
+    int64 [6], _lib.CUBE_STATS names them; labels: int32 [X,Y,Z], the lowest linear index of each inside point's 18-connected
+    component, -1 elsewhere.  The workspace (8 bytes per point) comes from torch's caching allocator and goes back when the call
+    returns."""
+    lib = L.lib()
+    dims = _cube_dims(cube, "cube_clean")
+    flags, min_points = parse_keep(keep)
+    flags |= L.CUBE_FILL if fill_cavities else 0
+    nbytes = int(lib.gpnerf_cube_clean_workspace_bytes(dims))
+    if nbytes <= 0:
+        raise L.GpnerfError(f"cube_clean: dims {tuple(cube.shape)} refused (each >= 2, at most 2^28 points)")
+    dev = cube.device
+    ws = torch.empty((nbytes,), device=dev, dtype=torch.uint8)
+    out = torch.empty_like(cube)
+    stats = torch.empty((6,), device=dev, dtype=torch.int64)
+    labels = torch.empty(tuple(cube.shape), device=dev, dtype=torch.int32) if want_labels else None
+    L.check(lib.gpnerf_cube_clean(cube.data_ptr(), dims, float(iso), flags, min_points, ws.data_ptr(), ws.numel(), out.data_ptr(),
+                                  labels.data_ptr() if labels is not None else None, stats.data_ptr(), _stream_ptr(dev)), "gpnerf_cube_clean")
+    return out, stats, labels
+
+
+def mesh_normals(cube, vertices, step=None):
+    """gpnerf_mesh_normals: unit normals (device float32 [n,3]) at `vertices` (device float32 [n,3], index units of `cube`, e.g.
+    marching_cubes' as they come) from the cube's central differences, pointing toward lower values.  step: the lattice's voxel size
+    per axis (1 / step scales the differences, so that an anisotropic lattice gives geometric normals), or None for 1, 1, 1."""
+    lib = L.lib()
+    dims = _cube_dims(cube, "mesh_normals")
+    _require_gpu(vertices, "vertices")
+    if vertices.dtype != torch.float32 or not vertices.is_contiguous() or vertices.dim() != 2 or vertices.shape[1] != 3:
+        raise L.GpnerfError(f"mesh_normals: expected contiguous float32 vertices [n,3], got {vertices.dtype} {tuple(vertices.shape)}")
+    n = vertices.shape[0]
+    normals = torch.empty((n, 3), device=cube.device, dtype=torch.float32)
+    inv = None
+    if step is not None:
+        inv = (C.c_float * 3)(*[float(np.float32(1.0) / np.float32(v)) for v in np.asarray(step, dtype=np.float64).ravel()[:3]])
+    L.check(lib.gpnerf_mesh_normals(cube.data_ptr(), dims, vertices.data_ptr() if n else None, n, inv,
+                                    normals.data_ptr() if n else None, _stream_ptr(cube.device)), "gpnerf_mesh_normals")
+    return normals
+
+
+def extract_mesh(frame, voxel_size, bounds_min, Rh, Th, neg_ray=False, iso=1.0 / 50.0, host=None, clean=None, fill_cavities=None,
+                 normals=False):
     """The geometry mode of demo_render.py's render_rays (:166-175, 249-311, 366-376) on the device: the box of the occupied voxels,
     the lattice, the alpha cube and its marching-cubes mesh.  Two host reads: the box (6 values) and the mesh counts (2).
     Returns {"cube" (device [X+20,Y+20,Z+20]), "vertices", "faces" (device), "axes", "can_bounds", "n_kept" (device int64),
-    "lattice" (lattice_of(axes): query_points at the vertices as they come)}."""
+    "lattice" (lattice_of(axes): query_points at the vertices as they come)}.
+    clean (cube_clean's `keep`: "largest" or N) and fill_cavities (None: filled whenever clean is given): marching cubes then runs on
+    the cleaned cube -- "cube" stays the untouched one -- and "clean_stats" (device int64 [6]) is added; normals: "normals" (device
+    [nv,3], mesh_normals of the cube the mesh was made from, scaled by 1 / voxel size) is added.  With all three off no further launch
+    is enqueued."""
     box = mesh_box(frame, voxel_size, bounds_min, Rh, Th, host=host)
     vs = host[0] if host is not None else voxel_size
     axes = lattice_axes(box, vs)
     cube, n_kept = density_lattice(frame, axes, neg_ray=neg_ray)
-    verts, faces = marching_cubes(cube, iso)
-    return {"cube": cube, "vertices": verts, "faces": faces, "axes": axes, "can_bounds": box, "n_kept": n_kept,
-            "lattice": lattice_of(axes, vs)}
+    res = {"cube": cube, "axes": axes, "can_bounds": box, "n_kept": n_kept, "lattice": lattice_of(axes, vs)}
+    fill = (clean is not None) if fill_cavities is None else bool(fill_cavities)
+    surface = cube
+    if clean is not None or fill:
+        surface, res["clean_stats"], _ = cube_clean(cube, iso, keep=clean, fill_cavities=fill)
+    res["vertices"], res["faces"] = marching_cubes(surface, iso)
+    if normals:
+        res["normals"] = mesh_normals(surface, res["vertices"], step=np.asarray(vs, dtype=np.float64).ravel()[:3])
+    return res

@@ -88,10 +88,10 @@ def case_tables():
 
 
 class Mesh:
-    """vertices float64 [nv,3], faces int64 [nf,3] (trimesh's names), vertex_colors float32 [nv,3] in [0, 1] or None; export() writes a
-    binary little-endian PLY."""
+    """vertices float64 [nv,3], faces int64 [nf,3] (trimesh's names), vertex_colors float32 [nv,3] in [0, 1] or None, vertex_normals
+    float32 [nv,3] or None; export() writes a binary little-endian PLY."""
 
-    def __init__(self, vertices, faces, vertex_colors=None):
+    def __init__(self, vertices, faces, vertex_colors=None, vertex_normals=None):
         self.vertices = np.ascontiguousarray(vertices, dtype=np.float64).reshape(-1, 3)
         self.faces = np.ascontiguousarray(faces, dtype=np.int64).reshape(-1, 3)
         self.vertex_colors = None
@@ -99,31 +99,45 @@ class Mesh:
             self.vertex_colors = np.ascontiguousarray(vertex_colors, dtype=np.float32).reshape(-1, 3)
             if len(self.vertex_colors) != len(self.vertices):
                 raise ValueError(f"{len(self.vertex_colors)} vertex colours for {len(self.vertices)} vertices")
+        self.vertex_normals = None
+        if vertex_normals is not None:
+            self.vertex_normals = np.ascontiguousarray(vertex_normals, dtype=np.float32).reshape(-1, 3)
+            if len(self.vertex_normals) != len(self.vertices):
+                raise ValueError(f"{len(self.vertex_normals)} vertex normals for {len(self.vertices)} vertices")
 
     def __repr__(self):
         c = "" if self.vertex_colors is None else ", coloured"
-        return f"Mesh(vertices={len(self.vertices)}, faces={len(self.faces)}{c})"
+        n = "" if self.vertex_normals is None else ", normals"
+        return f"Mesh(vertices={len(self.vertices)}, faces={len(self.faces)}{c}{n})"
 
     def export(self, file_obj, file_type="ply"):
-        """Binary little-endian PLY: float64 x y z per vertex (the array as it is) -- followed, when the mesh has vertex colours, by
-        uchar red green blue = clip(rint(255 c), 0, 255) -- and one uint8-counted int32 index list per face."""
+        """Binary little-endian PLY: float64 x y z per vertex (the array as it is) -- followed, when the mesh has vertex normals, by
+        float32 nx ny nz and, when it has vertex colours, by uchar red green blue = clip(rint(255 c), 0, 255) -- and one
+        uint8-counted int32 index list per face."""
         if file_type != "ply":
             raise ValueError("only PLY is written (trimesh is not a dependency)")
         if len(self.faces) and (self.faces.min() < 0 or self.faces.max() >= len(self.vertices) or len(self.vertices) >= 2 ** 31):
             raise ValueError("face indices out of range for a PLY int32 list")
+        normal = ("property float nx\nproperty float ny\nproperty float nz\n" if self.vertex_normals is not None else "")
         colour = ("property uchar red\nproperty uchar green\nproperty uchar blue\n" if self.vertex_colors is not None else "")
         head = ("ply\nformat binary_little_endian 1.0\n"
-                f"element vertex {len(self.vertices)}\nproperty double x\nproperty double y\nproperty double z\n{colour}"
+                f"element vertex {len(self.vertices)}\nproperty double x\nproperty double y\nproperty double z\n{normal}{colour}"
                 f"element face {len(self.faces)}\nproperty list uchar int vertex_indices\nend_header\n").encode("ascii")
         faces = np.empty(len(self.faces), dtype=[("n", "u1"), ("i", "<i4", (3,))])
         faces["n"] = 3
         faces["i"] = self.faces
-        if self.vertex_colors is None:
+        if self.vertex_colors is None and self.vertex_normals is None:
             verts = self.vertices.astype("<f8").tobytes()
         else:
-            v = np.empty(len(self.vertices), dtype=[("xyz", "<f8", (3,)), ("rgb", "u1", (3,))])
+            fields = [("xyz", "<f8", (3,))]
+            fields += [("n", "<f4", (3,))] if self.vertex_normals is not None else []
+            fields += [("rgb", "u1", (3,))] if self.vertex_colors is not None else []
+            v = np.empty(len(self.vertices), dtype=fields)             # (packed: no padding between the fields)
             v["xyz"] = self.vertices
-            v["rgb"] = colour_bytes(self.vertex_colors)
+            if self.vertex_normals is not None:
+                v["n"] = self.vertex_normals
+            if self.vertex_colors is not None:
+                v["rgb"] = colour_bytes(self.vertex_colors)
             verts = v.tobytes()
         body = verts + faces.tobytes()
         if hasattr(file_obj, "write"):

@@ -32,11 +32,30 @@ from . import mesh as M_
 from . import parallel as P_
 
 
+def parse_mesh_clean(value):
+    """Renderer(mesh_clean=...) / GPNERF_MESH_CLEAN -> None (off), "largest", or an int N >= 1: off is None, False, 0, "0" or "";
+    anything else is refused."""
+    if value is None or value is False:
+        return None
+    if isinstance(value, str):
+        text = value.strip()
+        if text in ("", "0"):
+            return None
+        if text == "largest":
+            return "largest"
+        if not text.isdigit():
+            raise L.GpnerfError(f"mesh_clean / GPNERF_MESH_CLEAN: expected 0, 'largest' or a number of points, got {value!r}")
+        return int(text)
+    if isinstance(value, bool) or int(value) != value or int(value) < 0:
+        raise L.GpnerfError(f"mesh_clean: expected None, 'largest' or a number of points, got {value!r}")
+    return int(value) or None
+
+
 class Renderer(nn.Module):
     def __init__(self, encoder, nerfhead, is_train=False, neg_ray_train=False, neg_ray_val=False, n_rays=1024,
                  n_samples=64, voxel_size=(0.005, 0.005, 0.005), chunk=64, mesh_th=-1, early_term=None, term_eps=1e-5,
                  progressive=False, split_f16=None, sharded_outputs="all", shard_group=None, encoder_graph=None, fold_levels=None, reserve_cus=None,
-                 mesh_colors=None):
+                 mesh_colors=None, mesh_clean=None, mesh_normals=None):
         super().__init__()
         self.encoder = encoder
         self.nerfhead = nerfhead
@@ -92,6 +111,13 @@ class Renderer(nn.Module):
         # field's rgb there (gpnerf_query_points; GP-NeRF's colour does not depend on a viewing direction).  Off by default;
         # GPNERF_MESH_COLORS=1 turns it on from outside, e.g. for the reference's tools/inference.py run.
         self.mesh_colors = (os.environ.get("GPNERF_MESH_COLORS", "0") == "1") if mesh_colors is None else bool(mesh_colors)
+        # mesh_clean (not in the reference, which returns the raw marching-cubes surface: 54-70 separate surfaces on a body cube):
+        # render_mesh cleans the alpha cube on the device before marching cubes (gpnerf_cube_clean) -- "largest" keeps the largest
+        # solid component, an integer N those of at least N points -- and fills the enclosed cavities whenever it cleans.
+        # GPNERF_MESH_CLEAN = unset / 0 (off), largest, or N sets it from outside.  mesh_normals (GPNERF_MESH_NORMALS=1): the mesh
+        # carries vertex_normals, the cube's gradient at the vertices (gpnerf_mesh_normals).  Both off by default.
+        self.mesh_clean = parse_mesh_clean(os.environ.get("GPNERF_MESH_CLEAN", "0") if mesh_clean is None else mesh_clean)
+        self.mesh_normals = (os.environ.get("GPNERF_MESH_NORMALS", "0") == "1") if mesh_normals is None else bool(mesh_normals)
 
     # ---- helpers the reference exposes as methods (stage entry points) ----------------------------
     def _neg_ray(self, batch):
@@ -280,7 +306,13 @@ class Renderer(nn.Module):
         float32 numpy), `time_slots`, `etime`, `rtime`.  The iso value is the reference's literal 1 / 50 (cfg.test.mesh_th is not
         read there either).  Host reads: the frame's constants before the encoder, the box (6 values), the mesh counts (2).
         With mesh_colors, the mesh carries vertex_colors: the field's rgb at every vertex (query_points on the device, the vertices
-        as they come in index units of the padded cube), copied to the host with the vertices."""
+        as they come in index units of the padded cube), copied to the host with the vertices.
+        With mesh_clean, the mesh is that of the cleaned cube (kept solid components, cavities filled; colours are queried at ITS
+        vertices), `cube` stays the untouched alpha cube, and `mesh_stats` holds gpnerf_cube_clean's six counts as a dict (_lib.CUBE_STATS)
+        -- at most one more small host read per call (48 bytes).  With mesh_normals, the mesh carries vertex_normals: unit normals
+        from the gradient of the cube the mesh was made from, scaled by 1 / voxel_size per axis (geometric normals on an anisotropic
+        lattice), in the vertices' frame (the cube's index axes).  With both off, extract_mesh enqueues exactly the launches it
+        did before there were these options."""
         dev = batch["src_imgs"].device
         torch.cuda.synchronize(dev)
         te = time.time()
@@ -297,17 +329,19 @@ class Renderer(nn.Module):
         frame.build_occupancy()
         ev[2].record()
         m = F_.extract_mesh(frame, self.voxel_size, batch["bounds"][0, 0], batch["Rh"][0], batch["Th"][0], neg_ray=self._neg_ray(batch),
-                            iso=M_.ISO_REFERENCE, host=box_host)
+                            iso=M_.ISO_REFERENCE, host=box_host, clean=self.mesh_clean, normals=self.mesh_normals)
         colours = None
         if self.mesh_colors:
             colours = F_.query_points(frame, m["vertices"], neg_ray=self._neg_ray(batch), want=("rgb",), lattice=m["lattice"])["rgb"]
         ev[3].record()
         cube = m["cube"].cpu().numpy()
-        mesh = M_.Mesh(m["vertices"].cpu().numpy(), m["faces"].cpu().numpy(), colours.cpu().numpy() if colours is not None else None)
+        mesh = M_.Mesh(m["vertices"].cpu().numpy(), m["faces"].cpu().numpy(), colours.cpu().numpy() if colours is not None else None,
+                       m["normals"].cpu().numpy() if "normals" in m else None)
+        stats = dict(zip(L.CUBE_STATS, m["clean_stats"].cpu().tolist())) if "clean_stats" in m else None
         t4 = time.time()
         etime = ev[0].elapsed_time(ev[1]) * 1e-3
         t_frame, t_mesh = ev[1].elapsed_time(ev[2]) * 1e-3, ev[2].elapsed_time(ev[3]) * 1e-3
-        return {"mesh": mesh, "cube": cube,
+        return {"mesh": mesh, "cube": cube, **({"mesh_stats": stats} if stats is not None else {}),
                 "time_slots": {"frame": t_frame, "mesh": t_mesh, "bc_time": 0.0, "sigma_c": 0.0, "bc_attn": 0.0, "sigma_attn": 0.0,
                                "sp_encode": t_frame, "bf_sigma": 0.0, "sigma_f": t_mesh},
                 "etime": etime, "rtime": max(0.0, (t4 - te) - etime)}

@@ -420,6 +420,54 @@ int gpnerf_mesh_count(const float* cube, const int32_t* dims, float iso, void* w
 int gpnerf_mesh_emit(const float* cube, const int32_t* dims, float iso, const void* workspace, size_t workspace_bytes,
                      int64_t max_vertices, int64_t max_triangles, float* vertices, int32_t* faces, void* stream);
 
+/* Finishing the cube before / the mesh after marching cubes (gpnerf_mesh.hip): floaters, enclosed cavities, vertex normals.  Both
+ * entry points: kernel launches only, on the caller's stream; nothing allocated, nothing waited for; a fixed number of launches sized
+ * from dims alone (no sweep-until-stable loop, no host read); the call captures into a HIP graph; the result is a function of the
+ * inputs alone.  dims as for gpnerf_mesh_count (each >= 2, product <= 2^28, x slowest).
+ *
+ * gpnerf_cube_clean(cube, dims, iso, flags, min_points, workspace, workspace_bytes, out_cube, labels, stats, stream):
+ *   - a point is INSIDE iff !(value < iso): the exact negation of marching cubes' corner bit, so the two never disagree (NaN is inside);
+ *   - SOLID COMPONENTS are the inside points under 18-connectivity (6 face + 12 face-diagonal neighbours): the case tables cut every
+ *     face on its own and separate the two below-iso corners of an ambiguous face, so the solid is joined across a face diagonal and
+ *     not across a body diagonal, and the outside is 6-connected;
+ *     labels (device int32 [X][Y][Z], or NULL): for every inside point the linear index of the lowest point of its component, -1 elsewhere;
+ *   - GPNERF_CUBE_KEEP: with min_points > 0 every component of at least min_points points is kept; with min_points == 0 only the
+ *     largest, a tie going to the component with the lower label; every inside point of a component that is not kept is written as
+ *     0.0f.  Without the flag every component is kept (min_points is then ignored; min_points < 0 is refused);
+ *   - GPNERF_CUBE_FILL, applied to the cube AFTER the step above (a bubble inside a removed floater has opened and is not filled): the
+ *     below-iso points are grouped under 6-connectivity; a component that reaches none of the cube's six boundary faces is a cavity,
+ *     and every point of a cavity is written as 1.0f;
+ *   - every other element of out_cube is cube's, bit for bit; every element is written.  out_cube must not alias cube (refused);
+ *   - stats: device int64[6] = {solid components, inside points, components kept, inside points kept, cavities filled, points filled};
+ *   - a cube with no inside point is not an error (out_cube = cube, the stats are zeros); other flag bits are refused;
+ *   - workspace: gpnerf_cube_clean_workspace_bytes(dims) bytes on the device (8 per point: a parent word and a count word, the same
+ *     two arrays serve both passes; plus one 256-byte line for the selection), contents meaningless between calls.
+ *   Zeroing whole solid components and raising whole cavities never touches a value on an edge that still crosses, so every triangle of
+ *   the cleaned cube's mesh is a triangle of the unfiltered mesh, positions bit for bit.
+ *   Atomics, and why the outcome does not depend on their arrival order (all integer, none float):
+ *     - the union-find's parent words only ever decrease (atomicMin of a smaller index of the SAME set), a set's root is the one word
+ *       that points at itself, and a union links the larger of two roots below the smaller: whatever the order, the root of a set ends
+ *       as its lowest index, which is what the flattening pass (a kernel of its own) writes everywhere;
+ *     - sizes, the boundary-face bit and the six stats are integer adds / ors: commutative and associative, no overflow (<= 2^28 points);
+ *     - "largest" is one 64-bit atomicMax over (size << 32 | ~label): a total order, so the maximum is the same in any order.
+ *
+ * gpnerf_mesh_normals(cube, dims, vertices, n_vertices, inv_step, normals, stream): unit normals (device float [n][3]) at any points
+ * inside the cube, in index units (device float [n][3]; marching-cubes vertices as they come), from the cube's central differences:
+ *   - G(p)[a] = (f(p + e_a) - f(p - e_a)) * 0.5 * inv_step[a] at a lattice point p, the two indices clamped to the cube;
+ *     inv_step: host float[3] or NULL = 1, 1, 1 (1 / voxel size gives geometric normals on an anisotropic lattice);
+ *   - for a vertex v, per axis: i = clamp(floor(v), 0, dim - 2), t = v - i; g = the trilinear interpolation of G over the cell's eight
+ *     corners, lerp along z, then y, then x, each lerp as a + t * (b - a) -- for a marching-cubes vertex the lerp between the two ends
+ *     of its edge;
+ *   - n = -g / |g|, |g| = sqrt((gx gx + gy gy) + gz gz): toward lower values, the side the triangles' winding faces; n = (0, 0, 0)
+ *     exactly when |g| is 0 or not finite; all arithmetic in float32, unfused; n_vertices == 0 is a no-op. */
+#define GPNERF_CUBE_KEEP 1u
+#define GPNERF_CUBE_FILL 2u
+int64_t gpnerf_cube_clean_workspace_bytes(const int32_t* dims);
+int gpnerf_cube_clean(const float* cube, const int32_t* dims, float iso, uint32_t flags, int64_t min_points, void* workspace,
+                      size_t workspace_bytes, float* out_cube, int32_t* labels, int64_t* stats, void* stream);
+int gpnerf_mesh_normals(const float* cube, const int32_t* dims, const float* vertices, int64_t n_vertices, const float* inv_step,
+                        float* normals, void* stream);
+
 /* The evaluator's metrics of one rendered view (gpnerf_metrics.hip; libs/evaluators/if_nerf.py:15-63), written into a slot of
  * GPNERF_METRICS_DOUBLES doubles on the device: kernel launches only (four), nothing allocated, nothing waited for, no atomics --
  * the slot is a function of the inputs alone, and the call captures into a HIP graph.
