@@ -437,13 +437,17 @@ __global__ void copy_rows_kernel(const float* __restrict__ src, float* __restric
     if (i < n) dst[i] = src[i];
 }
 
-// strided conv, step 1: mark every coarse site reached by an active fine site (out = (p + 1 - k) / 2 when even)
+// strided conv, step 1: mark every coarse site reached by an active fine site (out = (p + 1 - k) / 2 when even).  A row outside
+// the fine grid marks nothing, as index_kernel ignores it: beyond the far faces every tap fails `o < out_dims`; a NEGATIVE coordinate
+// is refused here, because p = -1 gives num = 0 at tap 0 -- coarse site 0 of that axis, a site with no indexed input that would
+// hold max(bn_shift, 0) in the dense level.
 __global__ void mark_kernel(const int32_t* __restrict__ coords, const int* __restrict__ m_ptr, const int m_cap, const Dims out_dims,
                             int32_t* __restrict__ out_grid) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     const int m = m_ptr ? min(*m_ptr, m_cap) : m_cap;
     if (i >= m) return;
     const int p[3] = {coords[3 * i], coords[3 * i + 1], coords[3 * i + 2]};
+    if (p[0] < 0 || p[1] < 0 || p[2] < 0) return;
     for (int k = 0; k < KV; ++k) {
         const int kk[3] = {k / 9, (k / 3) % 3, k % 3};
         int o[3];

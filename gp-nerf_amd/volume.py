@@ -262,8 +262,10 @@ class SparseConvNet(nn.Module):
         for i in range(self.n_layers):
             sc, dc = self.net[2 * i + 1], self.net[2 * i + 2]
             mods += [(True, sc[0], sc[1]), (False, dc[0], dc[1]), (False, dc[3], dc[4])]
-        key = (str(dev),) + tuple((m.weight.data_ptr(), m.weight._version, bn.weight._version, bn.bias._version, bn.running_mean._version,
-                                   bn.running_var._version, bn.running_mean.data_ptr()) for _, m, bn in mods)
+        # pointer AND version of every tensor the table is made from (as _folded_bn's own key): a tensor re-bound to a fresh one
+        # (`bn.running_var = torch.full_like(...)`) comes with the version its predecessor may have had, only the pointer tells them apart
+        key = (str(dev),) + tuple((t.data_ptr(), t._version) for _, m, bn in mods
+                                  for t in (m.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var))
         hit = self.__dict__.get("_conv_table_cache")
         hit = hit.v if hit is not None else None
         if hit is not None and hit[0] == key:

@@ -11,7 +11,9 @@ reference), so one set of weights drives both sides.
 * `dense_levels(net, code, coord, out_sh)` -- libs/nerfheads/networks/SparseConvNet.py:22-111 on the published algorithm of
   spconv v1.2.1 (SubMConv3d / SparseConv3d by coordinate rulebook, `.dense()`).  spconv is absent from the reference tree and
   not installable here: **parity unpinned**; tests/test_volume_builder.py checks this restatement against the dense
-  conv3d-with-mask definition it must agree with.
+  conv3d-with-mask definition it must agree with.  Since the volume builder's stage tests the pieces are used one by one as well
+  (tests/volume_cases.py, tests/test_gpu_volume_stages.py): `sparse_conv3d(..., 2, 1).coords` for gpnerf_sparse_down_sites,
+  `subm_conv3d_rulebook` for a convolution through the merged grid, `dense_levels` in float64 for one-level nets on crowded voxels.
 
 spconv v1.2.1 semantics this restatement (and csrc/gpnerf_volume.hip behind it) assumes -- the reference pins the version in
 README.md:27-33 (`git checkout abf0acf30f5526ea93e687e3f424f62d9cd8313a`).  The library is NOT in this image and there is no

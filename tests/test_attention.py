@@ -85,3 +85,37 @@ def test_matrix_core_attention_for_every_head_size_and_view_count(n_head, views,
                                         n, d, d, n_head, views, out.data_ptr(), None), "gpnerf_vertex_attention")
     torch.cuda.synchronize()
     assert float((out.cpu() - ref).abs().max()) < 2e-5 * max(1.0, float(ref.abs().max()))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("d_model,kv_dim,n_head,views,n", [(64, 64, 4, 3, 50), (64, 32, 8, 4, 33), (16, 64, 4, 2, 70), (48, 40, 3, 3, 37),
+                                                           (32, 32, 16, 3, 65), (32, 32, 32, 1, 10), (8, 32, 2, 4, 5), (32, 16, 4, 3, 2500),
+                                                           (64, 64, 1, 4, 2049)])
+def test_shuffle_form_attention_at_every_shape_class(d_model, kv_dim, n_head, views, n):
+    """gpnerf_vertex_attention off the matrix-core form (vertex_attention_kernel): the 64-wide instantiation (d_model or kv_dim above
+    32), heads of 1 and 2 channels at 32 / 32, a d_model that is no power of two (3 heads of 16), and from 2 048 vertices on the
+    512-workgroup grid-stride launch -- against the same float64 formula and bound as the matrix-core test.  `out` starts as NaN with
+    one guard row past n, which has to survive."""
+    L = importlib.import_module("gp-nerf_amd._lib")
+    lib = L.lib()
+    assert not (d_model == 32 and kv_dim == 32 and d_model // n_head >= 4), "this shape takes the matrix-core form"
+    g = torch.Generator().manual_seed(d_model * 1000 + kv_dim * 10 + n_head + views)
+    q = torch.randn((n, d_model), generator=g)
+    kv = torch.randn((n, views, kv_dim), generator=g)
+    w = [torch.randn((d_model, c), generator=g) * 0.25 for c in (d_model, kv_dim, kv_dim, d_model)]
+    qd, kd = q.double(), kv.double()
+    d_k = d_model // n_head
+    qh = (qd @ w[0].double().T).view(n, n_head, d_k) / d_k ** 0.5
+    kh = (kd @ w[1].double().T).view(n, views, n_head, d_k)
+    vh = (kd @ w[2].double().T).view(n, views, n_head, d_k)
+    att = torch.softmax(torch.einsum("nhd,nvhd->nhv", qh, kh), dim=-1)
+    ref = (torch.einsum("nhv,nvhd->nhd", att, vh).reshape(n, d_model) @ w[3].double().T).float()
+    dev = "cuda:0"
+    qg, kg, wg = q.to(dev), kv.to(dev), [t.to(dev).contiguous() for t in w]
+    out = torch.full((n + 1, d_model), float("nan"), device=dev)
+    L.check(lib.gpnerf_vertex_attention(qg.data_ptr(), kg.data_ptr(), wg[0].data_ptr(), wg[1].data_ptr(), wg[2].data_ptr(), wg[3].data_ptr(),
+                                        n, d_model, kv_dim, n_head, views, out.data_ptr(), None), "gpnerf_vertex_attention")
+    torch.cuda.synchronize()
+    out = out.cpu()
+    assert torch.isnan(out[n]).all(), "the row past n was written"
+    assert float((out[:n] - ref).abs().max()) < 2e-5 * max(1.0, float(ref.abs().max()))
