@@ -206,6 +206,10 @@ SYMBOLS = {
     "gpnerf_patch_order": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gpnerf_density_lattice": (C.c_int, [C.POINTER(GpnerfFrame), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_int32,
                                          C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gpnerf_visual_hull": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_int32, C.c_void_p, C.c_int32, C.c_int32,
+                                     C.POINTER(C.c_double), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gpnerf_density_lattice_masked": (C.c_int, [C.POINTER(GpnerfFrame), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_int32,
+                                                C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gpnerf_query_points": (C.c_int, [C.POINTER(GpnerfFrame), C.c_void_p, C.c_int64, C.c_uint32, C.POINTER(C.c_double), C.c_void_p,
                                       C.c_void_p, C.c_void_p]),
     "gpnerf_mesh_workspace_bytes": (C.c_int64, [C.POINTER(C.c_int32)]),

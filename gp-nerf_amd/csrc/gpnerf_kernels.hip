@@ -2668,9 +2668,15 @@ struct LatticeArgs {          // the kernel's only argument, read through the ke
     int bricks_y, bricks_z;   // of the padded cube
     float* cube;              // [n0 + 2 pad][n1 + 2 pad][n2 + 2 pad]
     unsigned long long* n_kept;
+    const uint8_t* inside;    // MASKED: [n0][n1][n2], the caller's kept set (a visual hull); nullptr otherwise
 };
 typedef const __attribute__((address_space(4))) LatticeArgs* lattice_ptr;
 
+// MASKED false: the demo's lattice -- a point is kept where the occupancy volume interpolates to > 0 at the demo's grid coordinates
+// (the launcher sets the literal voxel size).  MASKED true: the dense renderer's (BaseRender.py:255-272) -- a point is kept iff the
+// caller's mask is non-zero there (batch['inside'], .bool()), grid coordinates with the frame's voxel size, no occupancy volume; a
+// kept point's alpha is field_points_kernel<false>'s at the same world point, bit for bit.
+template <bool MASKED>
 __global__ void __launch_bounds__(LAT_WAVES * 64, LAT_WAVES / 4) density_lattice_kernel(const LatticeArgs) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     lattice_ptr ka = (lattice_ptr)__builtin_amdgcn_kernarg_segment_ptr();
@@ -2696,7 +2702,13 @@ __global__ void __launch_bounds__(LAT_WAVES * 64, LAT_WAVES / 4) density_lattice
         const bool inside = in_cube && (unsigned)i < (unsigned)n0 && (unsigned)j < (unsigned)n1 && (unsigned)k < (unsigned)n2;
         float px = 0.f, py = 0.f, pz = 0.f, gx = 0.f, gy = 0.f, gz = 0.f;
         bool keep = false;
-        if (inside) {
+        if constexpr (MASKED) {
+            if (inside && kt->inside[((long)i * n1 + j) * n2 + k] != 0) {  // pts[inside], BaseRender.py:262
+                keep = true;
+                px = kt->axis[0][i]; py = kt->axis[1][j]; pz = kt->axis[2][k];
+                grid_coords(fr, px, py, pz, gx, gy, gz);               // pts_to_can_pts + the renderer's get_grid_coords
+            }
+        } else if (inside) {
             px = kt->axis[0][i]; py = kt->axis[1][j]; pz = kt->axis[2][k];
             grid_coords(fr, px, py, pz, gx, gy, gz);                   // pts_to_can_pts + the demo's get_grid_coords (/ 0.005)
             keep = sample_occupancy(fr.occ, fr.vol_dhw[0][0], fr.vol_dhw[0][1], fr.vol_dhw[0][2], gx, gy, gz) > 0.f;   // :270-281
@@ -3615,7 +3627,8 @@ int device_ready(int* cus) {
                 {reinterpret_cast<const void*>(&head_forward_kernel<FUSED_WAVES, 0>), render_lds_bytes(FORM_F32)},
                 {reinterpret_cast<const void*>(&head_forward_kernel<FUSED_WAVES, 1>), render_lds_bytes(FORM_F32)},
                 {reinterpret_cast<const void*>(&head_forward_kernel<FUSED_WAVES, 2>), render_lds_bytes(FORM_F32)},
-                {reinterpret_cast<const void*>(&density_lattice_kernel), head_bytes},
+                {reinterpret_cast<const void*>(&density_lattice_kernel<false>), head_bytes},
+                {reinterpret_cast<const void*>(&density_lattice_kernel<true>), head_bytes},
                 {reinterpret_cast<const void*>(&field_points_kernel<true>), head_bytes},
                 {reinterpret_cast<const void*>(&field_points_kernel<false>), head_bytes},
             };
@@ -4290,16 +4303,17 @@ int gpnerf_build_occupancy(const GpnerfFrame* f, float* occ, void* stream) {
     return launch_status();
 }
 
-int gpnerf_density_lattice(const GpnerfFrame* f, const float* axis_x, const float* axis_y, const float* axis_z, const int32_t* dims,
-                           int32_t pad, int32_t neg_ray, float* cube, int64_t* n_kept, void* stream) {
-    if (!f || !axis_x || !axis_y || !axis_z || !dims || !cube || pad < 0 || !f->occ || !f->head_blob_ref) return GPNERF_E_ARG;
+// the two lattice entry points: `inside` null = the demo's (occupancy cull, literal voxel size), otherwise the caller's kept set
+static int launch_lattice(const GpnerfFrame* f, const float* axis_x, const float* axis_y, const float* axis_z, const int32_t* dims,
+                          int32_t pad, int32_t neg_ray, const uint8_t* inside, float* cube, int64_t* n_kept, void* stream) {
+    if (!f || !axis_x || !axis_y || !axis_z || !dims || !cube || pad < 0 || !f->head_blob_ref) return GPNERF_E_ARG;
     if (dims[0] < 1 || dims[1] < 1 || dims[2] < 1) return GPNERF_E_ARG;
     const int64_t PX = (int64_t)dims[0] + 2 * (int64_t)pad, PY = (int64_t)dims[1] + 2 * (int64_t)pad, PZ = (int64_t)dims[2] + 2 * (int64_t)pad;
     if (PX >= ((int64_t)1 << 24) || PY >= ((int64_t)1 << 24) || PZ >= ((int64_t)1 << 24) || PX * PY * PZ >= ((int64_t)1 << 40))
         return GPNERF_E_ARG;
     FrameK k;
     if (!to_framek(f, k, true, true)) return GPNERF_E_ARG;
-    k.voxel[0] = k.voxel[1] = k.voxel[2] = 0.005f;     // demo_render.py:91 `xyz / 0.005`, as under GPNERF_FLAG_OCC_CULL
+    if (!inside) k.voxel[0] = k.voxel[1] = k.voxel[2] = 0.005f;     // demo_render.py:91 `xyz / 0.005`, as under GPNERF_FLAG_OCC_CULL
     int n_cus = 0;
     if (device_ready(&n_cus) != GPNERF_OK) return GPNERF_E_DEVICE;
     LatticeArgs a;
@@ -4313,12 +4327,29 @@ int gpnerf_density_lattice(const GpnerfFrame* f, const float* axis_x, const floa
     a.n_tiles = (long)PX * a.bricks_y * a.bricks_z;
     a.cube = cube;
     a.n_kept = reinterpret_cast<unsigned long long*>(n_kept);
+    a.inside = inside;
     if (n_kept && !zero_async(n_kept, sizeof(int64_t), stream)) return GPNERF_E_LAUNCH;
     // one workgroup per CU (the head image fills most of its LDS), persistent over the tiles
     const long wgs = (a.n_tiles + LAT_WAVES - 1) / LAT_WAVES;
     const unsigned grid = (unsigned)(wgs < n_cus ? wgs : n_cus);
-    hipLaunchKernelGGL(density_lattice_kernel, dim3(grid), dim3(LAT_WAVES * 64), sizeof(float) * gpl::BLOB_FLOATS, S_(stream), a);
+    if (inside)
+        hipLaunchKernelGGL(density_lattice_kernel<true>, dim3(grid), dim3(LAT_WAVES * 64), sizeof(float) * gpl::BLOB_FLOATS, S_(stream), a);
+    else
+        hipLaunchKernelGGL(density_lattice_kernel<false>, dim3(grid), dim3(LAT_WAVES * 64), sizeof(float) * gpl::BLOB_FLOATS, S_(stream), a);
     return launch_status();
+}
+
+int gpnerf_density_lattice(const GpnerfFrame* f, const float* axis_x, const float* axis_y, const float* axis_z, const int32_t* dims,
+                           int32_t pad, int32_t neg_ray, float* cube, int64_t* n_kept, void* stream) {
+    if (!f || !f->occ) return GPNERF_E_ARG;
+    return launch_lattice(f, axis_x, axis_y, axis_z, dims, pad, neg_ray, nullptr, cube, n_kept, stream);
+}
+
+int gpnerf_density_lattice_masked(const GpnerfFrame* f, const float* axis_x, const float* axis_y, const float* axis_z,
+                                  const int32_t* dims, int32_t pad, int32_t neg_ray, const uint8_t* inside, float* cube,
+                                  int64_t* n_kept, void* stream) {
+    if (!inside) return GPNERF_E_ARG;
+    return launch_lattice(f, axis_x, axis_y, axis_z, dims, pad, neg_ray, inside, cube, n_kept, stream);
 }
 
 int gpnerf_query_points(const GpnerfFrame* f, const float* pts, int64_t n_points, uint32_t flags, const double* lattice, float* raw,

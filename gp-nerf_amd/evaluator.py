@@ -14,6 +14,9 @@ Image writing (cfg.test.save_imgs) is I/O and out of scope.
 `render.render(batch)` -> `Evaluator.evaluate`, the render time summed from `ret["rtime"]`, the means from `summarize()`;
 pinned to the reference's own loop over three frames (tests/golden/loop_demo_3frames.npz).
 
+`MeshEvaluator` mirrors libs/evaluators/if_nerf_mesh.py for a geometry-mode renderer (use_rgbhead False); the loop takes it
+through `evaluate_loop(evaluator=...)` and otherwise constructs the image evaluator, as the reference's loop always does.
+
 `DeviceEvaluator` (opt-in: `evaluate_loop(device_metrics=True)` or GPNERF_DEVICE_METRICS=1) computes the same three numbers with
 gpnerf_image_metrics (csrc/gpnerf_metrics.hip): four kernel launches per frame into a device slot, no host synchronisation in
 `evaluate`; the host reads every frame's slot in one copy when `.mse` / `.psnr` / `.ssim` are first asked for.
@@ -220,12 +223,57 @@ class DeviceEvaluator(Evaluator):
             raise ValueError("win_size exceeds image extent")
 
 
+class MeshEvaluator:
+    """The geometry mode's evaluator (libs/evaluators/if_nerf_mesh.py): `evaluate` saves the lattice points whose alpha is above
+    `mesh_th` to `<result_path>/pts/<frame_index>.npy`, `visualize` exports the mesh to `<result_path>/mesh/<frame_index>.ply`
+    (`..._cam<c>.ply` when the batch has `cam_ind`), `summarize()` returns {} (the reference evaluates no mesh metric).  `output` is
+    what Renderer.render returns with use_rgbhead False.  The directories are made with os.makedirs (the reference shells out to
+    mkdir -p and announces them through termcolor).  export_mesh (not in the reference, whose loop never calls visualize):
+    `evaluate` also calls `visualize`, so that an evaluation loop leaves the meshes behind."""
+    PAD = 10                              # if_nerf_mesh.py:20, the np.pad(cube, 10) of BaseRender.py:269
+
+    def __init__(self, result_path, mesh_th, export_mesh=False):
+        self.mesh_th = mesh_th
+        self.export_mesh = bool(export_mesh)
+        self.vis_result_dir = os.path.join(result_path, "mesh")
+        self.pts_result_dir = os.path.join(result_path, "pts")
+
+    @staticmethod
+    def _scalar(v):
+        return int(np.asarray(v.detach().cpu() if isinstance(v, torch.Tensor) else v).reshape(-1)[0])
+
+    def evaluate(self, output, batch):
+        p = self.PAD
+        cube = np.asarray(output["cube"])[p:-p, p:-p, p:-p]
+        above = cube > self.mesh_th
+        if "pts" in batch:
+            pts = torch.as_tensor(batch["pts"][0]).detach().cpu().numpy()[above]
+        else:
+            # the same points from the three axes: pts[i, j, k] = (x[i], y[j], z[k]), without the [X,Y,Z,3] array
+            i, j, k = np.nonzero(above)
+            ax = [np.asarray(a, dtype=np.float32) for a in output["axes"]]
+            pts = np.stack([ax[0][i], ax[1][j], ax[2][k]], axis=-1)
+        os.makedirs(self.pts_result_dir, exist_ok=True)
+        np.save(os.path.join(self.pts_result_dir, f"{self._scalar(batch['frame_index'])}.npy"), pts)
+        if self.export_mesh:
+            self.visualize(output, batch)
+
+    def summarize(self):
+        return {}
+
+    def visualize(self, output, batch):
+        os.makedirs(self.vis_result_dir, exist_ok=True)
+        i = self._scalar(batch["frame_index"])
+        name = f"{i}_cam{self._scalar(batch['cam_ind'])}.ply" if "cam_ind" in batch else f"{i}.ply"
+        output["mesh"].export(os.path.join(self.vis_result_dir, name))
+
+
 def metrics_switch(device_metrics=None):
     """evaluate_loop's `device_metrics`: None -> the environment's GPNERF_DEVICE_METRICS=1, anything else -> bool(...)"""
     return os.environ.get("GPNERF_DEVICE_METRICS", "0") == "1" if device_metrics is None else bool(device_metrics)
 
 
-def evaluate_loop(render, eval_loader, cfg, device=None, quiet=False, pipeline=None, device_metrics=None):
+def evaluate_loop(render, eval_loader, cfg, device=None, quiet=False, pipeline=None, device_metrics=None, evaluator=None):
     """`Trainer.evaluate` (libs/trainers/BaseTrainer.py:255-280) without its image writing: for every batch of `eval_loader`
     move it to `device` (`_read_inputs`, :89-97), `ret = render.render(batch)` (the reference calls `.module.render` on its
     DataParallel wrapper; a wrapped model is unwrapped here too), `Evaluator.evaluate(ret, batch)`, `total_time += ret["rtime"]`;
@@ -238,13 +286,20 @@ def evaluate_loop(render, eval_loader, cfg, device=None, quiet=False, pipeline=N
     frame t.  Default: on when the renderer offers `prefetch` and is neither progressive nor sharded.  Same bits per frame.
     device_metrics (not in the reference): the frames' metrics by `DeviceEvaluator` -- enqueued behind each frame's per-ray kernel,
     read once behind the last frame (inside `wall_time`).  Default (None): on with GPNERF_DEVICE_METRICS=1 in the environment,
-    otherwise off."""
+    otherwise off.
+    evaluator (not in the reference, whose Trainer.evaluate always constructs the image Evaluator, BaseTrainer.py:257, and imports
+    the mesh one without using it): an instance used in place of the one constructed here -- a MeshEvaluator for a geometry-mode
+    renderer, whose output has no rgb_map.  Without it the loop builds what it always built, whatever use_rgbhead says.  The
+    per-frame lists are the evaluator's where it has them, otherwise empty.  A renderer whose head has use_rgbhead False has no
+    per-ray kernel to prefetch behind: `pipeline` defaults to off for it."""
     model = getattr(render, "module", render)
     model.eval()
-    evaluator = (DeviceEvaluator if metrics_switch(device_metrics) else Evaluator)(cfg, cfg.test.test_seq)
+    if evaluator is None:
+        evaluator = (DeviceEvaluator if metrics_switch(device_metrics) else Evaluator)(cfg, cfg.test.test_seq)
     count, total_time = 0, 0.0
     if pipeline is None:
-        pipeline = hasattr(model, "prefetch") and not getattr(model, "progressive", False) and getattr(model, "shard_group", None) is None
+        pipeline = (hasattr(model, "prefetch") and not getattr(model, "progressive", False) and getattr(model, "shard_group", None) is None
+                    and getattr(getattr(model, "nerfhead", None), "use_rgbhead", True))
 
     def move(v):
         if device is None:
@@ -291,7 +346,7 @@ def evaluate_loop(render, eval_loader, cfg, device=None, quiet=False, pipeline=N
                 total_time += ret["rtime"]
                 count += 1
                 val = nxt
-    per_frame = {"mse": list(evaluator.mse), "psnr": list(evaluator.psnr), "ssim": list(evaluator.ssim)}
+    per_frame = {k: list(getattr(evaluator, k, ())) for k in ("mse", "psnr", "ssim")}
     wall = _time.time() - t_loop                              # (behind the lists: the device evaluator's one read belongs to the loop)
     if quiet:                                                 # (summarize() prints its three means, as the reference's does)
         import contextlib

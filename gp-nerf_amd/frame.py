@@ -711,17 +711,83 @@ def lattice_axes(box, voxel_size):
     return [lattice_axis(box[0, a], box[1, a], vs[a]) for a in range(3)]
 
 
-def density_lattice(frame, axes, neg_ray=False, pad=MESH_PAD):
-    """gpnerf_density_lattice: the padded alpha cube [X+2p, Y+2p, Z+2p] (float32, device) of the lattice `axes` (host float32 arrays,
-    lattice_axes()), and the device int64 count of kept (occupied) points."""
+def dataset_lattice_axis(lo, hi, step):
+    """np.arange(lo, hi + step, step) as ZjumocapDataset.py:397-402 calls it (lo, hi float32 entries of can_bounds, step the float64
+    voxel size), followed by :404's astype(float32), on the host.  The source line's result depends on numpy's promotion rules; the
+    arithmetic here is fixed to the reference era's (numpy < 2, value-based casting: a float32 array scalar plus a Python float is
+    float64, where NEP 50 would round the stop to float32): lo = the float32 bound widened, stop = float64(hi) + step,
+    n = ceil((stop - lo) / step), value i = lo + i * step in float64, rounded to float32."""
+    lo, step = np.float64(np.float32(lo)), np.float64(step)
+    stop = np.float64(np.float32(hi)) + step
+    n = int(np.ceil((stop - lo) / step))
+    return (lo + np.arange(max(n, 0), dtype=np.float64) * step).astype(np.float32)
+
+
+def dataset_lattice_axes(can_bounds, voxel_size):
+    """The three lattice axes of ZjumocapDataset.py:397-402 (float32 host arrays): dataset_lattice_axis() per axis of can_bounds
+    [2,3].  batch['pts'] is their meshgrid ('ij', x slowest)."""
+    box = np.asarray(can_bounds, dtype=np.float32).reshape(2, 3)
+    vs = np.asarray(voxel_size, dtype=np.float64).ravel()
+    return [dataset_lattice_axis(box[0, a], box[1, a], vs[a]) for a in range(3)]
+
+
+def _axes_to(axes, dev):
+    return [torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev, non_blocking=False) for a in axes]
+
+
+def visual_hull(axes, masks, Ks, RTs):
+    """gpnerf_visual_hull: batch['inside'] (ZjumocapDataset.prepare_inside_pts) of the lattice `axes` (host float32 arrays,
+    dataset_lattice_axes()) carved on the device.  masks: device uint8 [n,h,w], the views of inside_view in order (0, 1, and 100 on
+    the border band); Ks [n,3,3] and RTs [n,3,4] (T in metres): host arrays, used in float64.  Returns (inside uint8 [X,Y,Z] holding
+    the mask VALUES -- a border value is sticky and counts as inside --, n_inside int64 [1]), both on the device; nothing is read
+    back."""
     lib = L.lib()
-    if not frame.c.occ:
-        frame.build_occupancy()
+    _require_gpu(masks, "masks")
+    if masks.dtype != torch.uint8 or masks.dim() != 3 or not masks.is_contiguous():
+        raise L.GpnerfError(f"visual_hull: expected contiguous uint8 masks [n,h,w], got {masks.dtype} {tuple(masks.shape)}")
+    n, mh, mw = masks.shape
+    cams = np.concatenate([np.asarray(Ks, dtype=np.float64).reshape(-1, 9), np.asarray(RTs, dtype=np.float64).reshape(-1, 12)], axis=1)
+    if cams.shape[0] != n:
+        raise L.GpnerfError(f"visual_hull: {n} masks but {cams.shape[0]} cameras")
+    cams = np.ascontiguousarray(cams)
+    dev = masks.device
+    ax = _axes_to(axes, dev)
+    dims = (C.c_int32 * 3)(*[len(a) for a in axes])
+    inside = torch.empty(tuple(len(a) for a in axes), device=dev, dtype=torch.uint8)
+    n_inside = torch.empty((1,), device=dev, dtype=torch.int64)
+    L.check(lib.gpnerf_visual_hull(ax[0].data_ptr(), ax[1].data_ptr(), ax[2].data_ptr(), dims, n, masks.data_ptr(), mh, mw,
+                                   cams.ctypes.data_as(L.DP), inside.data_ptr(), n_inside.data_ptr(), _stream_ptr(dev)), "gpnerf_visual_hull")
+    return inside, n_inside
+
+
+def density_lattice(frame, axes, neg_ray=False, pad=MESH_PAD, inside=None):
+    """gpnerf_density_lattice: the padded alpha cube [X+2p, Y+2p, Z+2p] (float32, device) of the lattice `axes` (host float32 arrays,
+    lattice_axes()), and the device int64 count of kept (occupied) points.  With `inside` (device uint8 or bool [X,Y,Z]: visual_hull()'s
+    output or batch['inside']) it is gpnerf_density_lattice_masked: the kept points are the non-zero ones, grid coordinates are the
+    renderer's (the frame's voxel size), and no occupancy volume is built."""
+    lib = L.lib()
     if frame.c.head_blob_ref is None:
         raise L.GpnerfError("density_lattice: the frame's head blob must be pack_head()'s tensor (it carries the reference-order image)")
-    dev = frame.occ.device
-    ax = [torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev, non_blocking=False) for a in axes]
     dims = (C.c_int32 * 3)(*[len(a) for a in axes])
+    if inside is not None:
+        _require_gpu(inside, "inside")
+        if inside.dtype == torch.bool:
+            inside = inside.view(torch.uint8)
+        if inside.dtype != torch.uint8 or tuple(inside.shape) != tuple(len(a) for a in axes) or not inside.is_contiguous():
+            raise L.GpnerfError(f"density_lattice: inside must be contiguous uint8 / bool {tuple(len(a) for a in axes)}, got "
+                                f"{inside.dtype} {tuple(inside.shape)}")
+        dev = inside.device
+        ax = _axes_to(axes, dev)
+        cube = torch.empty(tuple(len(a) + 2 * pad for a in axes), device=dev, dtype=torch.float32)
+        n_kept = torch.empty((1,), device=dev, dtype=torch.int64)
+        L.check(lib.gpnerf_density_lattice_masked(C.byref(frame.c), ax[0].data_ptr(), ax[1].data_ptr(), ax[2].data_ptr(), dims, int(pad),
+                                                  int(bool(neg_ray)), inside.data_ptr(), cube.data_ptr(), n_kept.data_ptr(),
+                                                  _stream_ptr(dev)), "gpnerf_density_lattice_masked")
+        return cube, n_kept
+    if not frame.c.occ:
+        frame.build_occupancy()
+    dev = frame.occ.device
+    ax = _axes_to(axes, dev)
     cube = torch.empty(tuple(len(a) + 2 * pad for a in axes), device=dev, dtype=torch.float32)
     n_kept = torch.empty((1,), device=dev, dtype=torch.int64)
     L.check(lib.gpnerf_density_lattice(C.byref(frame.c), ax[0].data_ptr(), ax[1].data_ptr(), ax[2].data_ptr(), dims, int(pad),
@@ -867,7 +933,7 @@ def mesh_normals(cube, vertices, step=None):
 
 
 def extract_mesh(frame, voxel_size, bounds_min, Rh, Th, neg_ray=False, iso=1.0 / 50.0, host=None, clean=None, fill_cavities=None,
-                 normals=False):
+                 normals=False, lattice=None):
     """The geometry mode of demo_render.py's render_rays (:166-175, 249-311, 366-376) on the device: the box of the occupied voxels,
     the lattice, the alpha cube and its marching-cubes mesh.  Two host reads: the box (6 values) and the mesh counts (2).
     Returns {"cube" (device [X+20,Y+20,Z+20]), "vertices", "faces" (device), "axes", "can_bounds", "n_kept" (device int64),
@@ -875,12 +941,19 @@ def extract_mesh(frame, voxel_size, bounds_min, Rh, Th, neg_ray=False, iso=1.0 /
     clean (cube_clean's `keep`: "largest" or N) and fill_cavities (None: filled whenever clean is given): marching cubes then runs on
     the cleaned cube -- "cube" stays the untouched one -- and "clean_stats" (device int64 [6]) is added; normals: "normals" (device
     [nv,3], mesh_normals of the cube the mesh was made from, scaled by 1 / voxel size) is added.  With all three off no further launch
-    is enqueued."""
-    box = mesh_box(frame, voxel_size, bounds_min, Rh, Th, host=host)
+    is enqueued.
+    lattice: a ready (cube, axes, n_kept) -- the dense renderer's hull-carved cube (density_lattice(inside=...)) -- in place of the
+    box, the lattice and the occupancy-culled cube; cleaning, marching cubes, normals and "lattice" are then the same code.  The box
+    read does not happen and "can_bounds" is left out."""
     vs = host[0] if host is not None else voxel_size
-    axes = lattice_axes(box, vs)
-    cube, n_kept = density_lattice(frame, axes, neg_ray=neg_ray)
-    res = {"cube": cube, "axes": axes, "can_bounds": box, "n_kept": n_kept, "lattice": lattice_of(axes, vs)}
+    if lattice is not None:
+        cube, axes, n_kept = lattice
+        res = {"cube": cube, "axes": axes, "n_kept": n_kept, "lattice": lattice_of(axes, vs)}
+    else:
+        box = mesh_box(frame, voxel_size, bounds_min, Rh, Th, host=host)
+        axes = lattice_axes(box, vs)
+        cube, n_kept = density_lattice(frame, axes, neg_ray=neg_ray)
+        res = {"cube": cube, "axes": axes, "can_bounds": box, "n_kept": n_kept, "lattice": lattice_of(axes, vs)}
     fill = (clean is not None) if fill_cavities is None else bool(fill_cavities)
     surface = cube
     if clean is not None or fill:

@@ -8,6 +8,8 @@ Drop-in contract:
     (libs/trainers/BaseTrainer.py:276) and only the reference's demo renderer returned.
   * sub-modules are named `encoder` and `nerfhead` and own the reference's parameters, so
     `load_state_dict(ckpt['state_dict'], strict=True)` works (tools/inference.py:67-74).
+  * with `cfg.head.rgb.use_rgbhead = False` `.render(batch)` is the geometry mode of BaseRender.py:255-272 instead
+    (`Renderer.render_geometry`: `cube`, `mesh`, ... from `batch['pts']` + `batch['inside']`, or with the hull carved on the device).
   * sampling is deterministic (is_train=False, as libs/renders/demo_render.py:661 forces for inference;
     SURVEY.md §0-6 explains why the dense renderer's `is_train` latch is not reproduced).
 
@@ -346,6 +348,83 @@ class Renderer(nn.Module):
                                "sp_encode": t_frame, "bf_sigma": 0.0, "sigma_f": t_mesh},
                 "etime": etime, "rtime": max(0.0, (t4 - te) - etime)}
 
+    HULL_KEYS = ("hull_masks", "hull_Ks", "hull_RTs", "can_bounds")
+
+    def render_geometry(self, batch):
+        """The dense renderer's geometry mode (BaseRender.py:255-272, use_rgbhead False) on the device: density at the lattice points
+        of the visual hull, 1 - exp(-sigma) scattered into a cube, np.pad(cube, 10), marching cubes at self.mesh_th (build_render:
+        1 / cfg.test.mesh_th).  (The reference's own branch cannot run as written -- render_rays reads an undefined rays_d at
+        BaseRender.py:120 when the batch brings `pts` --, so its parts are mirrored one by one: DESIGN 4.9.)
+        The lattice and the kept set come
+          (a) from the reference's batch keys: `pts` [1,X,Y,Z,3] (the meshgrid of ZjumocapDataset.py:397-404; only its three edge
+              slices are read) and `inside` [1,X,Y,Z] (prepare_inside_pts: non-zero = inside); or
+          (b) when `inside` is absent, from keys the reference does not have: `hull_masks` [1,n,h,w] uint8 (the inside_view masks in
+              order: 0, 1, and 100 on the border band), `hull_Ks` [1,n,3,3], `hull_RTs` [1,n,3,4] (T in metres) and `can_bounds`
+              [1,2,3] -- the axes are frame.dataset_lattice_axes' and the hull is carved on the device (gpnerf_visual_hull): the
+              loader neither builds the 12 B/point `pts` array nor carves.
+        Returns `cube` (the padded alpha cube, float32 numpy), `mesh` (mesh.Mesh, vertices in index units of the padded cube), `axes`
+        (three host float32 arrays), `n_inside` (kept points), `time_slots`, `etime`, `rtime`, and `mesh_stats` with mesh_clean.
+        mesh_clean / mesh_normals / mesh_colors act as in render_mesh.  Host reads: the constants (with the axes or the cameras) before
+        the encoder, the mesh counts, and the results."""
+        dev = batch["src_imgs"].device
+        have_a = "pts" in batch and "inside" in batch
+        have_b = all(k in batch for k in self.HULL_KEYS)
+        if not have_a and not have_b:
+            raise L.GpnerfError("geometry mode (use_rgbhead=False) needs the batch keys 'pts' and 'inside', or -- to carve the hull on "
+                                "the device -- " + ", ".join(repr(k) for k in self.HULL_KEYS) + f"; the batch has {sorted(batch.keys())}")
+        torch.cuda.synchronize(dev)
+        te = time.time()
+        if have_a:
+            pts = batch["pts"]
+            if pts.dim() != 5 or pts.shape[0] != 1 or pts.shape[-1] != 3 or tuple(batch["inside"].shape) != tuple(pts.shape[:4]):
+                raise L.GpnerfError(f"geometry mode: expected pts [1,X,Y,Z,3] and inside [1,X,Y,Z], got {tuple(pts.shape)} and "
+                                    f"{tuple(batch['inside'].shape)}")
+            extra = [pts[0, :, 0, 0, 0].float(), pts[0, 0, :, 0, 1].float(), pts[0, 0, 0, :, 2].float()]
+        else:
+            extra = [batch["can_bounds"][0], batch["hull_Ks"][0], batch["hull_RTs"][0]]
+        fetched = F_.fetch_host(batch["src_Ks"][0], batch["src_poses"][0], batch["Rh"][0], batch["Th"][0], batch["bounds"][0, 0],
+                                self.voxel_size, batch["out_sh"][0], self.voxel_size, *extra)
+        consts, vs_host, extra = fetched[:7], fetched[7], fetched[8:]
+        prepared = self.prepare_builder_inputs(batch, consts)
+        self.nerfhead.head_blob(dev)
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(5)]
+        ev[0].record()
+        featmaps = self.encode(batch)
+        ev[1].record()
+        frame = self.build_frame(batch, featmaps, consts, prepared)
+        ev[2].record()
+        if have_a:
+            axes = [a.astype(np.float32) for a in extra]
+            inside = batch["inside"][0]
+            if inside.dtype not in (torch.uint8, torch.bool):
+                inside = inside != 0
+            inside = inside.to(dev).contiguous()
+        else:
+            axes = F_.dataset_lattice_axes(extra[0], vs_host)
+            masks = batch["hull_masks"][0]
+            if masks.dtype != torch.uint8:
+                raise L.GpnerfError(f"geometry mode: hull_masks must be uint8 (0, 1, border 100), got {masks.dtype}")
+            inside, _ = F_.visual_hull(axes, masks.to(dev).contiguous(), extra[1], extra[2])
+        ev[3].record()
+        neg = self._neg_ray(batch)
+        cube, n_kept = F_.density_lattice(frame, axes, neg_ray=neg, pad=F_.MESH_PAD, inside=inside)
+        m = F_.extract_mesh(frame, self.voxel_size, None, None, None, neg_ray=neg, iso=self.mesh_th, host=[vs_host], clean=self.mesh_clean,
+                            normals=self.mesh_normals, lattice=(cube, axes, n_kept))
+        colours = None
+        if self.mesh_colors:
+            colours = F_.query_points(frame, m["vertices"], neg_ray=neg, want=("rgb",), lattice=m["lattice"])["rgb"]
+        ev[4].record()
+        cube_np = m["cube"].cpu().numpy()
+        mesh = M_.Mesh(m["vertices"].cpu().numpy(), m["faces"].cpu().numpy(), colours.cpu().numpy() if colours is not None else None,
+                       m["normals"].cpu().numpy() if "normals" in m else None)
+        stats = dict(zip(L.CUBE_STATS, m["clean_stats"].cpu().tolist())) if "clean_stats" in m else None
+        n_inside = int(n_kept.cpu().item())
+        t4 = time.time()
+        etime = ev[0].elapsed_time(ev[1]) * 1e-3
+        t_frame, t_hull, t_mesh = (ev[i].elapsed_time(ev[i + 1]) * 1e-3 for i in (1, 2, 3))
+        return {"cube": cube_np, "mesh": mesh, "axes": axes, "n_inside": n_inside, **({"mesh_stats": stats} if stats is not None else {}),
+                "time_slots": {"frame": t_frame, "hull": t_hull, "mesh": t_mesh}, "etime": etime, "rtime": max(0.0, (t4 - te) - etime)}
+
     def query_points(self, batch, pts, want=("rgb", "sigma"), occ_cull=False):
         """The frame's radiance field at world points pts [n,3] (device float32): the producers as render_mesh runs them (encoder,
         volumes, frame, occupancy), then frame.query_points under the batch's neg_ray.  Returns its dict of device tensors
@@ -511,7 +590,7 @@ class Renderer(nn.Module):
         if self.progressive:
             return self.render_progressive(batch)
         if not self.nerfhead.use_rgbhead:
-            raise L.GpnerfError("mesh extraction (use_rgbhead=False, BaseRender.py:255-272) is outside the per-ray render path")
+            return self.render_geometry(batch)
         dev = batch["ray_o"].device
         main = torch.cuda.current_stream(dev)
         if prefetched is None:

@@ -372,6 +372,45 @@ int gpnerf_make_rays_demo(int32_t H, int32_t W, const float* Kinv, const float* 
 int gpnerf_density_lattice(const GpnerfFrame* frame, const float* axis_x, const float* axis_y, const float* axis_z, const int32_t* dims,
                            int32_t pad, int32_t neg_ray, float* cube, int64_t* n_kept, void* stream);
 
+/* ---- geometry mode of the dense renderer (libs/renders/BaseRender.py:255-272: cfg.head.rgb.use_rgbhead False) ----
+ *
+ * gpnerf_visual_hull: batch['inside'] -- ZjumocapDataset.prepare_inside_pts (libs/datasets/ZjumocapDataset.py:259-283) with
+ * data_utils.project (libs/datasets/data_utils.py:239-250), which the reference runs in numpy on a loader worker for every batch --
+ * on the lattice axis_x (x) axis_y (x) axis_z (meshgrid 'ij', x slowest; frame.dataset_lattice_axes() makes the axes of :397-402).
+ *   axis_*: device float32; dims: host int32[3], each >= 1, X * Y * Z <= 2^28;
+ *   masks: device uint8 [n_views][mask_h][mask_w], the views of self.inside_view in order (get_mask, :68-86: 0, 1 and the erode /
+ *     dilate border band's 100); n_views: 1 to 8;
+ *   cams: host double [n_views][21] = K 3x3 row-major, then RT 3x4 row-major, T in metres (the reference divides by 1000 at :268);
+ *   inside: device uint8 [X][Y][Z], every element written; n_inside: device int64 or NULL, receives the number of non-zero elements
+ *     (set by the call: a kernel of the library's own, one integer atomic per wavefront, order-independent).
+ * A point's value starts at 1.  For each view in order, only while the value is exactly 1: the float32 point widened to float64,
+ * c = p0 RT[:,0] + p1 RT[:,1] + p2 RT[:,2] + RT[:,3], h = c0 K[:,0] + c1 K[:,1] + c2 K[:,2] (float64, multiply then add in that
+ * order, unfused), x = h0 / h2, y = h1 / h2, column = clip(int32(rint(x)), 0, mask_w - 1), row likewise (rint: half to even, as
+ * np.round); the value becomes masks[view][row][column].  Two quirks of the reference are kept:
+ *   - border pixels are sticky: a point that picks up 100 is not 1 any more, no later view tests it, and it stays 100 (the renderer's
+ *     .bool() counts it as inside); a point that picks up 0 stays 0.  The output is the value, not a boolean;
+ *   - a quotient that is not finite, or whose rounded value does not fit int32, converts to INT32_MIN as numpy's astype does on
+ *     x86-64, so the clip gives column / row 0 (tested explicitly, not left to the device's saturating conversion).
+ * Kernel launches only, on the caller's stream; nothing allocated, nothing waited for; captures into a HIP graph.  GPNERF_E_ARG for a
+ * null pointer (n_inside excepted), n_views outside 1..8, a mask or lattice size < 1, or more than 2^28 points. */
+int gpnerf_visual_hull(const float* axis_x, const float* axis_y, const float* axis_z, const int32_t* dims, int32_t n_views,
+                       const uint8_t* masks, int32_t mask_h, int32_t mask_w, const double* cams, uint8_t* inside, int64_t* n_inside,
+                       void* stream);
+
+/* gpnerf_density_lattice_masked: gpnerf_density_lattice with a caller-given kept set -- the cube of BaseRender.py:262-269
+ * (sigma at pts[inside], cube[inside] = 1 - exp(-sigma), np.pad(cube, pad)).  The same kernel (a second instantiation: the same bricks
+ * of 4 x 8 points of one x-slice of the padded cube, one lane per point, persistent workgroups), with these differences:
+ *   - a point is kept iff inside[i][j][k] != 0 (device uint8 [X][Y][Z]: gpnerf_visual_hull's output or batch['inside']; 100 and 255
+ *     keep a point as 1 does);
+ *   - grid coordinates are the renderer's (BaseRender.get_grid_coords, the frame's voxel size), the form gpnerf_query_points uses
+ *     without GPNERF_FLAG_OCC_CULL; frame->occ is not read;
+ *   - a kept point's alpha is, bit for bit, gpnerf_query_points' alpha at the world point (axis_x[i], axis_y[j], axis_z[k]) with
+ *     GPNERF_FLAG_DENSITY_ONLY and no cull; every other element of the cube, padding included, is written as 0;
+ *   - a 32-point tile with no kept point does no gather and no matrix work; n_kept (device int64 or NULL) is set by the call. */
+int gpnerf_density_lattice_masked(const GpnerfFrame* frame, const float* axis_x, const float* axis_y, const float* axis_z,
+                                  const int32_t* dims, int32_t pad, int32_t neg_ray, const uint8_t* inside, float* cube,
+                                  int64_t* n_kept, void* stream);
+
 /* gpnerf_query_points: the radiance field at n_points caller-given world points -- NeRFHead.forward (trainhead.py:159-163) in the
  * reference-order form (GPNERF_FLAG_REF_ORDER), the arithmetic of the fused kernel's step: grid coordinates (pts_to_can_pts +
  * get_grid_coords), the four volume levels (multiply-then-add trilinear taps), the sigma feature layer, Projector.compute of the three
