@@ -241,12 +241,21 @@ def test_ray_order_changes_tiling_not_results(fm, syn):
             assert torch.equal(torch.nan_to_num(got[k].float()), torch.nan_to_num(base[k].float())), k
 
 
-@pytest.mark.parametrize("neg,split_f16,lb", [(False, False, False), (True, False, False), (False, True, False), (False, False, True),
-                                              (True, True, True)])
-def test_progressive_sample_culling_matches_restatement(neg, split_f16, lb, fm, oracle, syn):
+CULL_CASES = [(False, False, False, None), (True, False, False, None), (False, True, False, None), (False, False, True, None), (True, True, True, None),
+              (False, False, True, "mask"), (False, False, False, "in-loop")]
+
+
+@pytest.mark.parametrize("neg,split_f16,lb,flip", CULL_CASES,
+                         ids=[f"{n}-{sp}-{lb}" if fl is None else f"flip-{fl}" for n, sp, lb, fl in CULL_CASES])
+def test_progressive_sample_culling_matches_restatement(neg, split_f16, lb, flip, fm, oracle, syn):
     """demo_render.py's occupancy / alpha culling against the oracle's restatement (itself pinned to outputs of that file,
     tests/golden/demo_*.npz): neg_ray (front test only -- the progressive integral never flips), both kernel forms and the
-    sample-split launch geometry."""
+    sample-split launch geometry.
+
+    flip: GPNERF_FLAG_OCC_CULL | GPNERF_FLAG_FLIP_SAMPLES, which the ABI takes and the oracle models (occ=, flip=True) although
+    the progressive renderer never asks for it: composite step k keeps or culls SAMPLE S-1-k.  "mask": the keep bits computed
+    before the launch into the workspace (occupancy_mask_kernel, Loop::CULLED -- a launch without per-sample outputs);
+    "in-loop": the test inside the sample loop (no workspace)."""
     sc = syn.make_scene(H=24, W=24, seed=77, fill="full", pose="random", aabb_half=(0.2, 0.3, 0.12), bias_std=0.1,
                         vol_occupancy=0.35, neg_cams=neg)
     S = 48
@@ -255,6 +264,35 @@ def test_progressive_sample_culling_matches_restatement(neg, split_f16, lb, fm, 
     occ_ref = oracle.build_occupancy(sc)
     assert_close(occ, occ_ref, 1e-4, "masks3d")
     assert 0.2 < (occ_ref > 0).mean() < 0.8
+    if flip:
+        ref = oracle.render(sc, S, stages=True, occ=occ_ref, flip=True)
+        fwd = oracle.render(sc, S, stages=True, occ=occ_ref)
+        # on the oracle's outputs: culling removes a good part of the samples that have density, not all of them, and the flipped
+        # culled weights are far from the un-flipped ones on most rays that have any weight
+        dense = oracle.render(sc, S, stages=True)["st_raw"][..., 3] > 0
+        removed = (dense & (fwd["st_raw"][..., 3] == 0)).sum() / dense.sum()
+        has = (ref["weights"].sum(1) > 0) | (fwd["weights"].sum(1) > 0)
+        far = (np.abs(ref["weights"] - fwd["weights"]).max(1)[has] > 1e-2).mean()
+        print(f"\n  oracle: culling removes {removed:.3f} of the samples with density; flipping moves the weights of {far:.3f} of the {has.sum()} rays that have any by > 1e-2")
+        assert 0.2 < removed < 0.8 and has.sum() >= 64 and far >= 0.5
+        rays = rays_of(sc)
+        if flip == "mask":
+            kw = dict(occ_cull=True, flip=True, neg_ray=False, load_balance=True, want=("z_vals", "rgb_in", "ray_mask"))
+            plan = fm.render_plan(fr, rays, S, **kw)
+            print(f"  plan: {plan}")
+            assert plan.regions().get("mask"), str(plan)
+            keys = ("rgb_map", "acc_map", "depth_map", "rgb_in_map")
+        else:
+            kw = dict(occ_cull=True, flip=True, neg_ray=False, load_balance=False, want=("weights", "raw", "z_vals", "rgb_in", "ray_mask"))
+            keys = ("rgb_map", "acc_map", "depth_map", "weights", "rgb_in_map")
+        got = cpu(fm.render_fused(fr, rays, S, **kw))
+        for k in keys:
+            print(f"  flip-{flip} {k}: max error against the oracle {assert_close(got[k], ref[k], TOL, k):.3g}")
+        assert_close(got["z_vals"], ref["z_vals"], 1e-6, "z_vals")
+        assert np.array_equal(got["ray_mask"].astype(bool), ref["ray_mask"].astype(bool))
+        if "raw" in got:
+            assert_close(got["raw"], ref["st_raw"], TOL, "raw")
+        return
     got = cpu(fm.render_fused(fr, rays_of(sc), S, neg_ray=neg, occ_cull=True, split_f16=split_f16, load_balance=lb,
                               want=("weights", "raw", "z_vals", "rgb_in")))
     ref = oracle.render(sc, S, neg_ray=neg, stages=True, occ=occ_ref)
@@ -470,16 +508,21 @@ def test_deferred_colour_branch_is_the_plain_loop_bit_for_bit(form, fm, syn):
         rays = rays_all[:n].contiguous()
         order = torch.randperm(n, generator=g).int().cuda()
         for S in (1, 7, 33, 64):
-            for kw in ({}, {"ray_order": order}, {"load_balance": False}, {"early_term": True, "load_balance": False}, {"neg_ray": True}):
+            # (neg_ray on this scene: the all-masked path -- no view sees a sample.  flip: the flipped order on the scene's density)
+            for kw in ({}, {"ray_order": order}, {"load_balance": False}, {"early_term": True, "load_balance": False}, {"neg_ray": True}, {"flip": True}):
                 if form == "split-f16-guarded" and kw.get("load_balance") is False:
                     continue                                   # (the guard keeps its state in the workspace)
                 a = render(fr, rays, S, want=want + ("step_stats",), **kw)
                 b = render(fr, rays, S, want=want, exits=False, **kw)
                 st = a.pop("step_stats").cpu().numpy()
                 same(a, b, (n, S, tuple(kw)))
-                if not kw and n >= 1000 and S == 64:
+                if (not kw or kw.get("flip")) and n >= 1000 and S == 64:
                     fractions.append(st[2] / st[0])
-    assert fractions and all(0.05 < f < 0.95 for f in fractions), fractions       # the scene does queue, and does skip
+                    if kw.get("flip"):          # flipped, with density: another image than the forward order's
+                        assert float((a["rgb_map"] - fwd["rgb_map"]).abs().max()) > 1e-2 and float(a["acc_map"].max()) > 0.1
+                    else:
+                        fwd = a
+    assert len(fractions) == 4 and all(0.05 < f < 0.95 for f in fractions), fractions       # the scene does queue, and does skip, in both orders
     # progressive renderer's culling: keep bits computed before the launch (workspace) and tested sample by sample (none)
     sc3 = syn.make_scene(H=72, W=72, seed=93, fill="full", pose="random", aabb_half=(0.2, 0.3, 0.12), bias_std=0.1, vol_occupancy=0.3)
     fr3 = build_frame(fm, sc3)
@@ -493,7 +536,7 @@ def test_deferred_colour_branch_is_the_plain_loop_bit_for_bit(form, fm, syn):
     # multiplying, keeps counting views for ray_mask and writing zero weights -- same bits, samples_done included
     sc4 = syn.make_scene(H=96, W=96, seed=94, fill="full", pose="random", aabb_half=(0.2, 0.3, 0.12), bias_std=0.1, sigma_bias=60.0)
     fr4 = build_frame(fm, sc4)
-    for kw in ({}, {"load_balance": False}, {"neg_ray": True}):
+    for kw in ({}, {"load_balance": False}, {"neg_ray": True}, {"flip": True}):
         a = render(fr4, rays_of(sc4), 64, want=want + ("step_stats",), **kw)
         b = render(fr4, rays_of(sc4), 64, want=want, exits=False, **kw)
         st = a.pop("step_stats").cpu().numpy()
@@ -533,7 +576,7 @@ def test_frame_level_deferral_is_the_wavefront_level_one_bit_for_bit(form, fm, s
         for k in a:
             assert torch.equal(torch.nan_to_num(a[k].float()), torch.nan_to_num(b[k].float())), (tag, k)
 
-    listed = 0
+    listed, listed_flipped = 0, 0
     # (the last two: nearly every weight non-zero -- the list at its worst-case capacity, every visit's padded unit on top)
     for size, S, bias in ((362, 64, -0.3), (260, 64, -0.3), (370, 33, -0.3), (300, 128, 1.0), (260, 8, 3.0), (362, 8, 3.0)):
         sc = syn.make_scene(H=size, W=size, seed=100 + size, fill="full", pose="random", aabb_half=(0.2, 0.3, 0.12), bias_std=0.1, sigma_bias=bias)
@@ -542,8 +585,10 @@ def test_frame_level_deferral_is_the_wavefront_level_one_bit_for_bit(form, fm, s
         for n in (rays_all.shape[0], rays_all.shape[0] - 37):
             rays = rays_all[:n].contiguous()
             order = torch.randperm(n, generator=g).int().cuda()
-            for kw in ({}, {"ray_order": order}, {"neg_ray": True}, {"early_term": True, "term_eps": 1e-5}):
-                if kw.get("neg_ray") and n != rays_all.shape[0]:
+            # (neg_ray on these scenes: the all-masked path, nothing to list.  flip: the flipped order on the scene's own density --
+            #  the list's entries recompute their sample point from S-1-k)
+            for kw in ({}, {"ray_order": order}, {"neg_ray": True}, {"flip": True}, {"early_term": True, "term_eps": 1e-5}):
+                if (kw.get("neg_ray") or kw.get("flip")) and n != rays_all.shape[0]:
                     continue
                 if S == 128 and not kw.get("early_term"):
                     continue        # (1.4 rounds: with the small workspace this frame splits its tiles' samples -- another association of T)
@@ -564,6 +609,10 @@ def test_frame_level_deferral_is_the_wavefront_level_one_bit_for_bit(form, fm, s
                 assert sa[0] == sb[0] and sa[3] == sb[3] and sa[1] >= sb[1] and sa[4] >= sb[4], (sa, sb)
                 assert sa[5] <= sb[5] and sa[2] == sa[0] - sa[5], (sa, sb)
                 units = (int((a["weights"] != 0).sum()) + 31) // 32
+                if not kw:
+                    fwd = a
+                if kw.get("flip"):      # flipped, with density: as many samples to colour as a tenth of the forward order's at least, another image
+                    assert units * 10 >= (int((fwd["weights"] != 0).sum()) + 31) // 32 > 0 and float((a["rgb_map"] - fwd["rgb_map"]).abs().max()) > 1e-2
                 if "list" not in pa.regions():      # no list, no packed evaluation: the launches counted below are the ones planned to list
                     assert sa[5] == sb[5], (size, S, n, tuple(kw), str(pa), sa, sb)
                 if n == rays_all.shape[0]:
@@ -571,6 +620,7 @@ def test_frame_level_deferral_is_the_wavefront_level_one_bit_for_bit(form, fm, s
                     assert pc.triple()[1] != "UNIFIED" and ("list" in pc.regions()) == ("list" in pa.regions()), str(pc)
                 if sa[5] < sb[5]:
                     listed += 1
+                    listed_flipped += bool(kw.get("flip"))
                     assert "list" in pa.regions() and "list" not in pb.regions() and pa.triple()[0] != "STATIC", (size, S, n, tuple(kw), str(pa), str(pb))
                     # a packed list: exactly `units` evaluations where a second kernel walks it; where the launch's own wavefronts do
                     # (plain launches on the tile queue, the one-launch ZJU-sized shape) every tile pads its last unit
@@ -585,8 +635,11 @@ def test_frame_level_deferral_is_the_wavefront_level_one_bit_for_bit(form, fm, s
             same(a, c, (size, S, "every layer of every sample"))
     # the launches did take the frame-level path: a packed list needs fewer evaluations than per-wavefront passes (frames of two
     # round without a remainder launch evaluate the list themselves and pad what a tile leaves to a whole unit: the
-    # per-wavefront count, 362 x 362 here)
-    assert listed >= 12, listed
+    # per-wavefront count, 362 x 362 here).  12 in the forward order: the eight early-terminated launches of the first four frames
+    # and the four launches of 370 x 370 x 33, whose list a second kernel walks; and one more in the flipped order at least, the
+    # flipped 370 x 370 x 33 launch (QUEUE_REMAINDER / LIST): 13.
+    print(f"\n  launches that needed fewer colour evaluations with the frame's list: {listed}, {listed_flipped} of them flipped")
+    assert listed >= 13 and listed_flipped >= 1, (listed, listed_flipped)
 
 
 def test_reserved_cus_render_the_same_frame(fm, syn):

@@ -276,6 +276,38 @@ REACHABLE = (
 )
 
 
+def test_the_sample_order_and_the_front_test_change_no_plan():
+    """GPNERF_FLAG_NEG_RAY | GPNERF_FLAG_FLIP_SAMPLES (the dense renderer on THuman data) is kernel arithmetic only: for every
+    reachable (shape, colour, arithmetic) triple the planner returns the same plan -- triple, geometry, grid, main_rays, every
+    region and every cleared range -- with the two flags as without, and with either alone.  tests/test_gpu_plans.py relies on it:
+    its direction axis renders the forward order's candidate calls flipped and expects the forward order's plans.
+
+    Points: the chip and the 8 CUs GPNERF_FLAG_RESERVE_CUS leaves at least, every ray count and sample count of the sweep above,
+    every PAIR_COMBOS setting and every early-terminated launch without exits that differs in one more (the chained launches with the
+    colour branch in the step, in the folded and the split forms), at the documented workspace size and at the 48 MB cap that takes
+    a frame's list away."""
+    plan = Planner()
+    lib = plan.lib
+    both = L.FLAG_NEG_RAY | L.FLAG_FLIP_SAMPLES
+    reached, n_points = set(), 0
+    combos = PAIR_COMBOS + tuple(c for c in ALL_COMBOS if c[1] and c[3] and sum(1 for v in c if v) == 3)
+    for n_cus in (256, 8):
+        for S in S_LIST:
+            for n in ray_counts(n_cus, S):
+                W = int(lib.gpnerf_render_workspace_bytes(n, S))
+                for c in combos:
+                    flags, facts = flags_of(c)
+                    for ws in (W, min(W, 48 << 20)):
+                        rc, p = plan(n, S, flags, n_cus, facts, ws)
+                        for extra in (both, L.FLAG_NEG_RAY, L.FLAG_FLIP_SAMPLES):
+                            assert plan(n, S, flags | extra, n_cus, facts, ws) == (rc, p), ("the direction changes the plan", extra, (n_cus, n, S, c, ws), p)
+                        n_points += 1
+                        if rc == 0:
+                            reached.add((SHAPES[p[2]], COLOURS[p[1]], SELS[p[0]]))
+    print(f"\ndirection sweep: {n_points} points, {len(reached)} triples")
+    assert reached == REACHABLE, (sorted(REACHABLE - reached), sorted(reached - REACHABLE))
+
+
 def test_reserved_cus_plan_as_the_smaller_chip():
     """GPNERF_FLAG_RESERVE_CUS(n) on a chip is the plan of a chip with n fewer CUs (whole XCD rounds of 8, at least 8 stay)."""
     plan = Planner()
