@@ -874,8 +874,7 @@ struct Axis {
 // (zero weight), -1 and size themselves give the same taps and weights as before the clamp, and NaN / +-inf land on a bound
 // (v_med3_f32 returns the smallest operand when one is NaN), so the float -> int conversion below is always in range and the
 // bounds tests can be two unsigned integer compares instead of four float compares.  Indices and weights are unchanged.
-DEV Axis axis_taps(float g, int size) {
-    const float sm1 = (float)(size - 1);
+DEV Axis axis_taps(float g, int size, float sm1) {       // sm1: (float)(size - 1), where the caller holds it already
     const float ix = __builtin_amdgcn_fmed3f(((g + 1.f) * 0.5f) * sm1, -1.f, (float)size);
     const float f0 = floorf(ix);
     const float t = ix - f0;
@@ -889,6 +888,7 @@ DEV Axis axis_taps(float g, int size) {
     a.w1 = v1 ? t : 0.f;
     return a;
 }
+DEV Axis axis_taps(float g, int size) { return axis_taps(g, size, (float)(size - 1)); }
 
 // Tap addresses are 32-bit BYTE offsets from a uniform base (to_framek() guarantees every tensor is below 4 GiB and every
 // index factor below 2^24): the products are v_mad_u32_u24 (full rate; v_mul_lo_u32 is quarter rate) and the loads take
@@ -902,6 +902,28 @@ DEV const float* at_byte(const float* base, unsigned byte_off) {
 DEV void pin_offsets(unsigned (&a)[4]) { asm volatile("" : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3])); }
 DEV void pin_offsets(unsigned (&a)[4], unsigned (&b)[4]) {
     asm volatile("" : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3]), "+v"(b[0]), "+v"(b[1]), "+v"(b[2]), "+v"(b[3]));
+}
+
+// Eight registers that hold one value P in lane half 0 and another, Q, in half 1 become sixteen that hold P and Q in both halves:
+// a copy, then v_permlane32_swap_b32 (see interleave16: ([a.lo, a.hi], [b.lo, b.hi]) -> ([a.lo, b.lo], [a.hi, b.hi])), so p = [P | P]
+// and q = [Q | Q].  The eight copies stand between every register's last write and the swap that reads it, which covers the two
+// wait states the swap needs behind a VALU write of an operand.  All 64 lanes must be active.  The results are tap indices and
+// weights, never MFMA operands.
+DEV void share_halves8(unsigned (&p)[8], unsigned (&q)[8]) {
+    asm("v_mov_b32 %8, %0\n\tv_mov_b32 %9, %1\n\tv_mov_b32 %10, %2\n\tv_mov_b32 %11, %3\n\t"
+        "v_mov_b32 %12, %4\n\tv_mov_b32 %13, %5\n\tv_mov_b32 %14, %6\n\tv_mov_b32 %15, %7\n\t"
+        "v_permlane32_swap_b32 %0, %8\n\tv_permlane32_swap_b32 %1, %9\n\tv_permlane32_swap_b32 %2, %10\n\tv_permlane32_swap_b32 %3, %11\n\t"
+        "v_permlane32_swap_b32 %4, %12\n\tv_permlane32_swap_b32 %5, %13\n\tv_permlane32_swap_b32 %6, %14\n\tv_permlane32_swap_b32 %7, %15"
+        : "+v"(p[0]), "+v"(p[1]), "+v"(p[2]), "+v"(p[3]), "+v"(p[4]), "+v"(p[5]), "+v"(p[6]), "+v"(p[7]),
+          "=&v"(q[0]), "=&v"(q[1]), "=&v"(q[2]), "=&v"(q[3]), "=&v"(q[4]), "=&v"(q[5]), "=&v"(q[6]), "=&v"(q[7]));
+}
+DEV void axis_words(const Axis& a, unsigned* w) {
+    w[0] = a.i0; w[1] = a.i1; w[2] = __builtin_bit_cast(unsigned, a.w0); w[3] = __builtin_bit_cast(unsigned, a.w1);
+}
+DEV Axis axis_of(const unsigned* w) {
+    Axis a;
+    a.i0 = w[0]; a.i1 = w[1]; a.w0 = __builtin_bit_cast(float, w[2]); a.w1 = __builtin_bit_cast(float, w[3]);
+    return a;
 }
 
 // 16 channels of one tap: 8 v_pk_fma_f32 (the tap weight is broadcast by op_sel)
@@ -1143,16 +1165,103 @@ DEV float view_valid(MP M, int ih, int iw, float px, float py, float pz, bool ne
     return (front && inb) ? 1.f : 0.f;
 }
 
+// The eight taps of one view from their axes (4 image texels, 4 x 64 B of the feature map), all loaded before the first is used.
+DEV void batch_taps(const float* __restrict__ img, int iw, const float* __restrict__ fm, int fw, int half,
+                    const Axis& ix, const Axis& iy, const Axis& ax, const Axis& ay, ViewSample& s, float* f) {
+    const unsigned ir0 = __umul24(iy.i0, (unsigned)iw * 16u), ir1 = __umul24(iy.i1, (unsigned)iw * 16u);
+    const unsigned ix0 = ix.i0 * 16u, ix1 = ix.i1 * 16u;
+    const unsigned r0 = __umul24(ay.i0, (unsigned)fw * 128u), r1 = __umul24(ay.i1, (unsigned)fw * 128u);
+    const unsigned x0 = ax.i0 * 128u + (unsigned)half * 64u, x1 = ax.i1 * 128u + (unsigned)half * 64u;
+    // Every tap's byte offset is final, in a register of its own, before the first load issues (pin_offsets): left to the
+    // register allocator, the later taps' address arithmetic lands in registers that the earlier loads are still writing, and
+    // the "one batch" runs as three dependent ones with an s_waitcnt vmcnt between them (tools/isa_gather_waits.py).
+    unsigned io[4] = {ir0 + ix0, ir0 + ix1, ir1 + ix0, ir1 + ix1};
+    unsigned fo[4] = {r0 + x0, r0 + x1, r1 + x0, r1 + x1};
+    pin_offsets(io, fo);
+    __builtin_amdgcn_sched_barrier(0);
+    const f32x4 nw = *reinterpret_cast<const f32x4*>(at_byte(img, io[0]));
+    const f32x4 ne = *reinterpret_cast<const f32x4*>(at_byte(img, io[1]));
+    const f32x4 sw = *reinterpret_cast<const f32x4*>(at_byte(img, io[2]));
+    const f32x4 se = *reinterpret_cast<const f32x4*>(at_byte(img, io[3]));
+    const float fwt[4] = {ax.w0 * ay.w0, ax.w1 * ay.w0, ax.w0 * ay.w1, ax.w1 * ay.w1};
+    f32x4 q[4][4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+        const f32x4* p = reinterpret_cast<const f32x4*>(at_byte(fm, fo[t]));
+#pragma unroll
+        for (int i = 0; i < 4; ++i) q[t][i] = p[i];
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    const float wnw = ix.w0 * iy.w0, wne = ix.w1 * iy.w0, wsw = ix.w0 * iy.w1, wse = ix.w1 * iy.w1;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) s.rgb[c] = fmaf(se[c], wse, fmaf(sw[c], wsw, fmaf(ne[c], wne, nw[c] * wnw)));
+#pragma unroll
+    for (int c = 0; c < 16; ++c) f[c] = 0.f;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+        const f32x2 w2 = {fwt[t], fwt[t]};
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const f32x2 a = __builtin_elementwise_fma(f32x2{q[t][i][0], q[t][i][1]}, w2, f32x2{f[4 * i], f[4 * i + 1]});
+            const f32x2 b = __builtin_elementwise_fma(f32x2{q[t][i][2], q[t][i][3]}, w2, f32x2{f[4 * i + 2], f[4 * i + 3]});
+            f[4 * i] = a[0]; f[4 * i + 1] = a[1]; f[4 * i + 2] = b[0]; f[4 * i + 3] = b[1];
+        }
+    }
+    __builtin_amdgcn_sched_barrier(0);
+}
+
 // Projector.compute for one view (libs/renders/BaseRender.py:301-324,296-299,283-294,352-362):
 // project p, bilinear RGB from imgs[v] (NHWC4) and 16 feature channels from featmaps[v] (NHWC32).
 // How the eight taps are fetched.  WALK: one after the other, each reduced as it arrives (the split forms, whose sample loops
 // have no registers for more).  WALK_PINNED: the same with the image's four offsets final before its first load (the fp32 forms'
 // second look at the images for rgb_in_map).  BATCH: all 20 loads in flight before the first is used, one round trip per view.
 enum class Taps { WALK, WALK_PINNED, BATCH };
-template <Taps TAPS = Taps::WALK, class MP>
+// The per-ray arithmetic of one view divided between the lane halves (a lane is (ray = lane & 31, half = lane >> 5), and both halves
+// of a ray used to run all of it): half 0 takes the x side -- hx, the image's and the feature map's widths -- and half 1
+// the y side, which is the same code on hy and the heights: the half's own quotient, clamp,
+// in-range test, normalised coordinate and its two axis_taps.  share_halves8 then gives both halves both sides, and the in-range
+// verdicts meet in the wavefront's ballot (bit r: x of ray r, bit 32 + r: y).  The same instructions on the same operands as
+// gather_view's own, value by value: the same bits.  Needs all 64 lanes active and the point a function of lane & 31 alone.
+template <class MP>
+DEV float view_axes_halved(MP M, int ih, int iw, int fh, int fw, float px, float py, float pz, bool neg, int half,
+                           Axis& ix, Axis& iy, Axis& ax, Axis& ay) {
+    const float hz = fmaf(M[10], pz, fmaf(M[9], py, M[8] * px)) + M[11];
+    // (both rows from their scalar operands and one select: selecting the row's four operands first costs eight instructions,
+    //  and read through a per-half address they arrive a memory round trip later)
+    const float hx = fmaf(M[2], pz, fmaf(M[1], py, M[0] * px)) + M[3];
+    const float hy = fmaf(M[6], pz, fmaf(M[5], py, M[4] * px)) + M[7];
+    const float hc = half ? hy : hx;
+    float c = hc / hz;
+    c = fminf(fmaxf(c, -1e6f), 1e6f);
+    const bool front = neg ? (hz < 0.f) : (hz > 0.f);
+    const int isz = half ? ih : iw, fsz = half ? fh : fw;
+    const float sm1 = (float)isz - 1.f;
+    const bool inb = (c <= sm1) && (c >= 0.f);
+    const float nc = 2.f * c / sm1 - 1.f;
+    const unsigned long long b = __builtin_amdgcn_ballot_w64(front && inb);
+    const unsigned both = (unsigned)b & (unsigned)(b >> 32);
+    unsigned p[8], q[8];
+    // ((float)isz - 1.f is (float)(isz - 1) to the bit: to_framek() keeps every size below 2^24; one register for both)
+    axis_words(axis_taps(nc, isz, sm1), p);
+    axis_words(axis_taps(nc, fsz), p + 4);
+    share_halves8(p, q);
+    ix = axis_of(p); ax = axis_of(p + 4);
+    iy = axis_of(q); ay = axis_of(q + 4);
+    return __builtin_amdgcn_inverse_ballot_w64(((unsigned long long)both << 32) | both) ? 1.f : 0.f;
+}
+
+template <Taps TAPS = Taps::WALK, bool HALVED = false, class MP>
 DEV ViewSample gather_view(MP M, const float* __restrict__ img, int ih, int iw,
                            const float* __restrict__ fm, int fh, int fw, float px, float py, float pz, bool neg,
                            int half, float* f) {
+    static_assert(!HALVED || TAPS == Taps::BATCH, "the halved per-ray arithmetic feeds the batched taps only");
+    if constexpr (HALVED) {
+        Axis ix, iy, ax, ay;
+        ViewSample s;
+        s.valid = view_axes_halved(M, ih, iw, fh, fw, px, py, pz, neg, half, ix, iy, ax, ay);
+        batch_taps(img, iw, fm, fw, half, ix, iy, ax, ay, s, f);
+        return s;
+    }
     // (K4 P4) bmm [p, 1] (BaseRender.py:314): on the reference's CPU path an sgemm whose micro-kernel accumulates over k = 0..3 with
     // FMAs, k ascending, the last term (x 1) a plain add -- checked bit for bit against torch.bmm; with this order the pixel
     // coordinates, the in-bounds masks and the gathered view features are the reference's own bits (round 3 summed left to
@@ -1173,48 +1282,7 @@ DEV ViewSample gather_view(MP M, const float* __restrict__ img, int ih, int iw,
     // flight and one round trip per view, where the compiler on its own walks the taps one at a time (BATCH: the folded form,
     // which has no matrix work between its two gather phases to cover them).
     if constexpr (TAPS == Taps::BATCH) {
-        const Axis ix = axis_taps(nx, iw), iy = axis_taps(ny, ih);
-        const unsigned ir0 = __umul24(iy.i0, (unsigned)iw * 16u), ir1 = __umul24(iy.i1, (unsigned)iw * 16u);
-        const unsigned ix0 = ix.i0 * 16u, ix1 = ix.i1 * 16u;
-        const Axis ax = axis_taps(nx, fw), ay = axis_taps(ny, fh);
-        const unsigned r0 = __umul24(ay.i0, (unsigned)fw * 128u), r1 = __umul24(ay.i1, (unsigned)fw * 128u);
-        const unsigned x0 = ax.i0 * 128u + (unsigned)half * 64u, x1 = ax.i1 * 128u + (unsigned)half * 64u;
-        // Every tap's byte offset is final, in a register of its own, before the first load issues (pin_offsets): left to the
-        // register allocator, the later taps' address arithmetic lands in registers that the earlier loads are still writing, and
-        // the "one batch" runs as three dependent ones with an s_waitcnt vmcnt between them (tools/isa_gather_waits.py).
-        unsigned io[4] = {ir0 + ix0, ir0 + ix1, ir1 + ix0, ir1 + ix1};
-        unsigned fo[4] = {r0 + x0, r0 + x1, r1 + x0, r1 + x1};
-        pin_offsets(io, fo);
-        __builtin_amdgcn_sched_barrier(0);
-        const f32x4 nw = *reinterpret_cast<const f32x4*>(at_byte(img, io[0]));
-        const f32x4 ne = *reinterpret_cast<const f32x4*>(at_byte(img, io[1]));
-        const f32x4 sw = *reinterpret_cast<const f32x4*>(at_byte(img, io[2]));
-        const f32x4 se = *reinterpret_cast<const f32x4*>(at_byte(img, io[3]));
-        const float fwt[4] = {ax.w0 * ay.w0, ax.w1 * ay.w0, ax.w0 * ay.w1, ax.w1 * ay.w1};
-        f32x4 q[4][4];
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            const f32x4* p = reinterpret_cast<const f32x4*>(at_byte(fm, fo[t]));
-#pragma unroll
-            for (int i = 0; i < 4; ++i) q[t][i] = p[i];
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        const float wnw = ix.w0 * iy.w0, wne = ix.w1 * iy.w0, wsw = ix.w0 * iy.w1, wse = ix.w1 * iy.w1;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) s.rgb[c] = fmaf(se[c], wse, fmaf(sw[c], wsw, fmaf(ne[c], wne, nw[c] * wnw)));
-#pragma unroll
-        for (int c = 0; c < 16; ++c) f[c] = 0.f;
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            const f32x2 w2 = {fwt[t], fwt[t]};
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const f32x2 a = __builtin_elementwise_fma(f32x2{q[t][i][0], q[t][i][1]}, w2, f32x2{f[4 * i], f[4 * i + 1]});
-                const f32x2 b = __builtin_elementwise_fma(f32x2{q[t][i][2], q[t][i][3]}, w2, f32x2{f[4 * i + 2], f[4 * i + 3]});
-                f[4 * i] = a[0]; f[4 * i + 1] = a[1]; f[4 * i + 2] = b[0]; f[4 * i + 3] = b[1];
-            }
-        }
-        __builtin_amdgcn_sched_barrier(0);
+        batch_taps(img, iw, fm, fw, half, axis_taps(nx, iw), axis_taps(ny, ih), axis_taps(nx, fw), axis_taps(ny, fh), s, f);
     } else {
         {   // RGB from the full-resolution image
             const Axis ax = axis_taps(nx, iw), ay = axis_taps(ny, ih);
@@ -1524,13 +1592,16 @@ __global__ void __launch_bounds__(256) compact_list_kernel(const int* __restrict
 // replicated in the group and the arithmetic per ray -- and with it every output bit -- is the same as with P = 1.
 // Projector.compute (:326-363) for the NV views of one sample, in the slot order the form's first colour / density layers take
 // (reference-order form: gpr::ref35, (r, g) (b, 0) (f0, f1) ... (f30, f31)); returns the number of views that see the sample
-template <int FORM>
+// HALVED: the caller's lanes are (ray = lane & 31, half = lane >> 5) with the point a function of the ray alone and all 64 active, so
+// each half computes one side of every view's per-ray arithmetic (view_axes_halved); the fp32 forms' batched taps only.
+template <int FORM, bool HALVED = false>
 DEV float gather_views(const __attribute__((address_space(4))) FrameK& fr, float px, float py, float pz, bool neg, int half,
                        float (&x)[NV][18], float (&vrgb)[NV][3]) {
+    constexpr bool BATCHED = FORM == FORM_F32_FOLD || FORM == FORM_F32;
     float nvalid = 0.f;
 #pragma unroll
     for (int v = 0; v < NV; ++v) {
-        const ViewSample s = gather_view<(FORM == FORM_F32_FOLD || FORM == FORM_F32) ? Taps::BATCH : Taps::WALK>(fr.proj[v], fr.imgs + (size_t)v * fr.img_h * fr.img_w * 4, fr.img_h, fr.img_w,
+        const ViewSample s = gather_view<BATCHED ? Taps::BATCH : Taps::WALK, BATCHED && HALVED>(fr.proj[v], fr.imgs + (size_t)v * fr.img_h * fr.img_w * 4, fr.img_h, fr.img_w,
                                          fr.featmaps + (size_t)v * fr.feat_h * fr.feat_w * 32, fr.feat_h, fr.feat_w,
                                          px, py, pz, neg, half, x[v]
                                          );
@@ -1711,7 +1782,8 @@ DEV bool render_tile(float* lds, const int lane, const long tile, const int seg,
                 sample_point(__shfl(ox, r), __shfl(oy, r), __shfl(oz, r), __shfl(dx, r), __shfl(dy, r), __shfl(dz, r), __shfl(near, r), __shfl(far, r),
                              flip ? (S - 1 - kk) : kk, S, step, zq, qx_, qy_, qz_);
                 float xq[NV][18], vq[NV][3], cq[3];
-                gather_views<FORM>(kb->fr, qx_, qy_, qz_, neg, half, xq, vq);
+                // (halved: the queue flush is taken by the whole wavefront, and entry n = lane & 31 is the same in both halves)
+                gather_views<FORM, true>(kb->fr, qx_, qy_, qz_, neg, half, xq, vq);
                 STAMP(st, 14);
                 if constexpr (SPLIT) {
                     Frag mvf[6];
@@ -1906,7 +1978,8 @@ DEV bool render_tile(float* lds, const int lane, const long tile, const int seg,
         // Projector.compute (:326-363)
         // (deferred form: every gather of the step ahead of its matrix work -- one memory phase, one compute phase -- was tried:
         //  105 spilled registers, 10.35 -> 12.39 ms)
-        nvalid = gather_views<FORM>(fr, px, py, pz, neg, half, x, vrgb);
+        // (halved: every exit above is the wavefront's as a whole, so all 64 lanes are here, and p is the ray's: lane & 31 alone, P > 1 included)
+        nvalid = gather_views<FORM, true>(fr, px, py, pz, neg, half, x, vrgb);
         const bool two_views = nvalid > 1.f && keep;    // pixel_mask (:139); culled samples never count
         if constexpr (P == 1) { if (two_views && !dead) ++n_two; }
 
@@ -2181,7 +2254,8 @@ DEV void colour_entries(float* lds, const int lane, const bool valid, const uint
     float zq, qx_, qy_, qz_;
     sample_point(r0[0], r0[1], r0[2], r0[3], r1[0], r1[1], r1[2], r1[3], flip ? (S - 1 - kk) : kk, S, step, zq, qx_, qy_, qz_);
     float xq[NV][18], vq[NV][3], cq[3], mvq[36];
-    gather_views<FORM>(kb->fr, qx_, qy_, qz_, neg, half, xq, vq);
+    // (halved: called by whole wavefronts only; the entry is read by lane & 31, an invalid lane computes on ray 0 in both halves)
+    gather_views<FORM, true>(kb->fr, qx_, qy_, qz_, neg, half, xq, vq);
     Stamps st;
     if constexpr (FORM == FORM_F32) { mean_var_ref(xq, mvq); mlp_colour_ref(lds, lane, xq, mvq, cq, st); }
     else { mean_var(xq, mvq); mlp_colour(lds, lane, xq, mvq, cq, st); }
