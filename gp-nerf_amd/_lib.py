@@ -128,6 +128,14 @@ CUBE_KEEP, CUBE_FILL = 1, 2
 CUBE_STATS = ("components", "inside_points", "components_kept", "inside_points_kept", "cavities_filled", "points_filled")
 # gpnerf_image_metrics' slot (include/gpnerf_hip.h GPNERF_METRICS_*)
 METRICS_MSE, METRICS_SSIM, METRICS_X, METRICS_Y, METRICS_W, METRICS_H, METRICS_POPULATION, METRICS_STATUS, METRICS_DOUBLES = range(9)
+# the mesh grid's header words, the sampler's status and gpnerf_distance_stats' slot (include/gpnerf_hip.h GPNERF_GRID_* / _SAMPLE_* / _DIST_*)
+GRID_OK, GRID_OVERFLOW, GRID_BUILDING = range(3)
+GRID_HDR = {"magic": 0, "status": 1, "skipped": 2, "valid": 3, "cells": 4, "n_cells": 7, "cell_cap": 8, "entry_cap": 9, "needed": 10,
+            "lo": 12, "size": 15, "inv": 18}
+GRID_HDR_INTS = 64
+SAMPLE_OK, SAMPLE_NO_AREA = range(2)
+DIST_FINITE, DIST_INF, DIST_NAN, DIST_MEAN, DIST_MEAN_SQ, DIST_MAX, DIST_WITHIN = range(7)
+DIST_MAX_THRESHOLDS, DIST_DOUBLES = 4, 10
 
 # every symbol include/gpnerf_hip.h declares: (restype, argtypes)
 SYMBOLS = {
@@ -223,6 +231,14 @@ SYMBOLS = {
     "gpnerf_metrics_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
     "gpnerf_image_metrics": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_size_t,
                                        C.c_void_p, C.c_void_p]),
+    "gpnerf_mesh_grid_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int64]),
+    "gpnerf_mesh_grid_build": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "gpnerf_mesh_distance": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_float, C.c_void_p,
+                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gpnerf_mesh_sample_workspace_bytes": (C.c_size_t, [C.c_int64]),
+    "gpnerf_mesh_sample_surface": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_uint32, C.c_void_p, C.c_size_t,
+                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gpnerf_distance_stats": (C.c_int, [C.c_void_p, C.c_int64, FP, C.c_int32, C.c_void_p, C.c_void_p]),
     "gpnerf_head_layout": (C.c_int, [C.POINTER(C.c_int32)]),
     "gpnerf_strerror": (C.c_char_p, [C.c_int]),
     "gpnerf_rays_per_tile": (C.c_int32, []),

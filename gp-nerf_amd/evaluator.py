@@ -15,7 +15,9 @@ Image writing (cfg.test.save_imgs) is I/O and out of scope.
 pinned to the reference's own loop over three frames (tests/golden/loop_demo_3frames.npz).
 
 `MeshEvaluator` mirrors libs/evaluators/if_nerf_mesh.py for a geometry-mode renderer (use_rgbhead False); the loop takes it
-through `evaluate_loop(evaluator=...)` and otherwise constructs the image evaluator, as the reference's loop always does.
+through `evaluate_loop(evaluator=...)` and otherwise constructs the image evaluator, as the reference's loop always does.  Given a
+`gt_mesh` per frame it also computes the geometry metrics (P2S, Chamfer, normal consistency, F-score) on the device
+(frame.mesh_metrics, csrc/gpnerf_meshdist.hip).
 
 `DeviceEvaluator` (opt-in: `evaluate_loop(device_metrics=True)` or GPNERF_DEVICE_METRICS=1) computes the same three numbers with
 gpnerf_image_metrics (csrc/gpnerf_metrics.hip): four kernel launches per frame into a device slot, no host synchronisation in
@@ -226,17 +228,38 @@ class DeviceEvaluator(Evaluator):
 class MeshEvaluator:
     """The geometry mode's evaluator (libs/evaluators/if_nerf_mesh.py): `evaluate` saves the lattice points whose alpha is above
     `mesh_th` to `<result_path>/pts/<frame_index>.npy`, `visualize` exports the mesh to `<result_path>/mesh/<frame_index>.ply`
-    (`..._cam<c>.ply` when the batch has `cam_ind`), `summarize()` returns {} (the reference evaluates no mesh metric).  `output` is
-    what Renderer.render returns with use_rgbhead False.  The directories are made with os.makedirs (the reference shells out to
-    mkdir -p and announces them through termcolor).  export_mesh (not in the reference, whose loop never calls visualize):
-    `evaluate` also calls `visualize`, so that an evaluation loop leaves the meshes behind."""
+    (`..._cam<c>.ply` when the batch has `cam_ind`).  `output` is what Renderer.render returns with use_rgbhead False.  The
+    directories are made with os.makedirs (the reference shells out to mkdir -p and announces them through termcolor).
+    export_mesh (not in the reference, whose loop never calls visualize): `evaluate` also calls `visualize`, so that an evaluation
+    loop leaves the meshes behind.
+    Metrics (not in the reference, which has `# TODO evaluate mesh` at if_nerf_mesh.py:32): a batch with `gt_mesh` -- a mesh.Mesh or
+    a (vertices, faces) pair in the frame of the lattice axes -- makes `evaluate` enqueue frame.mesh_metrics of the frame's mesh
+    against it (no host read; the predicted mesh goes through `to_lattice_frame(output["axes"], PAD)` when the output has `axes`
+    and is taken as it is otherwise) and keep the slots.  `summarize()` reads all slots in one copy and returns the per-key means
+    over the frames, with the per-frame lists under "per_frame", saves those lists as `<result_path>/mesh_metrics.npy` (next to
+    pts/) and resets.  With no `gt_mesh` ever seen it returns {} and writes nothing, as the reference does.
+    metric_samples: surface samples per mesh and direction; metric_thresholds: the F-score distances, in the meshes' unit (metres
+    for the project's scenes: 5 mm, 1 cm, 2 cm); metric_max_dist: gpnerf_mesh_distance's max_dist (inf: exact everywhere);
+    metric_cell_cap, metric_entry_cap: the grids' capacities (None: frame.mesh_grid_caps).  `evaluate` does not read the grids'
+    status, so a grid that overflows its entry capacity shows at `summarize()`, whose error says how to find the capacity to pass here."""
     PAD = 10                              # if_nerf_mesh.py:20, the np.pad(cube, 10) of BaseRender.py:269
 
-    def __init__(self, result_path, mesh_th, export_mesh=False):
+    def __init__(self, result_path, mesh_th, export_mesh=False, metric_samples=100000, metric_thresholds=(0.005, 0.01, 0.02),
+                 metric_max_dist=float("inf"), metric_device=None, metric_cell_cap=None, metric_entry_cap=None):
         self.mesh_th = mesh_th
         self.export_mesh = bool(export_mesh)
+        self.result_path = result_path
         self.vis_result_dir = os.path.join(result_path, "mesh")
         self.pts_result_dir = os.path.join(result_path, "pts")
+        self.metric_samples, self.metric_thresholds = int(metric_samples), tuple(float(t) for t in metric_thresholds)
+        self.metric_max_dist, self.metric_device = float(metric_max_dist), metric_device
+        self.metric_cell_cap, self.metric_entry_cap = metric_cell_cap, metric_entry_cap
+        self._slots, self._frames = [], []
+
+    @property
+    def has_mesh_metrics(self):
+        """True once a frame with `gt_mesh` has been evaluated and not yet summarized (evaluate_loop asks)"""
+        return bool(self._slots)
 
     @staticmethod
     def _scalar(v):
@@ -257,9 +280,35 @@ class MeshEvaluator:
         np.save(os.path.join(self.pts_result_dir, f"{self._scalar(batch['frame_index'])}.npy"), pts)
         if self.export_mesh:
             self.visualize(output, batch)
+        if batch.get("gt_mesh") is not None:
+            from . import frame as F
+            pred = output["mesh"]
+            if "axes" in output:
+                pred = pred.to_lattice_frame(output["axes"], self.PAD)
+            self._slots.append(F.mesh_metrics(pred, batch["gt_mesh"], n_samples=self.metric_samples, thresholds=self.metric_thresholds,
+                                              max_dist=self.metric_max_dist, device=self.metric_device, cell_cap=self.metric_cell_cap,
+                                              entry_cap=self.metric_entry_cap))
+            self._frames.append(self._scalar(batch["frame_index"]))
 
     def summarize(self):
-        return {}
+        if not self._slots:
+            return {}
+        from . import frame as F
+        host = torch.stack(self._slots).cpu().numpy()         # the one read: it waits for the frames' kernels
+        rows = [F.read_mesh_metrics(s, self.metric_thresholds) for s in host]
+        per_frame = {k: [r[k] for r in rows] for k in rows[0]}
+        per_frame["frame_index"] = list(self._frames)
+        metrics = {k: float(np.mean(v)) for k, v in per_frame.items() if k != "frame_index"}
+        table = np.zeros(len(rows), dtype=[(k, "i8" if k == "frame_index" else "f8") for k in ["frame_index"] + list(rows[0])])
+        for k in table.dtype.names:
+            table[k] = per_frame[k]
+        os.makedirs(self.result_path, exist_ok=True)
+        np.save(os.path.join(self.result_path, "mesh_metrics.npy"), table)      # a structured array: one row per frame, a field per key
+        for k in ("accuracy", "completeness", "chamfer", "normal_consistency"):
+            print(f"{k}: {metrics[k]}")
+        metrics["per_frame"] = per_frame
+        self._slots, self._frames = [], []
+        return metrics
 
     def visualize(self, output, batch):
         os.makedirs(self.vis_result_dir, exist_ok=True)
@@ -277,9 +326,9 @@ def evaluate_loop(render, eval_loader, cfg, device=None, quiet=False, pipeline=N
     """`Trainer.evaluate` (libs/trainers/BaseTrainer.py:255-280) without its image writing: for every batch of `eval_loader`
     move it to `device` (`_read_inputs`, :89-97), `ret = render.render(batch)` (the reference calls `.module.render` on its
     DataParallel wrapper; a wrapped model is unwrapped here too), `Evaluator.evaluate(ret, batch)`, `total_time += ret["rtime"]`;
-    then `summarize()` when the head renders colour.  Returns {"count", "total_time", "avg_time", "metrics" (summarize()'s dict or
-    None), "mse", "psnr", "ssim" (the per-frame lists), "wall_time" (the loop's own clock)} -- the reference prints the average and
-    returns nothing.
+    then `summarize()` when the head renders colour -- or when a MeshEvaluator has been given a `gt_mesh` (its `has_mesh_metrics`).
+    Returns {"count", "total_time", "avg_time", "metrics" (summarize()'s dict or None), "mse", "psnr", "ssim" (the per-frame
+    lists), "wall_time" (the loop's own clock)} -- the reference prints the average and returns nothing.
     pipeline (not in the reference, whose loop is strictly serial): frame t + 1 is fetched, moved to the device and PREFETCHED
     (Renderer.prefetch: encoder graph, volume builder, frame glue on a second stream) right after frame t's per-ray kernel has been
     enqueued, so the device goes from one frame's per-ray kernel straight into the next frame's producers while the host evaluates
@@ -304,11 +353,12 @@ def evaluate_loop(render, eval_loader, cfg, device=None, quiet=False, pipeline=N
     def move(v):
         if device is None:
             return v
+        to = lambda b: b.to(device) if hasattr(b, "to") else b   # (a batch's gt_mesh -- a mesh.Mesh or numpy arrays -- stays; mesh_metrics uploads it)
         if isinstance(v, (list, tuple)):
-            return [b.to(device) for b in v]
+            return [to(b) for b in v]
         if isinstance(v, dict):
-            return {k: b.to(device) for k, b in v.items()}
-        return v.to(device)
+            return {k: to(b) for k, b in v.items()}
+        return to(v)
 
     import time as _time
     t_loop = _time.time()
@@ -348,13 +398,15 @@ def evaluate_loop(render, eval_loader, cfg, device=None, quiet=False, pipeline=N
                 val = nxt
     per_frame = {k: list(getattr(evaluator, k, ())) for k in ("mse", "psnr", "ssim")}
     wall = _time.time() - t_loop                              # (behind the lists: the device evaluator's one read belongs to the loop)
-    if quiet:                                                 # (summarize() prints its three means, as the reference's does)
+    # the reference summarizes when the head renders colour; a MeshEvaluator that has seen a gt_mesh has numbers too
+    wants = cfg.head.rgb.use_rgbhead or getattr(evaluator, "has_mesh_metrics", False)
+    if quiet:                                                 # (summarize() prints its means, as the reference's does)
         import contextlib
         import io
         with contextlib.redirect_stdout(io.StringIO()):
-            metrics = evaluator.summarize() if cfg.head.rgb.use_rgbhead else None
+            metrics = evaluator.summarize() if wants else None
     else:
-        metrics = evaluator.summarize() if cfg.head.rgb.use_rgbhead else None
+        metrics = evaluator.summarize() if wants else None
     if not quiet:
         print(f"avg total render time: {total_time / max(count, 1)}s per sample")
     return dict(count=count, total_time=total_time, avg_time=total_time / max(count, 1), metrics=metrics, wall_time=wall, **per_frame)

@@ -962,3 +962,219 @@ def extract_mesh(frame, voxel_size, bounds_min, Rh, Th, neg_ray=False, iso=1.0 /
     if normals:
         res["normals"] = mesh_normals(surface, res["vertices"], step=np.asarray(vs, dtype=np.float64).ravel()[:3])
     return res
+
+
+# ---- evaluating a mesh against another (csrc/gpnerf_meshdist.hip)
+
+def _mesh_tensors(vertices, faces, what):
+    for t, name in ((vertices, "vertices"), (faces, "faces")):
+        if not isinstance(t, torch.Tensor):
+            raise L.GpnerfError(f"{what}: {name} must be a device tensor (mesh_to_device uploads a Mesh)")
+        _require_gpu(t, f"{what}: {name}")
+    if vertices.dtype != torch.float32 or vertices.dim() != 2 or vertices.shape[1] != 3 or not vertices.is_contiguous():
+        raise L.GpnerfError(f"{what}: expected contiguous float32 vertices [n,3], got {vertices.dtype} {tuple(vertices.shape)}")
+    if faces.dtype != torch.int32 or faces.dim() != 2 or faces.shape[1] != 3 or not faces.is_contiguous() or faces.shape[0] < 1:
+        raise L.GpnerfError(f"{what}: expected contiguous int32 faces [m,3], m >= 1, got {faces.dtype} {tuple(faces.shape)}")
+    if faces.device != vertices.device:
+        raise L.GpnerfError(f"{what}: vertices and faces are on different devices")
+    return int(vertices.shape[0]), int(faces.shape[0])
+
+
+def _points(t, what, like=None):
+    _require_gpu(t, what)
+    if t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] != 3 or not t.is_contiguous():
+        raise L.GpnerfError(f"{what}: expected a contiguous float32 [n,3] tensor, got {t.dtype} {tuple(t.shape)}")
+    if like is not None and t.shape != like.shape:
+        raise L.GpnerfError(f"{what}: shape {tuple(t.shape)}, expected {tuple(like.shape)}")
+    return t
+
+
+def mesh_to_device(mesh, device):
+    """(vertices float32 [n,3], faces int32 [m,3]) on `device` from a mesh.Mesh, a (vertices, faces) pair of arrays or tensors"""
+    v, f = (mesh.vertices, mesh.faces) if hasattr(mesh, "vertices") else mesh
+    as_t = lambda a, dt: (a.detach() if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a))).to(device=device, dtype=dt)
+    return as_t(v, torch.float32).reshape(-1, 3).contiguous(), as_t(f, torch.int32).reshape(-1, 3).contiguous()
+
+
+def mesh_grid_caps(n_faces):
+    """The default capacities of build_mesh_grid, from n_faces alone: cell_cap = n_faces clamped to [64, 2^22] -- about one cell per
+    face, so a marching-cubes triangle (no longer than a voxel's diagonal) overlaps 1 - 8 cells and a cell's run stays a few entries
+    long; entry_cap = 8 n_faces + 4 cell_cap -- eight cells per face, plus room for the few large faces of a hand-made mesh.  A
+    mesh whose faces are large against its cells (one face across the whole box lands in every cell) can need more: the build reports
+    the count and build_mesh_grid retries with it."""
+    cell_cap = int(min(max(n_faces, 64), 1 << 22))
+    return cell_cap, 8 * int(n_faces) + 4 * cell_cap
+
+
+class MeshGrid:
+    """gpnerf_mesh_grid_build's workspace with the mesh it was built for.  `header()` reads the header words (one device-to-host
+    copy): status, skipped, valid, cells [3], n_cells, cell_cap, entry_cap, needed, lo / size / inv [3] float32."""
+
+    def __init__(self, vertices, faces, workspace, cell_cap, entry_cap):
+        self.vertices, self.faces, self.workspace, self.cell_cap, self.entry_cap = vertices, faces, workspace, cell_cap, entry_cap
+
+    def header(self):
+        w = self.workspace[:4 * L.GRID_HDR_INTS].cpu().numpy().view(np.int32)
+        H = L.GRID_HDR
+        res = {k: int(w[H[k]]) for k in ("status", "skipped", "valid", "n_cells", "cell_cap", "entry_cap")}
+        res["cells"] = [int(v) for v in w[H["cells"]:H["cells"] + 3]]
+        res["needed"] = int(w[H["needed"]:H["needed"] + 2].view(np.int64)[0])
+        for k in ("lo", "size", "inv"):
+            res[k] = w[H[k]:H[k] + 3].view(np.float32).copy()
+        return res
+
+
+def build_mesh_grid(vertices, faces, cell_cap=None, entry_cap=None, check=True):
+    """gpnerf_mesh_grid_build on a device mesh (float32 [n,3], int32 [m,3]) -> MeshGrid.  Capacities default by mesh_grid_caps.
+    check (default): the header's status is read -- the call's one host read -- and on overflow the build runs once more with the
+    count the header reports (already in that read); a second overflow raises.  check=False enqueues only: an overflowed grid then
+    makes every distance NaN, which read_mesh_metrics reports."""
+    lib = L.lib()
+    nv, nf = _mesh_tensors(vertices, faces, "build_mesh_grid")
+    d_cell, d_entry = mesh_grid_caps(nf)
+    cell_cap, entry_cap = int(cell_cap or d_cell), int(entry_cap or d_entry)
+    dev = vertices.device
+    for attempt in (0, 1):
+        nbytes = int(lib.gpnerf_mesh_grid_workspace_bytes(nf, cell_cap, entry_cap))
+        if nbytes <= 0:
+            raise L.GpnerfError(f"build_mesh_grid: refused ({nf} faces, cell_cap {cell_cap}, entry_cap {entry_cap})")
+        ws = torch.empty((nbytes,), device=dev, dtype=torch.uint8)
+        L.check(lib.gpnerf_mesh_grid_build(vertices.data_ptr() or ws.data_ptr(), nv, faces.data_ptr(), nf, cell_cap, entry_cap, ws.data_ptr(),
+                                           ws.numel(), _stream_ptr(dev)), "gpnerf_mesh_grid_build")
+        grid = MeshGrid(vertices, faces, ws, cell_cap, entry_cap)
+        if not check:
+            return grid
+        h = grid.header()
+        if h["status"] == L.GRID_OK:
+            return grid
+        if attempt or h["status"] != L.GRID_OVERFLOW:
+            raise L.GpnerfError(f"build_mesh_grid: status {h['status']}, {h['needed']} entries needed, capacity {entry_cap}")
+        entry_cap = h["needed"]
+
+
+def point_mesh_distance(points, vertices=None, faces=None, grid=None, max_dist=float("inf"), query_normals=None, want_closest=False):
+    """gpnerf_mesh_distance: for device float32 points [n,3] the exact distance to the mesh, the nearest face (lowest index among
+    equal distances), optionally the nearest point and |n_q . n_f| -> {"dist" [n], "face" int32 [n], "closest" [n,3], "cosine" [n]}.
+    grid: a MeshGrid (its mesh is used); without one, `vertices` and `faces` go through the brute-force form.  Nothing is read back."""
+    lib = L.lib()
+    if grid is not None:
+        vertices, faces = grid.vertices, grid.faces
+    nv, nf = _mesh_tensors(vertices, faces, "point_mesh_distance")
+    points = _points(points, "point_mesh_distance: points")
+    if points.device != vertices.device:
+        raise L.GpnerfError("point_mesh_distance: points and mesh are on different devices")
+    if query_normals is not None:
+        query_normals = _points(query_normals, "point_mesh_distance: query_normals", like=points)
+    n, dev = int(points.shape[0]), points.device
+    res = {"dist": torch.empty((n,), device=dev, dtype=torch.float32), "face": torch.empty((n,), device=dev, dtype=torch.int32)}
+    if want_closest:
+        res["closest"] = torch.empty((n, 3), device=dev, dtype=torch.float32)
+    if query_normals is not None:
+        res["cosine"] = torch.empty((n,), device=dev, dtype=torch.float32)
+    ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None
+    L.check(lib.gpnerf_mesh_distance(ptr(points), n, vertices.data_ptr() or faces.data_ptr(), nv, faces.data_ptr(), nf,
+                                     grid.workspace.data_ptr() if grid is not None else None, float(max_dist),
+                                     (query_normals.data_ptr() or faces.data_ptr()) if query_normals is not None else None, ptr(res["dist"]),
+                                     ptr(res["face"]), ptr(res.get("closest")),
+                                     (res["cosine"].data_ptr() or faces.data_ptr()) if query_normals is not None else None,
+                                     _stream_ptr(dev)), "gpnerf_mesh_distance")
+    return res
+
+
+def sample_surface(vertices, faces, n_samples, seed=0, want_face=True, want_normal=True):
+    """gpnerf_mesh_sample_surface: n_samples deterministic, stratified, area-weighted points on a device mesh ->
+    {"points" [n,3], "face" int32 [n], "normal" [n,3], "workspace"} (the workspace's first int32 is the status: 1 when the mesh has
+    no area, every point NaN then).  Nothing is read back."""
+    lib = L.lib()
+    nv, nf = _mesh_tensors(vertices, faces, "sample_surface")
+    n, dev = int(n_samples), vertices.device
+    nbytes = int(lib.gpnerf_mesh_sample_workspace_bytes(nf))
+    if nbytes <= 0 or n < 0:
+        raise L.GpnerfError(f"sample_surface: refused ({nf} faces, {n} samples)")
+    ws = torch.empty((nbytes,), device=dev, dtype=torch.uint8)
+    res = {"points": torch.empty((n, 3), device=dev, dtype=torch.float32), "workspace": ws}
+    if want_face:
+        res["face"] = torch.empty((n,), device=dev, dtype=torch.int32)
+    if want_normal:
+        res["normal"] = torch.empty((n, 3), device=dev, dtype=torch.float32)
+    ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None
+    L.check(lib.gpnerf_mesh_sample_surface(vertices.data_ptr() or ws.data_ptr(), nv, faces.data_ptr(), nf, n, int(seed) & 0xffffffff, ws.data_ptr(),
+                                           ws.numel(), ptr(res["points"]), ptr(res.get("face")), ptr(res.get("normal")), _stream_ptr(dev)),
+            "gpnerf_mesh_sample_surface")
+    return res
+
+
+def distance_stats(values, thresholds=(), out=None):
+    """gpnerf_distance_stats: one slot (float64 [_lib.DIST_DOUBLES], device) from a device float32 list; out: a slot to write into"""
+    lib = L.lib()
+    _require_gpu(values, "distance_stats: values")
+    if values.dtype != torch.float32 or not values.is_contiguous():
+        raise L.GpnerfError(f"distance_stats: expected a contiguous float32 tensor, got {values.dtype}")
+    th = [float(t) for t in thresholds]
+    if len(th) > L.DIST_MAX_THRESHOLDS:
+        raise L.GpnerfError(f"distance_stats: at most {L.DIST_MAX_THRESHOLDS} thresholds")
+    if out is None:
+        out = torch.empty((L.DIST_DOUBLES,), device=values.device, dtype=torch.float64)
+    n = values.numel()
+    L.check(lib.gpnerf_distance_stats(values.data_ptr() if n else None, n, (C.c_float * len(th))(*th) if th else None, len(th), out.data_ptr(),
+                                      _stream_ptr(values.device)), "gpnerf_distance_stats")
+    return out
+
+
+MESH_METRIC_ROWS = ("pred_to_gt", "gt_to_pred", "cos_pred_to_gt", "cos_gt_to_pred")
+
+
+def mesh_metrics(pred, gt, n_samples=100000, thresholds=(0.005, 0.01, 0.02), seed=0, max_dist=float("inf"), device=None, cell_cap=None,
+                 entry_cap=None):
+    """The geometry metrics of a predicted mesh against a ground-truth one, enqueued on the device without a host read:
+    n_samples stratified surface samples of each (sample_surface; seeds `seed` and `seed + 1`), the exact distance of each sample
+    to the OTHER mesh with the cosine between the sample's face normal and the nearest face's (point_mesh_distance through a grid
+    built with check=False), and the four reductions (distance_stats).  pred, gt: mesh.Mesh, or (vertices, faces) arrays / tensors,
+    in the same frame and unit; device: where to compute (default: the tensors' device, else cuda:0).
+    Returns float64 [4, _lib.DIST_DOUBLES] on the device, rows MESH_METRIC_ROWS; read_mesh_metrics turns it into a dict."""
+    if device is None:
+        v = pred[0] if isinstance(pred, (tuple, list)) else None
+        device = v.device if isinstance(v, torch.Tensor) and v.is_cuda else torch.device("cuda:0")
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise L.GpnerfError(f"mesh_metrics computes on the GPU (got {device}); the HIP path has no CPU fallback")
+    th = tuple(float(t) for t in thresholds)
+    pv, pf = mesh_to_device(pred, device)
+    gv, gf = mesh_to_device(gt, device)
+    slots = torch.empty((4, L.DIST_DOUBLES), device=device, dtype=torch.float64)
+    sp = sample_surface(pv, pf, n_samples, seed=seed, want_face=False)
+    sg = sample_surface(gv, gf, n_samples, seed=seed + 1, want_face=False)
+    g_gt = build_mesh_grid(gv, gf, cell_cap, entry_cap, check=False)
+    g_pred = build_mesh_grid(pv, pf, cell_cap, entry_cap, check=False)
+    a = point_mesh_distance(sp["points"], grid=g_gt, max_dist=max_dist, query_normals=sp["normal"])
+    b = point_mesh_distance(sg["points"], grid=g_pred, max_dist=max_dist, query_normals=sg["normal"])
+    distance_stats(a["dist"], th, out=slots[0])
+    distance_stats(b["dist"], th, out=slots[1])
+    distance_stats(a["cosine"], (), out=slots[2])
+    distance_stats(b["cosine"], (), out=slots[3])
+    return slots
+
+
+def read_mesh_metrics(slots, thresholds=(0.005, 0.01, 0.02)):
+    """mesh_metrics' slots (one [4, DIST_DOUBLES] tensor or array) -> dict, in the meshes' own unit: accuracy (mean distance pred ->
+    gt, the usual P2S), completeness (gt -> pred), chamfer (half their sum), normal_consistency (the mean of the two cosine means),
+    per threshold t precision@t, recall@t (the fractions within t) and fscore@t (their harmonic mean, 0 when both are 0),
+    accuracy_max, completeness_max, and the counts n_pred / n_gt (finite), beyond_pred / beyond_gt (past max_dist), nan_pred / nan_gt.
+    Raises when a direction has nothing but NaN: its grid overflowed (pass entry_cap) or the sampled mesh has no valid face with area."""
+    s = np.asarray(slots.detach().cpu() if isinstance(slots, torch.Tensor) else slots, dtype=np.float64).reshape(4, L.DIST_DOUBLES)
+    for row, name in ((0, "pred -> gt"), (1, "gt -> pred")):
+        if s[row, L.DIST_NAN] > 0 and s[row, L.DIST_FINITE] + s[row, L.DIST_INF] == 0:
+            raise L.GpnerfError(f"mesh_metrics: every distance {name} is NaN: either the grid of the mesh measured against overflowed its "
+                                "entry capacity (build_mesh_grid(vertices, faces).entry_cap is a capacity that fits: pass it as entry_cap), "
+                                "or the sampled mesh has no valid face with a positive area")
+    res = {"accuracy": float(s[0, L.DIST_MEAN]), "completeness": float(s[1, L.DIST_MEAN])}
+    res["chamfer"] = 0.5 * (res["accuracy"] + res["completeness"])
+    res["normal_consistency"] = 0.5 * float(s[2, L.DIST_MEAN] + s[3, L.DIST_MEAN])
+    for k, t in enumerate(thresholds):
+        p, r = float(s[0, L.DIST_WITHIN + k]), float(s[1, L.DIST_WITHIN + k])
+        res[f"precision@{t:g}"], res[f"recall@{t:g}"] = p, r
+        res[f"fscore@{t:g}"] = 2.0 * p * r / (p + r) if p + r > 0 else 0.0
+    res["accuracy_max"], res["completeness_max"] = float(s[0, L.DIST_MAX]), float(s[1, L.DIST_MAX])
+    for row, name in ((0, "pred"), (1, "gt")):
+        res[f"n_{name}"], res[f"beyond_{name}"], res[f"nan_{name}"] = (int(s[row, k]) for k in (L.DIST_FINITE, L.DIST_INF, L.DIST_NAN))
+    return res

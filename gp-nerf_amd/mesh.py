@@ -147,6 +147,109 @@ class Mesh:
                 f.write(head + body)
 
 
+    def to_lattice_frame(self, axes, pad):
+        """The mesh in the coordinates of the lattice axes (the frame a scan is given in) from marching-cubes vertices in index units of
+        the padded cube: per axis axes[a][0] + (v[a] - pad) * step[a], step[a] = (axes[a][-1] - axes[a][0]) / (len(axes[a]) - 1), all
+        in float64 on the host (an axis of one point has step 1).  A new Mesh: faces and colours carried over, normals -- gradients,
+        which scale with the inverse step -- divided by the step and renormalised (a zero normal stays zero)."""
+        ax = [np.asarray(a.detach().cpu() if hasattr(a, "detach") else a, dtype=np.float64).reshape(-1) for a in axes]
+        if len(ax) != 3 or any(len(a) < 1 for a in ax):
+            raise ValueError("to_lattice_frame: three non-empty axes expected")
+        lo = np.array([a[0] for a in ax])
+        step = np.array([(a[-1] - a[0]) / (len(a) - 1) if len(a) > 1 else 1.0 for a in ax])
+        verts = lo + (self.vertices - float(pad)) * step
+        normals = None
+        if self.vertex_normals is not None:
+            n = self.vertex_normals.astype(np.float64) / step
+            length = np.sqrt((n * n).sum(axis=1, keepdims=True))
+            normals = np.where(length > 0, n / np.where(length > 0, length, 1.0), 0.0).astype(np.float32)
+        return Mesh(verts, self.faces.copy(), None if self.vertex_colors is None else self.vertex_colors.copy(), normals)
+
+
 def colour_bytes(c):
     """float colours in [0, 1] -> uint8: clip(rint(255 c), 0, 255), in float32"""
     return np.clip(np.rint(np.float32(255) * np.asarray(c, dtype=np.float32)), 0, 255).astype(np.uint8)
+
+
+_PLY_TYPES = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short": "<i2", "int16": "<i2", "ushort": "<u2", "uint16": "<u2",
+              "int": "<i4", "int32": "<i4", "uint": "<u4", "uint32": "<u4", "float": "<f4", "float32": "<f4", "double": "<f8", "float64": "<f8"}
+
+
+def _load_ply(data):
+    end = data.find(b"end_header\n")
+    if end < 0:
+        raise ValueError("PLY: no end_header")
+    lines = data[:end].decode("ascii").split("\n")
+    if lines[0].strip() != "ply" or lines[1].split() != ["format", "binary_little_endian", "1.0"]:
+        raise ValueError("PLY: only binary_little_endian 1.0 is read (what Mesh.export writes)")
+    elements = []
+    for line in lines[2:]:
+        w = line.split()
+        if not w or w[0] in ("comment", "obj_info"):
+            continue
+        if w[0] == "element":
+            elements.append((w[1], int(w[2]), []))
+        elif w[0] == "property":
+            elements[-1][2].append(w[1:])
+        else:
+            raise ValueError(f"PLY: unexpected header line {line!r}")
+    if [e[0] for e in elements] != ["vertex", "face"]:
+        raise ValueError("PLY: expected the elements vertex and face, in that order")
+    (_, nv, vprops), (_, nf, fprops) = elements
+    if any(p[0] == "list" for p in vprops):
+        raise ValueError("PLY: a list property on the vertices")
+    vtype = np.dtype([(p[1], _PLY_TYPES[p[0]]) for p in vprops])
+    pos = end + len(b"end_header\n")
+    v = np.frombuffer(data, dtype=vtype, count=nv, offset=pos)
+    pos += nv * vtype.itemsize
+    names = vtype.names
+    if not all(k in names for k in "xyz"):
+        raise ValueError("PLY: vertices without x, y, z")
+    verts = np.stack([v[k].astype(np.float64) for k in "xyz"], axis=1)
+    normals = np.stack([v[k] for k in ("nx", "ny", "nz")], axis=1).astype(np.float32) if all(k in names for k in ("nx", "ny", "nz")) else None
+    colours = None
+    if all(k in names for k in ("red", "green", "blue")):
+        colours = np.stack([v[k] for k in ("red", "green", "blue")], axis=1).astype(np.float32) / np.float32(255)
+    if len(fprops) != 1 or fprops[0][0] != "list":
+        raise ValueError("PLY: the face element is expected to be one index list")
+    ctype, itype = np.dtype(_PLY_TYPES[fprops[0][1]]), np.dtype(_PLY_TYPES[fprops[0][2]])
+    ftype = np.dtype([("n", ctype), ("i", itype, (3,))])
+    if len(data) - pos != nf * ftype.itemsize:
+        raise ValueError("PLY: only triangles are read")
+    f = np.frombuffer(data, dtype=ftype, count=nf, offset=pos)
+    if nf and not (f["n"] == 3).all():
+        raise ValueError("PLY: only triangles are read")
+    return Mesh(verts, f["i"].astype(np.int64), colours, normals)
+
+
+def _load_obj(text):
+    verts, faces = [], []
+    for line in text.split("\n"):
+        w = line.split()
+        if not w:
+            continue
+        if w[0] == "v":
+            verts.append([float(x) for x in w[1:4]])
+        elif w[0] == "f":
+            idx = []
+            for item in w[1:]:
+                i = int(item.split("/")[0])
+                idx.append(i - 1 if i > 0 else len(verts) + i)            # 1-based, or negative: counted back from the vertices so far
+            for k in range(1, len(idx) - 1):                             # a polygon as a fan from its first corner
+                faces.append([idx[0], idx[k], idx[k + 1]])
+    f = np.asarray(faces, dtype=np.int64).reshape(-1, 3)
+    if len(f) and (f.min() < 0 or f.max() >= len(verts)):
+        raise ValueError("OBJ: a face index outside the vertices")
+    return Mesh(np.asarray(verts, dtype=np.float64).reshape(-1, 3), f)
+
+
+def load_mesh(path):
+    """A `Mesh` from a file: the binary little-endian PLY `Mesh.export` writes (plain, with normals, coloured, or both; x y z as double
+    or float; colours come back as byte / 255, which `export` maps to the same bytes again) or a Wavefront OBJ (`v` and `f` lines
+    only; `f` items as i, i/j or i/j/k, 1-based or negative; polygons are fanned into triangles).  The format is told from the
+    file's first bytes, not its name."""
+    with open(path, "rb") as fh:
+        data = fh.read()
+    if data[:4] == b"ply\n" or data[:5] == b"ply\r\n":
+        return _load_ply(data)
+    return _load_obj(data.decode("utf-8", errors="replace"))

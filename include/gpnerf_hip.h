@@ -536,6 +536,137 @@ size_t gpnerf_metrics_workspace_bytes(int32_t H, int32_t W);
 int gpnerf_image_metrics(const float* pred, const float* gt, const uint8_t* mask, int32_t H, int32_t W, int64_t n, void* workspace,
                          size_t workspace_bytes, double* out, void* stream);
 
+/* ---- evaluating a mesh against another (gpnerf_meshdist.hip): the exact nearest point of a triangle mesh, area-weighted surface
+ * samples, and the reduction of a list of distances.  Point-to-surface distance, Chamfer, normal consistency and F-score are these
+ * three.  All entry points: kernel launches only, on the caller's stream; nothing allocated, nothing waited for; a fixed number of
+ * launches sized from the arguments alone; every data-dependent length stays on the device; every call captures into a HIP graph
+ * and replays with the same bits; the result is a function of the inputs alone (integer atomics only where the arrival order
+ * cannot matter -- gpnerf_meshdist.hip says where and why -- and no float atomic).
+ * A mesh is vertices: device float [n_vertices][3] and faces: device int32 [n_faces][3], 1 <= n_faces < 2^31.  A face with an index
+ * outside [0, n_vertices) or a non-finite vertex is INVALID: skipped, counted, never dereferenced.
+ *
+ * THE DISTANCE of a point p to a triangle (a, b, c), the one __device__ function every caller uses, in float32, unfused: the
+ * vertices are taken relative to p (a - p, ...: one rounding each), dot(u, v) = (ux vx + uy vy) + uz vz, and the closest point is
+ * Ericson's (Real-Time Collision Detection 5.1.5), its seven regions tested in his order -- vertex a, vertex b, edge ab, vertex c,
+ * edge ca, edge bc, interior -- with an edge's parameter taken as clamp(projection on the edge / |edge|^2, 0, 1) (0 when |edge|^2
+ * is 0) and the interior point as a + ab (vb / den) + ac (vc / den), den = (va + vb) + vc.  A triangle whose normal ab x ac is
+ * exactly zero (collinear vertices, three equal vertices), or whose den is not positive, is the nearest of its three segments
+ * (ab, bc, ca in that order, a strictly smaller squared distance replaces).  distance = sqrt(dot(cp, cp)).  Never NaN for finite input.
+ *
+ * gpnerf_mesh_grid_build(vertices, n_vertices, faces, n_faces, cell_cap, entry_cap, workspace, workspace_bytes, stream): a uniform
+ * cell grid over the bounding box of the valid faces, six launches:
+ *   - the box by a min / max reduction; the plan (one thread): extents e in double; cubic cells of edge s = (prod e / cell_cap)^(1/k)
+ *     over the k axes of positive extent, n[a] = min(floor(e[a] / s), 1024); an axis with e[a] < s gets ONE cell and the others share
+ *     cell_cap again; the product is at most cell_cap; cell size = e / n in float32, 1.0 on an axis of zero extent (a flat mesh is
+ *     legal).  cell(x) on an axis = clamp(floor((x - lo) * (1 / size)), 0, n - 1), in float32: monotone in x, defined for every x;
+ *   - a face is entered into every cell of cell(min corner) .. cell(max corner) of its own bounding box: count (integer atomic
+ *     add), exclusive scan (integers), fill, then every entry is written at run start + the number of smaller faces of its run:
+ *     within a cell the entries are in ascending face index whatever order the fill ran in.  That last step costs the sum of the
+ *     squared run lengths: choose cell_cap so that runs stay short (the Python wrapper's default does);
+ *   - the header, int32 words at the start of the workspace (GPNERF_GRID_HDR_*): STATUS (GPNERF_GRID_OK; GPNERF_GRID_OVERFLOW: the
+ *     entries needed exceed entry_cap, NO entry has been written, NEEDED holds the count to retry with), SKIPPED (invalid faces),
+ *     VALID, CELLS[3], N_CELLS, CELL_CAP, ENTRY_CAP, NEEDED (int64 in two words, low first), LO[3], SIZE[3], INV[3] (float32 bits).
+ *     A mesh with no valid face builds an empty grid (status OK): every distance to it is +inf;
+ *   - GPNERF_E_ARG, before any device call: a null pointer, n_vertices < 0, n_faces < 1 or >= 2^31, cell_cap < 1 or > 2^24,
+ *     entry_cap < 1 or > 2^30, a workspace under gpnerf_mesh_grid_workspace_bytes(n_faces, cell_cap, entry_cap) (host arithmetic
+ *     only; 0 for what the build refuses; 8 bytes per cell + 12 per entry + 33 KiB).
+ *
+ * gpnerf_mesh_distance(points, n_points, vertices, n_vertices, faces, n_faces, grid_workspace, max_dist, query_normals, dist, face,
+ * closest, cosine, stream): for each of the device float [n_points][3] queries
+ *   dist (device float [n]): min over the valid faces of THE DISTANCE -- exact, not approximate;  face (device int32 [n]): the face
+ *   that attains it, the LOWEST index among faces at bit-equal float32 distance;  closest (device float [n][3] or NULL): p + cp of
+ *   that face;  cosine (device float [n] or NULL, given together with query_normals, device float [n][3]): |n_q . n_f|, n_f =
+ *   (b - a) x (c - a) / its length in float32, 0 where that length is 0 or not finite or the product is NaN (n_q is used as given).
+ *   - max_dist = +inf: exact everywhere.  Finite and positive: exact wherever the result is at most max_dist; elsewhere dist = +inf,
+ *     face = -1, closest and cosine NaN.  Zero, negative or NaN is refused.  A mesh without a valid face: +inf / -1 everywhere;
+ *   - a query with a non-finite coordinate: dist NaN, face -1, closest and cosine NaN;
+ *   - grid_workspace NULL selects the BRUTE-FORCE form: the faces staged through LDS in tiles of 256, every query against every face,
+ *     the same distance function, tie rule and max_dist rule: dist and face are bit-equal to the grid form's.  It is the on-device
+ *     cross-check and the right form for small meshes.  n_vertices lets it refuse an invalid face by itself;
+ *   - grid_workspace: a workspace gpnerf_mesh_grid_build has filled FOR THE SAME vertices, faces and n_faces.  One query per lane;
+ *     the search visits the cells in shells r = 0, 1, 2, ... (Chebyshev distance r, in cells, from the query's own cell, clipped
+ *     to the grid) and stops behind shell r as soon as best <= B(r) or B(r) >= max_dist, or when every cell has been visited.
+ *     A grid whose status is not OK makes every dist NaN (face -1): a half-built grid is never read;
+ *   - THE BOUND.  B(r) = (r - 1/16) * w * 0.999, w = the smallest cell size among the axes on which shells 0..r do not yet reach
+ *     both ends of the grid.  Proof.  Let T be a face no cell of which lies in shells 0..r.  T's cells are a box of cell indices, so
+ *     on some axis a the box lies wholly above q[a] + r or wholly below q[a] - r, q = the query's cell; that axis is one the shells
+ *     have not covered from end to end.  Above: cell(Tmin) >= q + r + 1 >= 1, so floor(t(Tmin)) >= q + r + 1 (the clamp at n - 1
+ *     only lowers), t(x) = (x - lo) * inv as computed; and floor(t(p)) <= q -- the clamp at 0 only raises, and q = n - 1 by the
+ *     upper clamp is impossible here because q + r + 1 <= n - 1.  So t(Tmin) - t(p) > r.  Below is the mirror image: cell(Tmax) <=
+ *     q - r - 1 gives t(Tmax) < q - r, and t(p) >= q whether by floor or by the upper clamp.  Both hold for a query OUTSIDE the box:
+ *     its coordinate only enters through the one-sided inequality on the side it is clamped to.  The computed t differs from the
+ *     real (x - lo) / size by a factor 1 + d, |d| <= 3 * 2^-24, applied to values of magnitude at most n + 1 <= 1025 in these
+ *     inequalities, so the real separation exceeds (r - 2^-12) cells: every point of T is farther than (r - 2^-12) * size[a] from p.
+ *     The computed distance of such a face errs by at most 2^-20 * (distance + diameter of T), under 0.002 of a cell for any T
+ *     inside the grid; the 1/16 and the 0.999 cover both, so no face outside the visited shells can have a computed distance <= B(r):
+ *     none can beat or tie the best one, and dist and face equal the brute-force form's bit for bit;
+ *   - GPNERF_E_ARG, before any device call: n_points < 0, n_vertices < 0, n_faces < 1, null vertices or faces, a max_dist that is
+ *     not > 0, cosine without query_normals or the reverse, and (with n_points > 0) null points, dist or face.  n_points == 0 is a no-op.
+ *
+ * gpnerf_mesh_sample_surface(vertices, n_vertices, faces, n_faces, n_samples, seed, workspace, workspace_bytes, points, sample_face,
+ * sample_normal, stream): n_samples (< 2^31) deterministic area-weighted points on the surface, three launches:
+ *   - a face's area is 0.5 |(b - a) x (c - a)| in double from the float32 vertices (0 for an INVALID face, which so receives no sample); the
+ *     inclusive prefix sums P are taken in double in one fixed association (four faces in a thread, 256 threads in thread order,
+ *     chunks of 1024 faces in chunk order), so P never decreases and is a function of the inputs alone;
+ *   - sample i takes the first face f with P[f] > (i + 0.5) / n_samples * total: stratified, every face receives its share to
+ *     within one sample, a face of zero area receives none;
+ *   - the point is (1 - s) a + s (1 - r2) b + s r2 c, s = sqrt(r1), each coordinate (wa a + wb b) + wc c in float32;
+ *     r1 = (h(seed ^ h(2 i)) >> 8) * 2^-24, r2 = (h(seed ^ h(2 i + 1)) >> 8) * 2^-24 in [0, 1), uint32 arithmetic, i's low 32 bits,
+ *     h = MurmurHash3's 32-bit finalizer fmix32 (Appleby): h ^= h >> 16; h *= 0x85ebca6b; h ^= h >> 13; h *= 0xc2b2ae35; h ^= h >> 16;
+ *   - points: device float [n][3]; sample_face: device int32 [n] or NULL; sample_normal: device float [n][3] or NULL, the face's
+ *     (b - a) x (c - a) / its length in float32;
+ *   - the workspace (gpnerf_mesh_sample_workspace_bytes(n_faces): 8 bytes per face and a little) starts with an int32 status:
+ *     GPNERF_SAMPLE_OK, or GPNERF_SAMPLE_NO_AREA when the total area is zero or not finite: every point is then NaN, every face -1;
+ *     the total (double) is at byte 8;
+ *   - GPNERF_E_ARG, before any device call: null vertices, faces or workspace, n_vertices < 0, n_faces < 1 or >= 2^31, n_samples < 0
+ *     or >= 2^31, a workspace that is too small, null points with n_samples > 0.  n_samples == 0 is a no-op.
+ *
+ * gpnerf_distance_stats(values, n, thresholds, n_thresholds, out, stream): one slot of GPNERF_DIST_DOUBLES doubles on the device from
+ * device float [n] values (distances, or cosines), one launch of one workgroup: every thread adds its values t, t + 256, ... in
+ * order in double, then a fixed tree; no atomics.  thresholds: HOST float [n_thresholds], n_thresholds <= GPNERF_DIST_MAX_THRESHOLDS.
+ *   FINITE, INF, NAN: the counts of finite, infinite (+inf: beyond max_dist; -inf is counted here too) and NaN values;  MEAN, MEAN_SQ, MAX: of the finite values,
+ *   NaN when there is none;  WITHIN + k: the fraction of the non-NaN values that are <= thresholds[k] (an infinite value of either sign is
+ *   not within), NaN when there is no non-NaN value or k >= n_thresholds.  n == 0: the counts are 0, everything else NaN.
+ *   GPNERF_E_ARG: null out, n < 0, null values with n > 0, n_thresholds outside [0, 4], null thresholds with n_thresholds > 0. */
+#define GPNERF_GRID_OK 0
+#define GPNERF_GRID_OVERFLOW 1
+#define GPNERF_GRID_BUILDING 2
+#define GPNERF_GRID_HDR_MAGIC 0
+#define GPNERF_GRID_HDR_STATUS 1
+#define GPNERF_GRID_HDR_SKIPPED 2
+#define GPNERF_GRID_HDR_VALID 3
+#define GPNERF_GRID_HDR_CELLS 4
+#define GPNERF_GRID_HDR_N_CELLS 7
+#define GPNERF_GRID_HDR_CELL_CAP 8
+#define GPNERF_GRID_HDR_ENTRY_CAP 9
+#define GPNERF_GRID_HDR_NEEDED 10
+#define GPNERF_GRID_HDR_LO 12
+#define GPNERF_GRID_HDR_SIZE 15
+#define GPNERF_GRID_HDR_INV 18
+#define GPNERF_GRID_HDR_INTS 64
+#define GPNERF_SAMPLE_OK 0
+#define GPNERF_SAMPLE_NO_AREA 1
+#define GPNERF_DIST_FINITE 0
+#define GPNERF_DIST_INF 1
+#define GPNERF_DIST_NAN 2
+#define GPNERF_DIST_MEAN 3
+#define GPNERF_DIST_MEAN_SQ 4
+#define GPNERF_DIST_MAX 5
+#define GPNERF_DIST_WITHIN 6
+#define GPNERF_DIST_MAX_THRESHOLDS 4
+#define GPNERF_DIST_DOUBLES 10
+size_t gpnerf_mesh_grid_workspace_bytes(int64_t n_faces, int64_t cell_cap, int64_t entry_cap);
+int gpnerf_mesh_grid_build(const float* vertices, int64_t n_vertices, const int32_t* faces, int64_t n_faces, int64_t cell_cap,
+                           int64_t entry_cap, void* workspace, size_t workspace_bytes, void* stream);
+int gpnerf_mesh_distance(const float* points, int64_t n_points, const float* vertices, int64_t n_vertices, const int32_t* faces,
+                         int64_t n_faces, void* grid_workspace, float max_dist, const float* query_normals, float* dist, int32_t* face,
+                         float* closest, float* cosine, void* stream);
+size_t gpnerf_mesh_sample_workspace_bytes(int64_t n_faces);
+int gpnerf_mesh_sample_surface(const float* vertices, int64_t n_vertices, const int32_t* faces, int64_t n_faces, int64_t n_samples,
+                               uint32_t seed, void* workspace, size_t workspace_bytes, float* points, int32_t* sample_face,
+                               float* sample_normal, void* stream);
+int gpnerf_distance_stats(const float* values, int64_t n, const float* thresholds, int32_t n_thresholds, double* out, void* stream);
+
 /* ---- per-frame sparse convolution pyramid (gpnerf_volume.hip), replacing the external spconv v1.2.1 calls of
  * libs/nerfheads/networks/SparseConvNet.py:22-111 (SubMConv3d / SparseConv3d + BatchNorm1d + ReLU, .dense()).
  * A sparse tensor is: features [M][C] fp32, coords [M][3] int32 (d,h,w), and a dense int32 index grid [D][H][W]
