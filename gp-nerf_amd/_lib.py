@@ -136,6 +136,10 @@ GRID_HDR_INTS = 64
 SAMPLE_OK, SAMPLE_NO_AREA = range(2)
 DIST_FINITE, DIST_INF, DIST_NAN, DIST_MEAN, DIST_MEAN_SQ, DIST_MAX, DIST_WITHIN = range(7)
 DIST_MAX_THRESHOLDS, DIST_DOUBLES = 4, 10
+# gpnerf_mesh_rasterize's stats row and gpnerf_silhouette_stats' row (include/gpnerf_hip.h GPNERF_RASTER_* / GPNERF_SILHOUETTE_*)
+RASTER_DRAWN, RASTER_SKIPPED_VERTEX, RASTER_SKIPPED_AREA, RASTER_PIXELS = range(4)
+SILHOUETTE_COVERED, SILHOUETTE_GT, SILHOUETTE_BOTH, SILHOUETTE_EITHER, SILHOUETTE_IGNORED, SILHOUETTE_COUNTS = range(6)
+RASTER_MAX_VIEWS, RASTER_MAX_ATTRS = 8, 4
 
 # every symbol include/gpnerf_hip.h declares: (restype, argtypes)
 SYMBOLS = {
@@ -239,6 +243,12 @@ SYMBOLS = {
     "gpnerf_mesh_sample_surface": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_uint32, C.c_void_p, C.c_size_t,
                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gpnerf_distance_stats": (C.c_int, [C.c_void_p, C.c_int64, FP, C.c_int32, C.c_void_p, C.c_void_p]),
+    "gpnerf_mesh_raster_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32, C.c_int32]),
+    "gpnerf_mesh_rasterize": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, DP, C.c_int32, C.c_int32, C.c_int32, C.c_double,
+                                        C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gpnerf_mesh_interpolate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, DP, C.c_int32, C.c_int32, C.c_int32,
+                                          C.c_double, C.c_void_p, C.c_int32, FP, C.c_void_p, C.c_void_p]),
+    "gpnerf_silhouette_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "gpnerf_head_layout": (C.c_int, [C.POINTER(C.c_int32)]),
     "gpnerf_strerror": (C.c_char_p, [C.c_int]),
     "gpnerf_rays_per_tile": (C.c_int32, []),

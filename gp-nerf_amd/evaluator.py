@@ -17,7 +17,9 @@ pinned to the reference's own loop over three frames (tests/golden/loop_demo_3fr
 `MeshEvaluator` mirrors libs/evaluators/if_nerf_mesh.py for a geometry-mode renderer (use_rgbhead False); the loop takes it
 through `evaluate_loop(evaluator=...)` and otherwise constructs the image evaluator, as the reference's loop always does.  Given a
 `gt_mesh` per frame it also computes the geometry metrics (P2S, Chamfer, normal consistency, F-score) on the device
-(frame.mesh_metrics, csrc/gpnerf_meshdist.hip).
+(frame.mesh_metrics, csrc/gpnerf_meshdist.hip); with `silhouette=True` and the cameras and masks of the dense renderer's geometry mode
+in the batch it scores the mesh's silhouettes against the masks (frame.rasterize_mesh, csrc/gpnerf_raster.hip): what data without
+scans offers.
 
 `DeviceEvaluator` (opt-in: `evaluate_loop(device_metrics=True)` or GPNERF_DEVICE_METRICS=1) computes the same three numbers with
 gpnerf_image_metrics (csrc/gpnerf_metrics.hip): four kernel launches per frame into a device slot, no host synchronisation in
@@ -241,11 +243,19 @@ class MeshEvaluator:
     metric_samples: surface samples per mesh and direction; metric_thresholds: the F-score distances, in the meshes' unit (metres
     for the project's scenes: 5 mm, 1 cm, 2 cm); metric_max_dist: gpnerf_mesh_distance's max_dist (inf: exact everywhere);
     metric_cell_cap, metric_entry_cap: the grids' capacities (None: frame.mesh_grid_caps).  `evaluate` does not read the grids'
-    status, so a grid that overflows its entry capacity shows at `summarize()`, whose error says how to find the capacity to pass here."""
+    status, so a grid that overflows its entry capacity shows at `summarize()`, whose error says how to find the capacity to pass here.
+    silhouette (off by default; data with cameras and masks but no scan): a batch with `hull_masks` [1,n,h,w] uint8 (0, 1, border
+    100), `hull_Ks` [1,n,3,3] and `hull_RTs` [1,n,3,4] -- the keys of the dense renderer's geometry mode -- makes `evaluate` put the
+    frame's mesh through `to_lattice_frame(output["axes"], PAD)`, draw it into those cameras at the masks' size
+    (frame.rasterize_mesh) and enqueue frame.silhouette_stats against the masks: a slot per frame, no host read.  `summarize()`
+    reads the slots in one copy and adds `silhouette_iou`, `silhouette_precision`, `silhouette_recall` (means over views and
+    frames; the border band is left out) and their per-frame lists, and saves `<result_path>/silhouette_metrics.npy` (a structured
+    array: frame_index, the three means, and the per-view values).  An output without `axes` -- the inference renderer's
+    render_mesh, whose mesh is not in the cameras' frame -- raises a GpnerfError naming the key.  Off, nothing changes."""
     PAD = 10                              # if_nerf_mesh.py:20, the np.pad(cube, 10) of BaseRender.py:269
 
     def __init__(self, result_path, mesh_th, export_mesh=False, metric_samples=100000, metric_thresholds=(0.005, 0.01, 0.02),
-                 metric_max_dist=float("inf"), metric_device=None, metric_cell_cap=None, metric_entry_cap=None):
+                 metric_max_dist=float("inf"), metric_device=None, metric_cell_cap=None, metric_entry_cap=None, silhouette=False):
         self.mesh_th = mesh_th
         self.export_mesh = bool(export_mesh)
         self.result_path = result_path
@@ -255,11 +265,35 @@ class MeshEvaluator:
         self.metric_max_dist, self.metric_device = float(metric_max_dist), metric_device
         self.metric_cell_cap, self.metric_entry_cap = metric_cell_cap, metric_entry_cap
         self._slots, self._frames = [], []
+        self.silhouette = bool(silhouette)
+        self._sil_slots, self._sil_frames = [], []
+
+    SILHOUETTE_KEYS = ("hull_masks", "hull_Ks", "hull_RTs")
 
     @property
     def has_mesh_metrics(self):
-        """True once a frame with `gt_mesh` has been evaluated and not yet summarized (evaluate_loop asks)"""
-        return bool(self._slots)
+        """True once a frame with `gt_mesh` (or, with silhouette on, with masks and cameras) has been evaluated and not yet summarized
+        (evaluate_loop asks)"""
+        return bool(self._slots) or bool(self._sil_slots)
+
+    def _enqueue_silhouette(self, output, batch):
+        from . import frame as F
+        if "axes" not in output:
+            raise L.GpnerfError("MeshEvaluator(silhouette=True): the output has no 'axes', so its mesh cannot be put into the cameras' frame "
+                                "(the inference renderer's render_mesh; the dense renderer's geometry mode returns axes)")
+        masks = torch.as_tensor(batch["hull_masks"][0])
+        if not masks.is_cuda:
+            raise L.GpnerfError(f"MeshEvaluator(silhouette=True): hull_masks must live on the GPU (got {masks.device}); no CPU fallback")
+        if masks.dtype != torch.uint8 or masks.dim() != 3:
+            raise L.GpnerfError(f"MeshEvaluator(silhouette=True): hull_masks must be uint8 [1,n,h,w] (0, 1, border 100), got {masks.dtype} "
+                                f"{tuple(batch['hull_masks'].shape)}")
+        masks = masks.contiguous()
+        Ks, RTs = F.fetch_host(batch["hull_Ks"][0], batch["hull_RTs"][0])
+        pred = output["mesh"].to_lattice_frame(output["axes"], self.PAD)
+        v, f = F.mesh_to_device(pred, masks.device)
+        drawn = F.rasterize_mesh(v, f, Ks, RTs, int(masks.shape[1]), int(masks.shape[2]), want=("face_id",))
+        self._sil_slots.append(F.silhouette_stats(drawn["face_id"], masks))
+        self._sil_frames.append(self._scalar(batch["frame_index"]))
 
     @staticmethod
     def _scalar(v):
@@ -289,8 +323,49 @@ class MeshEvaluator:
                                               max_dist=self.metric_max_dist, device=self.metric_device, cell_cap=self.metric_cell_cap,
                                               entry_cap=self.metric_entry_cap))
             self._frames.append(self._scalar(batch["frame_index"]))
+        if self.silhouette and all(k in batch for k in self.SILHOUETTE_KEYS):
+            self._enqueue_silhouette(output, batch)
+
+    def _summarize_silhouettes(self):
+        """the silhouette slots -> (means, per-frame lists), silhouette_metrics.npy written; resets them"""
+        from . import frame as F
+        views = {int(s.shape[0]) for s in self._sil_slots}
+        host = [s.cpu().numpy() for s in self._sil_slots] if len(views) > 1 else list(torch.stack(self._sil_slots).cpu().numpy())   # the one read
+        rows = [F.read_silhouette_metrics(h) for h in host]
+        names = ("iou", "precision", "recall")
+        per_frame = {f"silhouette_{k}": [r[k] for r in rows] for k in names}
+        per_frame["silhouette_frame_index"] = list(self._sil_frames)
+        metrics = {f"silhouette_{k}": float(np.mean(per_frame[f"silhouette_{k}"])) for k in names}
+        n = max(views)
+        table = np.zeros(len(rows), dtype=[("frame_index", "i8"), ("views", "i8")] + [(k, "f8") for k in names] +
+                         [(f"{k}_per_view", "f8", (n,)) for k in names] + [("ignored_per_view", "i8", (n,))])
+        table["frame_index"], table["views"] = self._sil_frames, [len(r["per_view"]["iou"]) for r in rows]
+        for k in names:
+            table[k] = [r[k] for r in rows]
+            table[f"{k}_per_view"] = np.nan
+        for i, r in enumerate(rows):
+            for k in names:
+                table[f"{k}_per_view"][i, :len(r["per_view"][k])] = r["per_view"][k]
+            table["ignored_per_view"][i, :len(r["per_view"]["ignored"])] = r["per_view"]["ignored"]
+        os.makedirs(self.result_path, exist_ok=True)
+        np.save(os.path.join(self.result_path, "silhouette_metrics.npy"), table)    # a structured array: one row per frame
+        for k in names:
+            print(f"silhouette_{k}: {metrics['silhouette_' + k]}")
+        self._sil_slots, self._sil_frames = [], []
+        return metrics, per_frame
 
     def summarize(self):
+        if self._sil_slots:
+            sil, sil_frames = self._summarize_silhouettes()
+            metrics = self._summarize_mesh_metrics() if self._slots else {"per_frame": {}}
+            per_frame = metrics.pop("per_frame")
+            metrics.update(sil)
+            per_frame.update(sil_frames)
+            metrics["per_frame"] = per_frame
+            return metrics
+        return self._summarize_mesh_metrics()
+
+    def _summarize_mesh_metrics(self):
         if not self._slots:
             return {}
         from . import frame as F

@@ -1178,3 +1178,126 @@ def read_mesh_metrics(slots, thresholds=(0.005, 0.01, 0.02)):
     for row, name in ((0, "pred"), (1, "gt")):
         res[f"n_{name}"], res[f"beyond_{name}"], res[f"nan_{name}"] = (int(s[row, k]) for k in (L.DIST_FINITE, L.DIST_INF, L.DIST_NAN))
     return res
+
+
+# ---- drawing a mesh into calibrated cameras (csrc/gpnerf_raster.hip)
+
+def _raster_mesh(vertices, faces, what, device=None):
+    """a device mesh from (vertices, faces) device tensors, or -- faces None -- from a mesh.Mesh / a pair of host arrays, uploaded by
+    mesh_to_device; unlike the distance entry points the rasteriser takes a mesh without faces"""
+    if faces is None:
+        pair = (vertices.vertices, vertices.faces) if hasattr(vertices, "vertices") else vertices
+        if any(isinstance(t, torch.Tensor) for t in pair):
+            for t, name in zip(pair, ("vertices", "faces")):
+                if not isinstance(t, torch.Tensor):
+                    raise L.GpnerfError(f"{what}: {name} must be a device tensor like the other")
+                _require_gpu(t, f"{what}: {name}")
+            device = pair[0].device
+        vertices, faces = mesh_to_device(vertices, torch.device(device if device is not None else "cuda:0"))
+    for t, name in ((vertices, "vertices"), (faces, "faces")):
+        if not isinstance(t, torch.Tensor):
+            raise L.GpnerfError(f"{what}: {name} must be a device tensor (pass a Mesh alone and it is uploaded)")
+        _require_gpu(t, f"{what}: {name}")
+    if vertices.dtype != torch.float32 or vertices.dim() != 2 or vertices.shape[1] != 3 or not vertices.is_contiguous():
+        raise L.GpnerfError(f"{what}: expected contiguous float32 vertices [n,3], got {vertices.dtype} {tuple(vertices.shape)}")
+    if faces.dtype != torch.int32 or faces.dim() != 2 or faces.shape[1] != 3 or not faces.is_contiguous():
+        raise L.GpnerfError(f"{what}: expected contiguous int32 faces [m,3], got {faces.dtype} {tuple(faces.shape)}")
+    if faces.device != vertices.device:
+        raise L.GpnerfError(f"{what}: vertices and faces are on different devices")
+    return vertices, faces
+
+
+def _raster_cams(Ks, RTs, what):
+    host = lambda a: np.asarray(a.detach().cpu() if isinstance(a, torch.Tensor) else a, dtype=np.float64)
+    cams = np.ascontiguousarray(np.concatenate([host(Ks).reshape(-1, 9), host(RTs).reshape(-1, 12)], axis=1))
+    if not 1 <= cams.shape[0] <= L.RASTER_MAX_VIEWS:
+        raise L.GpnerfError(f"{what}: 1 to {L.RASTER_MAX_VIEWS} cameras, got {cams.shape[0]}")
+    return cams
+
+
+def rasterize_mesh(vertices, faces, Ks, RTs, H, W, z_near=1e-6, want=("depth", "face_id"), attributes=None, background=0.0):
+    """gpnerf_mesh_rasterize (and gpnerf_mesh_interpolate when `attributes` are given): the mesh drawn into the cameras Ks [n,3,3],
+    RTs [n,3,4] (host arrays, used in float64; T in the vertices' unit: visual_hull's cameras) at H x W.  vertices, faces: device
+    float32 [nv,3] and int32 [nf,3]; or faces=None and `vertices` a mesh.Mesh or a (vertices, faces) pair, which mesh_to_device uploads
+    (host arrays go to cuda:0).  include/gpnerf_hip.h states what a pixel receives: the nearest face covering its centre, edges
+    inclusive, the smaller face index among equal depths, bit-reproducible.
+    Returns a dict of device tensors: "depth" float32 [n,H,W] (+inf where empty) and "face_id" int32 [n,H,W] (-1 there) as `want`
+    names them, "stats" int64 [n,4] (_lib.RASTER_*: faces drawn, skipped for a vertex, skipped for zero area, pixels covered), and
+    "image" float32 [n,H,W,C] when attributes -- device float32 [nv,C] or [nv], C <= 4, e.g. vertex colours or normals -- are given:
+    interpolated perspective-correctly over the winning faces, `background` (a number or C numbers) elsewhere.  Nothing is read back."""
+    lib = L.lib()
+    vertices, faces = _raster_mesh(vertices, faces, "rasterize_mesh")
+    unknown = set(want) - {"depth", "face_id"}
+    if unknown:
+        raise L.GpnerfError(f"rasterize_mesh: want names {sorted(unknown)}; depth and face_id are what there is")
+    cams = _raster_cams(Ks, RTs, "rasterize_mesh")
+    n, nv, nf, dev = cams.shape[0], int(vertices.shape[0]), int(faces.shape[0]), vertices.device
+    H, W = int(H), int(W)
+    nbytes = int(lib.gpnerf_mesh_raster_workspace_bytes(nf, n, H, W))
+    if nbytes <= 0:
+        raise L.GpnerfError(f"rasterize_mesh: refused ({nf} faces, {n} views, {H} x {W})")
+    ws = _workspace(dev, nbytes)
+    res = {"stats": torch.empty((n, 4), device=dev, dtype=torch.int64)}
+    if "depth" in want:
+        res["depth"] = torch.empty((n, H, W), device=dev, dtype=torch.float32)
+    face_id = torch.empty((n, H, W), device=dev, dtype=torch.int32) if "face_id" in want or attributes is not None else None
+    if "face_id" in want:
+        res["face_id"] = face_id
+    ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None
+    L.check(lib.gpnerf_mesh_rasterize(ptr(vertices), nv, ptr(faces), nf, cams.ctypes.data_as(L.DP), n, H, W, float(z_near), ws.data_ptr(),
+                                      ws.numel(), ptr(res.get("depth")), ptr(face_id), res["stats"].data_ptr(), _stream_ptr(dev)),
+            "gpnerf_mesh_rasterize")
+    if attributes is not None:
+        if not isinstance(attributes, torch.Tensor):
+            raise L.GpnerfError("rasterize_mesh: attributes must be a device tensor")
+        _require_gpu(attributes, "rasterize_mesh: attributes")
+        attrs = attributes.reshape(nv, -1) if attributes.dim() == 1 else attributes
+        if attrs.dtype != torch.float32 or attrs.dim() != 2 or attrs.shape[0] != nv or not attrs.is_contiguous() or attrs.device != dev:
+            raise L.GpnerfError(f"rasterize_mesh: expected contiguous float32 attributes [{nv},C] on {dev}, got {attrs.dtype} {tuple(attrs.shape)}")
+        c = int(attrs.shape[1])
+        if not 1 <= c <= L.RASTER_MAX_ATTRS:
+            raise L.GpnerfError(f"rasterize_mesh: 1 to {L.RASTER_MAX_ATTRS} attribute channels, got {c}")
+        bg = np.broadcast_to(np.asarray(background, dtype=np.float32), (c,))
+        res["image"] = torch.empty((n, H, W, c), device=dev, dtype=torch.float32)
+        L.check(lib.gpnerf_mesh_interpolate(face_id.data_ptr(), ptr(vertices), nv, ptr(faces), nf, cams.ctypes.data_as(L.DP), n, H, W, float(z_near),
+                                            ptr(attrs), c, (C.c_float * c)(*[float(b) for b in bg]), res["image"].data_ptr(), _stream_ptr(dev)),
+                "gpnerf_mesh_interpolate")
+    return res
+
+
+def silhouette_stats(face_id, masks, out=None):
+    """gpnerf_silhouette_stats: device int64 [n,5] (_lib.SILHOUETTE_*: covered, gt, both, either over the pixels whose mask is not the
+    border band's 100, and the number of those left out) from rasterize_mesh's face_id int32 [n,H,W] and the views' masks, device
+    uint8 [n,H,W] (0, 1, border 100).  out: a [n,5] int64 slot to write into.  Nothing is read back."""
+    lib = L.lib()
+    for t, name in ((face_id, "face_id"), (masks, "masks")):
+        if not isinstance(t, torch.Tensor):
+            raise L.GpnerfError(f"silhouette_stats: {name} must be a device tensor")
+        _require_gpu(t, f"silhouette_stats: {name}")
+    if face_id.dtype != torch.int32 or face_id.dim() != 3 or not face_id.is_contiguous():
+        raise L.GpnerfError(f"silhouette_stats: expected contiguous int32 face_id [n,H,W], got {face_id.dtype} {tuple(face_id.shape)}")
+    if masks.dtype != torch.uint8 or masks.shape != face_id.shape or not masks.is_contiguous() or masks.device != face_id.device:
+        raise L.GpnerfError(f"silhouette_stats: expected contiguous uint8 masks {tuple(face_id.shape)} on {face_id.device}, got {masks.dtype} "
+                            f"{tuple(masks.shape)} on {masks.device}")
+    n, H, W = (int(s) for s in face_id.shape)
+    if out is None:
+        out = torch.empty((n, L.SILHOUETTE_COUNTS), device=face_id.device, dtype=torch.int64)
+    L.check(lib.gpnerf_silhouette_stats(face_id.data_ptr(), masks.data_ptr(), n, H, W, out.data_ptr(), _stream_ptr(face_id.device)),
+            "gpnerf_silhouette_stats")
+    return out
+
+
+def read_silhouette_metrics(host_counts):
+    """silhouette_stats' counts on the host ([n,5], array or tensor) -> {"iou", "precision", "recall": the means over the views,
+    "per_view": {"iou": [...], "precision": [...], "recall": [...], "ignored": [...]}}.  iou = both / either, precision = both / covered,
+    recall = both / gt; 0 / 0 is 1.0 (nothing drawn where nothing is to be drawn is a match)."""
+    c = np.asarray(host_counts.detach().cpu() if isinstance(host_counts, torch.Tensor) else host_counts).astype(np.int64).reshape(-1, L.SILHOUETTE_COUNTS)
+    if not len(c):
+        raise L.GpnerfError("read_silhouette_metrics: no view")
+    ratio = lambda num, den: [float(a) / float(b) if b else 1.0 for a, b in zip(c[:, num], c[:, den])]
+    per = {"iou": ratio(L.SILHOUETTE_BOTH, L.SILHOUETTE_EITHER), "precision": ratio(L.SILHOUETTE_BOTH, L.SILHOUETTE_COVERED),
+           "recall": ratio(L.SILHOUETTE_BOTH, L.SILHOUETTE_GT)}
+    res = {k: float(np.mean(v)) for k, v in per.items()}
+    per["ignored"] = [int(v) for v in c[:, L.SILHOUETTE_IGNORED]]
+    res["per_view"] = per
+    return res

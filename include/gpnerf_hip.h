@@ -667,6 +667,78 @@ int gpnerf_mesh_sample_surface(const float* vertices, int64_t n_vertices, const 
                                float* sample_normal, void* stream);
 int gpnerf_distance_stats(const float* values, int64_t n, const float* thresholds, int32_t n_thresholds, double* out, void* stream);
 
+/* ---- drawing a mesh into calibrated cameras (gpnerf_raster.hip): depth and face-id maps, vertex attributes interpolated over them,
+ * and the counts that compare the mesh's silhouette with a foreground mask (mask IoU, precision, recall: how a body mesh is judged on
+ * data that has cameras and masks but no scan).  All entry points: kernel launches only, on the caller's stream; nothing allocated,
+ * nothing waited for; every launch sized from the arguments alone; the one data-dependent length (the large-face list's) stays on
+ * the device; every call captures into a HIP graph and replays with the same bits; the result is a function of the inputs alone and
+ * of no launch geometry (integer atomics only -- a 64-bit unsigned minimum per covered pixel, integer sums -- and no float atomic).
+ * A mesh is vertices: device float [n_vertices][3] and faces: device int32 [n_faces][3], 0 <= n_faces < 2^31 (a pointer may be NULL
+ * where its count is 0).  cams: HOST double [n_views][21] = K 3x3 row-major, then RT 3x4 row-major: gpnerf_visual_hull's layout and
+ * meaning; n_views: 1 to 8; H, W: 1 to 16384.
+ *
+ * THE DEFINITION (gpnerf_mesh_rasterize), per view:
+ *   - a vertex: the float32 point widened to float64, c = p0 RT[:,0] + p1 RT[:,1] + p2 RT[:,2] + RT[:,3], h = c0 K[:,0] + c1 K[:,1]
+ *     + c2 K[:,2] (float64, multiply then add in that order, unfused: gpnerf_visual_hull's projection), z = h2, x = h0 / h2,
+ *     y = h1 / h2.  It is USABLE iff x, y and z are finite, z >= z_near and |x| <= 2^20 and |y| <= 2^20.  Its snapped position is
+ *     X = int64(rint(256 x)), Y = int64(rint(256 y)) (rint: half to even): 1/256 of a pixel.  The centre of pixel (column i, row j)
+ *     is (256 i, 256 j) -- the convention under which the hull's rint(x) picks a pixel;
+ *   - a face (a, b, c) is SKIPPED FOR A VERTEX when an index is outside [0, n_vertices) or a vertex is not usable in this view (behind
+ *     the near plane, beyond the guard band, not finite); otherwise it is SKIPPED FOR ITS AREA when its doubled area
+ *     A = (Xb - Xa)(Yc - Ya) - (Yb - Ya)(Xc - Xa) (int64, exact) is 0; otherwise it is DRAWN (whether or not it covers a pixel).
+ *     There is no backface culling;
+ *   - coverage, int64 (no overflow: differences are at most 2^29, products at most 2^58): with P the pixel's centre,
+ *     Ea = (Xc - Xb)(Py - Yb) - (Yc - Yb)(Px - Xb), Eb = (Xa - Xc)(Py - Yc) - (Ya - Yc)(Px - Xc), Ec = (Xb - Xa)(Py - Ya) - (Yb - Ya)
+ *     (Px - Xa) (Ea + Eb + Ec = A).  The pixel is covered iff Ek sign(A) >= 0 for all three: edges and vertices are inclusive, so two
+ *     faces that share an edge both cover a pixel centre on it and the key below decides;
+ *   - depth, perspective-correct, float64: wk = double(Ek) / double(A), q = (wa / za + wb / zb) + wc / zc, depth = float(1 / q);
+ *   - a pixel keeps the MINIMUM over the drawn faces that cover it of the 64-bit key (bits(depth) << 32) | face index: the nearest
+ *     depth, then the smaller face index.
+ * Outputs, each optional (NULL):  depth: device float [n_views][H][W], +inf where no face covers;  face_id: device int32
+ * [n_views][H][W], -1 there;  stats: device int64 [n_views][4] (GPNERF_RASTER_*): faces DRAWN, SKIPPED_VERTEX, SKIPPED_AREA
+ * (their sum is n_faces) and PIXELS covered.
+ * Launches: a clear; one lane per (face, view), which walks the face's clipped pixel box -- the pixels whose centres lie in
+ * [min X, max X] x [min Y, max Y] and in the image -- unless that box holds more than 256 pixels: such a pair is appended to a
+ * list in the workspace (one counter add per wavefront); a launch of fixed grid that reads the list's length on the device and
+ * gives each listed pair a wavefront, 64 pixels per step; a resolve that splits the keys (one integer add per wavefront for PIXELS).
+ * workspace: gpnerf_mesh_raster_workspace_bytes(n_faces, n_views, H, W) bytes (host arithmetic only; 0 for what the call refuses) =
+ * 256 + align256(8 n_views H W) + align256(8 n_faces n_views), align256 rounding up to a multiple of 256: the header, the keys,
+ * the list at its worst.  It carries nothing from call to call.
+ * GPNERF_E_ARG, before anything is launched: null cams or workspace, null vertices with n_vertices > 0 or faces with n_faces > 0,
+ * a count that is negative or >= 2^31, n_views outside 1..8, H or W outside 1..16384, a z_near that is not > 0 and finite, a
+ * workspace under the formula.
+ *
+ * gpnerf_mesh_interpolate(face_id, vertices, n_vertices, faces, n_faces, cams, n_views, H, W, z_near, attrs, C, background, out,
+ * stream): attrs: device float [n_vertices][C], C in 1..4; background: HOST float [C]; out: device float [n_views][H][W][C].  At a
+ * pixel whose face_id names a face that is drawn in that view (same z_near) and covers the pixel, the face's Ek, wk, zk and q are
+ * recomputed as above, uk = (wk / zk) / q, and out = (ua attr_a + ub attr_b) + uc attr_c in float64, rounded to float32; every other
+ * pixel (-1, an id outside [0, n_faces), a face that does not cover it) receives background.  One launch.  GPNERF_E_ARG as above,
+ * and for null face_id, background or out, null attrs with n_vertices > 0, C outside 1..4.
+ *
+ * gpnerf_silhouette_stats(face_id, masks, n_views, H, W, out, stream): masks: device uint8 [n_views][H][W] (get_mask: 0, 1 and the
+ * border band's 100); out: device int64 [n_views][GPNERF_SILHOUETTE_COUNTS], set by the call.  Per view, over the pixels whose mask
+ * is not 100: COVERED (face_id >= 0), GT (mask != 0), BOTH, EITHER; IGNORED: the pixels whose mask is 100 -- the border band is left
+ * out, as evaluation on this data does.  IoU = BOTH / EITHER, precision = BOTH / COVERED, recall = BOTH / GT.  Two launches (a zero,
+ * a count with one add per wavefront and counter).  GPNERF_E_ARG: a null pointer, n_views outside 1..8, H or W outside 1..16384. */
+#define GPNERF_RASTER_DRAWN 0
+#define GPNERF_RASTER_SKIPPED_VERTEX 1
+#define GPNERF_RASTER_SKIPPED_AREA 2
+#define GPNERF_RASTER_PIXELS 3
+#define GPNERF_SILHOUETTE_COVERED 0
+#define GPNERF_SILHOUETTE_GT 1
+#define GPNERF_SILHOUETTE_BOTH 2
+#define GPNERF_SILHOUETTE_EITHER 3
+#define GPNERF_SILHOUETTE_IGNORED 4
+#define GPNERF_SILHOUETTE_COUNTS 5
+size_t gpnerf_mesh_raster_workspace_bytes(int64_t n_faces, int32_t n_views, int32_t H, int32_t W);
+int gpnerf_mesh_rasterize(const float* vertices, int64_t n_vertices, const int32_t* faces, int64_t n_faces, const double* cams,
+                          int32_t n_views, int32_t H, int32_t W, double z_near, void* workspace, size_t workspace_bytes, float* depth,
+                          int32_t* face_id, int64_t* stats, void* stream);
+int gpnerf_mesh_interpolate(const int32_t* face_id, const float* vertices, int64_t n_vertices, const int32_t* faces, int64_t n_faces,
+                            const double* cams, int32_t n_views, int32_t H, int32_t W, double z_near, const float* attrs, int32_t C,
+                            const float* background, float* out, void* stream);
+int gpnerf_silhouette_stats(const int32_t* face_id, const uint8_t* masks, int32_t n_views, int32_t H, int32_t W, int64_t* out, void* stream);
+
 /* ---- per-frame sparse convolution pyramid (gpnerf_volume.hip), replacing the external spconv v1.2.1 calls of
  * libs/nerfheads/networks/SparseConvNet.py:22-111 (SubMConv3d / SparseConv3d + BatchNorm1d + ReLU, .dense()).
  * A sparse tensor is: features [M][C] fp32, coords [M][3] int32 (d,h,w), and a dense int32 index grid [D][H][W]
