@@ -2723,14 +2723,44 @@ head_forward_kernel(const float* __restrict__ blob, const float* __restrict__ vo
 }
 
 // ---------------------------------------------------------------------------------------------
+// one field point's density in the reference-order form: density_lattice_kernel's and field_points_kernel<false>'s evaluation
+// ---------------------------------------------------------------------------------------------
+// The device functions of the fused kernel's FORM_F32 step, for a tile of 32 points (one per lane & 31; the two lane halves split
+// the K dimension of every dense layer, as in the sample loop), all 64 lanes converged: SparseConvNet.forward's sampling of the
+// four volume levels (:113-122; multiply-then-add taps) and the sigma feature layer (test_forward, trainhead.py:61-76; ELU(bias),
+// the same bits, where all 32 lanes' features are zero), Projector.compute of the three views (BaseRender.py:326-363),
+// fused_mean_variance and the density branch (rgbhead.out_geometry_fc + masked_fill).  `lds` holds the reference-order head image
+// (gpnerf_pack_head_ref).  The lattice kernel's and the density-only query's sigma at one world point are the same bits because
+// this is the only evaluation either of them has; field_points_kernel<true> spells the same steps out (see there).
+DEV void field_point_ref(const float* lds, int lane, int half, const __attribute__((address_space(4))) FrameK& fr, float px, float py,
+                         float pz, float gx, float gy, float gz, bool neg, float& sigma) {
+    float fv[64], sf[32];
+#pragma unroll
+    for (int l = 0; l < GPNERF_LEVELS; ++l)
+        gather_volume<true>(fr.vol[l], fr.vol_dhw[l][0], fr.vol_dhw[l][1], fr.vol_dhw[l][2], gx, gy, gz, half, fv + 16 * l);
+    unsigned bits = 0u;
+#pragma unroll
+    for (int t = 0; t < 64; t += 2) bits |= __builtin_bit_cast(unsigned, fv[t]) | __builtin_bit_cast(unsigned, fv[t + 1]);
+    if (__all((bits << 1) == 0u)) geo_bias_ref(lds, lane, sf);
+    else {
+        float fk[64];
+#pragma unroll
+        for (int l = 0; l < GPNERF_LEVELS; ++l) interleave16(fv + 16 * l, fk + 16 * l);
+        geo_eval_ref(lds, lane, fk, sf);
+    }
+    float xv[NV][18], vrgb[NV][3], mv[36];
+    const float nvalid = gather_views<FORM_F32>(fr, px, py, pz, neg, half, xv, vrgb);
+    mean_var_ref(xv, mv);
+    mlp_density_ref(lds, lane, sf, mv, nvalid, sigma);
+}
+
+// ---------------------------------------------------------------------------------------------
 // the inference renderer's density lattice (libs/renders/demo_render.py:249-311,366-371; use_rgbhead=False)
 // ---------------------------------------------------------------------------------------------
-// One lane per lattice point, 32 points per wavefront (the two lane halves split the K dimension of every dense layer, as in the
-// sample loop).  A tile is a brick of LAT_BY x LAT_BZ points of one x-slice of the PADDED cube, so that neighbouring lanes sample
-// neighbouring texels and voxels (shared L2 lines); the tiles of the padding and the tiles whose 32 points are all culled only
-// store zeros -- no gather, no matrix work.  The kept points run the reference-order form's device code (the fused kernel's
-// FORM_F32 step without its colour branch): grid_sample of the occupancy (the cull), the four volume levels (multiply-then-add
-// taps), the sigma feature layer, Projector.compute of the three views, mean / variance and the density branch.
+// One lane per lattice point, 32 points per wavefront.  A tile is a brick of LAT_BY x LAT_BZ points of one x-slice of the PADDED
+// cube, so that neighbouring lanes sample neighbouring texels and voxels (shared L2 lines); the tiles of the padding and the tiles
+// whose 32 points are all culled only store zeros -- no gather, no matrix work.  The kept points run field_point_ref after
+// the cull (grid_sample of the occupancy, or the caller's mask).
 constexpr int LAT_BY = 4, LAT_BZ = 8, LAT_WAVES = 8;
 struct LatticeArgs {          // the kernel's only argument, read through the kernarg segment (as render_fused_kernel's)
     FrameK fr;
@@ -2790,26 +2820,8 @@ __global__ void __launch_bounds__(LAT_WAVES * 64, LAT_WAVES / 4) density_lattice
         float alpha = 0.f;
         const unsigned long long kept = __ballot(keep) & 0xffffffffull;
         if (kept) {
-            // SparseConvNet.forward sampling (:113-122) and the sigma feature layer: test_forward (trainhead.py:61-76)
-            float fv[64], sf[32];
-#pragma unroll
-            for (int l = 0; l < GPNERF_LEVELS; ++l)
-                gather_volume<true>(fr.vol[l], fr.vol_dhw[l][0], fr.vol_dhw[l][1], fr.vol_dhw[l][2], gx, gy, gz, half, fv + 16 * l);
-            unsigned bits = 0u;
-#pragma unroll
-            for (int t = 0; t < 64; t += 2) bits |= __builtin_bit_cast(unsigned, fv[t]) | __builtin_bit_cast(unsigned, fv[t + 1]);
-            if (__all((bits << 1) == 0u)) geo_bias_ref(lds, lane, sf);      // all volume features zero: ELU(bias), same bits
-            else {
-                float fk[64];
-#pragma unroll
-                for (int l = 0; l < GPNERF_LEVELS; ++l) interleave16(fv + 16 * l, fk + 16 * l);
-                geo_eval_ref(lds, lane, fk, sf);
-            }
-            // Projector.compute (BaseRender.py:326-363), fused_mean_variance, rgbhead.out_geometry_fc + masked_fill
-            float xv[NV][18], vrgb[NV][3], mv[36], sigma;
-            const float nvalid = gather_views<FORM_F32>(fr, px, py, pz, kt->neg != 0, half, xv, vrgb);
-            mean_var_ref(xv, mv);
-            mlp_density_ref(lds, lane, sf, mv, nvalid, sigma);
+            float sigma;
+            field_point_ref(lds, lane, half, fr, px, py, pz, gx, gy, gz, kt->neg != 0, sigma);
             alpha = keep ? 1.f - expf(-sigma) : 0.f;                    // sigma2alpha (demo_render.py:315-316)
         }
         if (half == 0 && in_cube) kt->cube[((long)x * PY + y) * PZ + z] = alpha;
@@ -2820,13 +2832,11 @@ __global__ void __launch_bounds__(LAT_WAVES * 64, LAT_WAVES / 4) density_lattice
 // ---------------------------------------------------------------------------------------------
 // the radiance field at caller-given points: NeRFHead.forward (trainhead.py:159-163) in the reference-order form
 // ---------------------------------------------------------------------------------------------
-// One lane per point, 32 consecutive points of the caller's list per wavefront (the two lane halves split K, as in the sample loop
-// and density_lattice_kernel); persistent workgroups, the reference-order head image staged once per workgroup.  Each point runs
-// the same device functions as the fused kernel's FORM_F32 step and the lattice kernel: the four volume levels (multiply-then-add
-// taps; ELU(bias) where all 32 lanes' features are zero), the sigma feature layer, Projector.compute of the three views, mean /
-// variance, the density branch and -- unless COLOUR is false -- the colour branch.  Optional: the occupancy cull of
-// GPNERF_FLAG_OCC_CULL (a culled point gets zeros; a tile whose 32 points are all culled stores zeros, no gather, no matrix work),
-// and points given in index units of a padded lattice cube (marching-cubes vertices), mapped as lattice_axis() makes its values.
+// One lane per point, 32 consecutive points of the caller's list per wavefront; persistent workgroups, the reference-order head
+// image staged once per workgroup.  Each point runs field_point_ref, as the lattice kernel's, or with COLOUR the same steps and
+// the colour branch.  Optional: the occupancy cull of GPNERF_FLAG_OCC_CULL (a culled point gets zeros; a tile whose 32 points are
+// all culled stores zeros, no gather, no matrix work), and points given in index units of a padded lattice cube (marching-cubes
+// vertices), mapped as lattice_axis() makes its values.
 constexpr int QRY_WAVES = 8;
 struct QueryArgs {            // the kernel's only argument, read through the kernarg segment (as render_fused_kernel's)
     FrameK fr;
@@ -2873,27 +2883,28 @@ __global__ void __launch_bounds__(QRY_WAVES * 64, QRY_WAVES / 4) field_points_ke
             keep = keep && sample_occupancy(fr.occ, fr.vol_dhw[0][0], fr.vol_dhw[0][1], fr.vol_dhw[0][2], gx, gy, gz) > 0.f;
         float sigma = 0.f, rgb[3] = {0.f, 0.f, 0.f};
         if (__ballot(keep) & 0xffffffffull) {
-            // SparseConvNet.forward sampling (:113-122) and the sigma feature layer: test_forward (trainhead.py:61-76)
-            float fv[64], sf[32];
-#pragma unroll
-            for (int l = 0; l < GPNERF_LEVELS; ++l)
-                gather_volume<true>(fr.vol[l], fr.vol_dhw[l][0], fr.vol_dhw[l][1], fr.vol_dhw[l][2], gx, gy, gz, half, fv + 16 * l);
-            unsigned bits = 0u;
-#pragma unroll
-            for (int t = 0; t < 64; t += 2) bits |= __builtin_bit_cast(unsigned, fv[t]) | __builtin_bit_cast(unsigned, fv[t + 1]);
-            if (__all((bits << 1) == 0u)) geo_bias_ref(lds, lane, sf);      // all volume features zero: ELU(bias), same bits
+            if constexpr (!COLOUR) field_point_ref(lds, lane, half, fr, px, py, pz, gx, gy, gz, kt->neg != 0, sigma);
             else {
-                float fk[64];
+                // field_point_ref's steps spelled out, then the colour branch: through a shared function this instantiation
+                // measured 0.7 % slower colouring a mesh's vertices (profiles/r12); as it stands its code is unchanged
+                float fv[64], sf[32];
 #pragma unroll
-                for (int l = 0; l < GPNERF_LEVELS; ++l) interleave16(fv + 16 * l, fk + 16 * l);
-                geo_eval_ref(lds, lane, fk, sf);
-            }
-            // Projector.compute (BaseRender.py:326-363), fused_mean_variance, the density branch + masked_fill, the colour branch
-            float xv[NV][18], vrgb[NV][3], mv[36];
-            const float nvalid = gather_views<FORM_F32>(fr, px, py, pz, kt->neg != 0, half, xv, vrgb);
-            mean_var_ref(xv, mv);
-            mlp_density_ref(lds, lane, sf, mv, nvalid, sigma);
-            if constexpr (COLOUR) {
+                for (int l = 0; l < GPNERF_LEVELS; ++l)
+                    gather_volume<true>(fr.vol[l], fr.vol_dhw[l][0], fr.vol_dhw[l][1], fr.vol_dhw[l][2], gx, gy, gz, half, fv + 16 * l);
+                unsigned bits = 0u;
+#pragma unroll
+                for (int t = 0; t < 64; t += 2) bits |= __builtin_bit_cast(unsigned, fv[t]) | __builtin_bit_cast(unsigned, fv[t + 1]);
+                if (__all((bits << 1) == 0u)) geo_bias_ref(lds, lane, sf);
+                else {
+                    float fk[64];
+#pragma unroll
+                    for (int l = 0; l < GPNERF_LEVELS; ++l) interleave16(fv + 16 * l, fk + 16 * l);
+                    geo_eval_ref(lds, lane, fk, sf);
+                }
+                float xv[NV][18], vrgb[NV][3], mv[36];
+                const float nvalid = gather_views<FORM_F32>(fr, px, py, pz, kt->neg != 0, half, xv, vrgb);
+                mean_var_ref(xv, mv);
+                mlp_density_ref(lds, lane, sf, mv, nvalid, sigma);
                 Stamps st;
                 mlp_colour_ref(lds, lane, xv, mv, rgb, st);
             }
@@ -3272,50 +3283,112 @@ float pack_scale(int L, int c) {
     }
 }
 
-void pack_layer(int L, const float* W, const float* b, int n_out, int n_in, float* blob) {
+// The head's 11 MFMA layers, once: the GpnerfHeadParams tensors a layer packs and their PyTorch shape [n_out][n_in].  The three
+// packers and gpnerf_head_layout walk this table.  BS and BV are the two column groups of base_fc.0 ([mean, var] and per view); BV's
+// chain runs onto BS's, so the layer's bias is packed with BS alone.
+struct HeadLayer {
+    int L;
+    const float* GpnerfHeadParams::*W;
+    const float* GpnerfHeadParams::*b;
+    int n_out, n_in;
+};
+typedef GpnerfHeadParams HP;
+constexpr HeadLayer HEAD_LAYERS[gpl::NLAYER] = {
+    {gpl::GEO, &HP::geo_w, &HP::geo_b, 64, 128}, {gpl::D1, &HP::d1_w, &HP::d1_b, 64, 134}, {gpl::D2, &HP::d2_w, &HP::d2_b, 32, 64},
+    {gpl::D3, &HP::d3_w, &HP::d3_b, 16, 32},     {gpl::BS, &HP::b1_w, &HP::b1_b, 64, 105}, {gpl::BV, &HP::b1_w, nullptr, 64, 105},
+    {gpl::B2, &HP::b2_w, &HP::b2_b, 32, 64},     {gpl::V1, &HP::v1_w, &HP::v1_b, 32, 32},  {gpl::V2, &HP::v2_w, &HP::v2_b, 32, 32},
+    {gpl::R1, &HP::r1_w, &HP::r1_b, 32, 96},     {gpl::R2, &HP::r2_w, &HP::r2_b, 16, 32}};
+// What can be checked at compile time: row i is layer i; n_out fits the layer's tiles and no k-step names a column at or past n_in
+// (head_layout.h); the rows' distinct weight tensors, each with a bias, and the two VALU tails (d4, r3: pack_tails) number the
+// tensors of GpnerfHeadParams, so a tensor pair added there fails here until a row packs it.  Not checked: an n_in larger than the
+// tensor's, or a weight paired with another layer's bias -- those change the images' bytes, which tests/test_head_image.py pins.
+constexpr bool head_layers_ok() {
+    size_t tensors = 4;
+    for (int i = 0; i < gpl::NLAYER; ++i) {
+        const HeadLayer& s = HEAD_LAYERS[i];
+        if (s.L != i || s.n_out > 32 * gpl::MT[i]) return false;
+        for (int t = 0; t < gpl::NT[i]; ++t)
+            for (int h = 0; h < 2; ++h)
+                if (gpl::col_of(i, t, h) >= s.n_in || gpr::col_of(i, t, h) >= s.n_in) return false;
+        bool first = true;
+        for (int j = 0; j < i; ++j) first = first && HEAD_LAYERS[j].W != s.W;
+        if (first != (s.b != nullptr)) return false;
+        tensors += first ? 2 : 0;
+    }
+    return tensors == sizeof(GpnerfHeadParams) / sizeof(const float*);
+}
+static_assert(head_layers_ok(), "HEAD_LAYERS disagrees with head_layout.h or leaves a tensor of GpnerfHeadParams unpacked");
+
+bool head_params_ok(const GpnerfHeadParams* p) {
+    if (!p) return false;
+    const float* const* all = reinterpret_cast<const float* const*>(p);
+    for (size_t i = 0; i < sizeof(GpnerfHeadParams) / sizeof(float*); ++i)
+        if (!all[i]) return false;
+    return true;
+}
+
+// What tells the two fp32 images apart (head_layout.h): gpl -- tile row i carries output feature i, accumulator slot [h][r] feature
+// ft(r, h), the scaled domain of elus(); gpr, the reference-order image -- row i carries gpr::feat_of_row(i), k-step t the columns
+// (2t, 2t + 1), slot [h][r] feature 2r + h, nothing is scaled.
+struct HeadOrder {
+    int (*feat_of_row)(int i);
+    int (*col_of)(int L, int t, int h);
+    int (*feat_of_slot)(int r, int h);       // of a bias tile, and of the VALU tails' weights
+    bool scaled;
+};
+const HeadOrder ORDER_GPL = {[](int i) { return i; }, gpl::col_of, gpl::ft, true};
+const HeadOrder ORDER_GPR = {gpr::feat_of_row, gpr::col_of, [](int r, int h) { return 2 * r + h; }, false};
+
+// tile m of a layer's biases, [half][16] as the accumulator holds them
+void pack_bias_tile(const float* b, int n_out, int m, int (*feat_of_slot)(int, int), bool scaled, float* bt) {
+    for (int h = 0; h < 2; ++h)
+        for (int r = 0; r < 16; ++r) {
+            const int row = 32 * m + feat_of_slot(r, h);
+            bt[h * 16 + r] = (b && row < n_out) ? (scaled ? b[row] * PACK_LOG2E : b[row]) : 0.f;
+        }
+}
+
+// one layer of an fp32 image: per 32-row tile the A operands as [group of 4 k-steps][lane][4] (+ a two-wide remainder), then the biases
+void pack_layer(const HeadOrder& o, const HeadLayer& s, const GpnerfHeadParams* p, float* blob) {
+    const int L = s.L, NT = gpl::NT[L], NG = NT / 4;
+    const float *W = p->*s.W, *b = s.b ? p->*s.b : nullptr;
     for (int m = 0; m < gpl::MT[L]; ++m) {
-        float* wt = blob + gpl::w_off(L) + m * gpl::NT[L] * 64;
-        const int NT = gpl::NT[L], NG = NT / 4;
+        float* wt = blob + gpl::w_off(L) + m * NT * 64;
         for (int t = 0; t < NT; ++t)
             for (int lane = 0; lane < 64; ++lane) {
-                const int row = 32 * m + (lane & 31), h = lane >> 5;
-                const int c = gpl::col_of(L, t, h);
-                const float v = (row < n_out && col_ok(c, n_in)) ? W[(size_t)row * n_in + c] * pack_scale(L, c) : 0.f;
+                const int row = 32 * m + o.feat_of_row(lane & 31), h = lane >> 5;
+                const int c = o.col_of(L, t, h);
+                float v = (row < s.n_out && col_ok(c, s.n_in)) ? W[(size_t)row * s.n_in + c] : 0.f;
+                if (o.scaled) v *= pack_scale(L, c);
                 const int g = t / 4;
                 if (g < NG) wt[(g * 64 + lane) * 4 + (t & 3)] = v;
                 else wt[NG * 256 + lane * 2 + (t - 4 * NG)] = v;
             }
-        float* bt = blob + gpl::b_off(L) + m * 32;
-        for (int h = 0; h < 2; ++h)
-            for (int r = 0; r < 16; ++r) {
-                const int row = 32 * m + gpl::ft(r, h);
-                bt[h * 16 + r] = (b && row < n_out) ? b[row] * PACK_LOG2E : 0.f;
-            }
+        pack_bias_tile(b, s.n_out, m, o.feat_of_slot, o.scaled, blob + gpl::b_off(L) + m * 32);
     }
 }
 
-// reference-order image (head_layout.h gpr): tile row i carries output feature gpr::feat_of_row(i), k-step t the columns
-// (2t, 2t+1) (gpr::col_of), nothing is scaled, the bias tile holds feature 2r + h at [h][r]
-void pack_layer_ref(int L, const float* W, const float* b, int n_out, int n_in, float* blob) {
-    for (int m = 0; m < gpl::MT[L]; ++m) {
-        float* wt = blob + gpl::w_off(L) + m * gpl::NT[L] * 64;
-        const int NT = gpl::NT[L], NG = NT / 4;
-        for (int t = 0; t < NT; ++t)
-            for (int lane = 0; lane < 64; ++lane) {
-                const int row = 32 * m + gpr::feat_of_row(lane & 31), h = lane >> 5;
-                const int c = gpr::col_of(L, t, h);
-                const float v = (row < n_out && col_ok(c, n_in)) ? W[(size_t)row * n_in + c] : 0.f;
-                const int g = t / 4;
-                if (g < NG) wt[(g * 64 + lane) * 4 + (t & 3)] = v;
-                else wt[NG * 256 + lane * 2 + (t - 4 * NG)] = v;
-            }
-        float* bt = blob + gpl::b_off(L) + m * 32;
-        for (int h = 0; h < 2; ++h)
-            for (int r = 0; r < 16; ++r) {
-                const int row = 32 * m + 2 * r + h;
-                bt[h * 16 + r] = (b && row < n_out) ? b[row] : 0.f;
-            }
-    }
+// the VALU tails behind the bias tiles (the same arrangement in the fp32 and the split image): density 16 -> 1 and colour 16 -> 3,
+// weights as [out][half][8] in the order the last accumulator holds its features, times `scale`; then the biases
+static_assert(gph::D4_B - gph::D4_W == gpl::D4_B - gpl::D4_W && gph::R3_W - gph::D4_W == gpl::R3_W - gpl::D4_W &&
+              gph::R3_B - gph::D4_W == gpl::R3_B - gpl::D4_W, "the split image's tails are laid out as the fp32 image's");
+void pack_tails(const GpnerfHeadParams* p, int (*feat_of_slot)(int, int), float scale, float* tails) {
+    float *d4_w = tails, *d4_b = tails + (gpl::D4_B - gpl::D4_W), *r3_w = tails + (gpl::R3_W - gpl::D4_W), *r3_b = tails + (gpl::R3_B - gpl::D4_W);
+    for (int h = 0; h < 2; ++h)
+        for (int r = 0; r < 8; ++r) {
+            d4_w[h * 8 + r] = p->d4_w[feat_of_slot(r, h)] * scale;
+            for (int o = 0; o < 3; ++o) r3_w[o * 16 + h * 8 + r] = p->r3_w[o * 16 + feat_of_slot(r, h)] * scale;
+        }
+    d4_b[0] = p->d4_b[0];
+    for (int o = 0; o < 3; ++o) r3_b[o] = p->r3_b[o];
+}
+
+int pack_head_fp32(const HeadOrder& o, const GpnerfHeadParams* p, float* blob) {
+    if (!head_params_ok(p) || !blob) return GPNERF_E_ARG;
+    memset(blob, 0, sizeof(float) * gpl::BLOB_FLOATS);
+    for (const HeadLayer& s : HEAD_LAYERS) pack_layer(o, s, p, blob);
+    pack_tails(p, o.feat_of_slot, o.scaled ? PACK_LN2 : 1.f, blob + gpl::D4_W);
+    return GPNERF_OK;
 }
 
 // Launch geometry of the fused kernel.  One workgroup is resident per CU (LDS), a wave's step time depends on how many
@@ -3345,9 +3418,10 @@ Geometry choose_geometry(int64_t tiles, int S, bool may_split, size_t ws_bytes, 
     }
     return best;
 }
-// persistent workgroups of GPNERF_MAX_WAVES wavefronts: one per CU, no more than the tiles fill
-unsigned full_grid(int64_t tiles, int n_cus) {
-    const int64_t wg = (tiles + GPNERF_MAX_WAVES - 1) / GPNERF_MAX_WAVES;
+// persistent workgroups of `waves` wavefronts, a tile each at a time: one per CU (the head image fills most of its LDS), no more
+// than the tiles fill
+unsigned full_grid(int64_t tiles, int n_cus, int waves = GPNERF_MAX_WAVES) {
+    const int64_t wg = (tiles + waves - 1) / waves;
     return (unsigned)(wg < n_cus ? wg : n_cus);
 }
 
@@ -3758,6 +3832,8 @@ bool to_framek(const GpnerfFrame* f, FrameK& k, bool need_vol, bool need_img) {
     for (int l = GPNERF_FOLD_FIRST_LEVEL; l < GPNERF_LEVELS; ++l) k.vol_fold[l] = fold ? f->vol_folded[l] : nullptr;
     return true;
 }
+// the progressive renderer's grid coordinates divide by a literal, not by the frame's voxel size (demo_render.py:91 `xyz / 0.005`)
+void use_demo_voxel(FrameK& k) { k.voxel[0] = k.voxel[1] = k.voxel[2] = 0.005f; }
 
 OutK to_outk(const GpnerfOutputs* o, const int32_t* order = nullptr) {
     OutK k;
@@ -3915,22 +3991,12 @@ GPNERF_DIAG_EXPORTS        /* nothing in the product (csrc/nodiag/gpnerf_diag.h)
 
 int gpnerf_head_layout(int32_t* table) {
     if (!table) return GPNERF_E_ARG;
-    for (int l = 0; l < gpl::NLAYER; ++l) {
-        table[4 * l + 0] = gpl::NT[l]; table[4 * l + 1] = gpl::MT[l];
+    for (const HeadLayer& s : HEAD_LAYERS) {
+        int32_t* row = table + 4 * s.L;
+        row[0] = gpl::NT[s.L]; row[1] = gpl::MT[s.L]; row[2] = gpl::w_off(s.L); row[3] = gpl::b_off(s.L);
     }
-    table[4 * gpl::GEO + 2] = gpl::w_off(gpl::GEO); table[4 * gpl::GEO + 3] = gpl::b_off(gpl::GEO);
-    table[4 * gpl::D1 + 2] = gpl::w_off(gpl::D1);   table[4 * gpl::D1 + 3] = gpl::b_off(gpl::D1);
-    table[4 * gpl::D2 + 2] = gpl::w_off(gpl::D2);   table[4 * gpl::D2 + 3] = gpl::b_off(gpl::D2);
-    table[4 * gpl::D3 + 2] = gpl::w_off(gpl::D3);   table[4 * gpl::D3 + 3] = gpl::b_off(gpl::D3);
-    table[4 * gpl::BS + 2] = gpl::w_off(gpl::BS);   table[4 * gpl::BS + 3] = gpl::b_off(gpl::BS);
-    table[4 * gpl::BV + 2] = gpl::w_off(gpl::BV);   table[4 * gpl::BV + 3] = gpl::b_off(gpl::BV);
-    table[4 * gpl::B2 + 2] = gpl::w_off(gpl::B2);   table[4 * gpl::B2 + 3] = gpl::b_off(gpl::B2);
-    table[4 * gpl::V1 + 2] = gpl::w_off(gpl::V1);   table[4 * gpl::V1 + 3] = gpl::b_off(gpl::V1);
-    table[4 * gpl::V2 + 2] = gpl::w_off(gpl::V2);   table[4 * gpl::V2 + 3] = gpl::b_off(gpl::V2);
-    table[4 * gpl::R1 + 2] = gpl::w_off(gpl::R1);   table[4 * gpl::R1 + 3] = gpl::b_off(gpl::R1);
-    table[4 * gpl::R2 + 2] = gpl::w_off(gpl::R2);   table[4 * gpl::R2 + 3] = gpl::b_off(gpl::R2);
-    table[4 * gpl::NLAYER + 0] = gpl::D4_W; table[4 * gpl::NLAYER + 1] = gpl::D4_B;
-    table[4 * gpl::NLAYER + 2] = gpl::R3_W; table[4 * gpl::NLAYER + 3] = gpl::R3_B;
+    int32_t* tails = table + 4 * gpl::NLAYER;
+    tails[0] = gpl::D4_W; tails[1] = gpl::D4_B; tails[2] = gpl::R3_W; tails[3] = gpl::R3_B;
     return GPNERF_OK;
 }
 
@@ -3944,82 +4010,24 @@ const char* gpnerf_strerror(int code) {
     }
 }
 
-int gpnerf_pack_head(const GpnerfHeadParams* p, float* blob) {
-    if (!p || !blob) return GPNERF_E_ARG;
-    const float* const* all = reinterpret_cast<const float* const*>(p);
-    for (size_t i = 0; i < sizeof(GpnerfHeadParams) / sizeof(float*); ++i)
-        if (!all[i]) return GPNERF_E_ARG;
-    memset(blob, 0, sizeof(float) * gpl::BLOB_FLOATS);
-    pack_layer(gpl::GEO, p->geo_w, p->geo_b, 64, 128, blob);
-    pack_layer(gpl::D1, p->d1_w, p->d1_b, 64, 134, blob);
-    pack_layer(gpl::D2, p->d2_w, p->d2_b, 32, 64, blob);
-    pack_layer(gpl::D3, p->d3_w, p->d3_b, 16, 32, blob);
-    pack_layer(gpl::BS, p->b1_w, p->b1_b, 64, 105, blob);     // [mean,var] columns + the layer's bias
-    pack_layer(gpl::BV, p->b1_w, nullptr, 64, 105, blob);     // per-view columns, accumulates onto BS
-    pack_layer(gpl::B2, p->b2_w, p->b2_b, 32, 64, blob);
-    pack_layer(gpl::V1, p->v1_w, p->v1_b, 32, 32, blob);
-    pack_layer(gpl::V2, p->v2_w, p->v2_b, 32, 32, blob);
-    pack_layer(gpl::R1, p->r1_w, p->r1_b, 32, 96, blob);
-    pack_layer(gpl::R2, p->r2_w, p->r2_b, 16, 32, blob);
-    for (int h = 0; h < 2; ++h)
-        for (int r = 0; r < 8; ++r) {
-            blob[gpl::D4_W + h * 8 + r] = p->d4_w[gpl::ft(r, h)] * PACK_LN2;
-            for (int o = 0; o < 3; ++o) blob[gpl::R3_W + o * 16 + h * 8 + r] = p->r3_w[o * 16 + gpl::ft(r, h)] * PACK_LN2;
-        }
-    blob[gpl::D4_B] = p->d4_b[0];
-    for (int o = 0; o < 3; ++o) blob[gpl::R3_B + o] = p->r3_b[o];
-    return GPNERF_OK;
-}
-
-int gpnerf_pack_head_ref(const GpnerfHeadParams* p, float* blob) {
-    if (!p || !blob) return GPNERF_E_ARG;
-    const float* const* all = reinterpret_cast<const float* const*>(p);
-    for (size_t i = 0; i < sizeof(GpnerfHeadParams) / sizeof(float*); ++i)
-        if (!all[i]) return GPNERF_E_ARG;
-    memset(blob, 0, sizeof(float) * gpl::BLOB_FLOATS);
-    pack_layer_ref(gpl::GEO, p->geo_w, p->geo_b, 64, 128, blob);
-    pack_layer_ref(gpl::D1, p->d1_w, p->d1_b, 64, 134, blob);
-    pack_layer_ref(gpl::D2, p->d2_w, p->d2_b, 32, 64, blob);
-    pack_layer_ref(gpl::D3, p->d3_w, p->d3_b, 16, 32, blob);
-    pack_layer_ref(gpl::BS, p->b1_w, p->b1_b, 64, 105, blob);     // [mean, var] columns; the bias tile is added after BV's chain
-    pack_layer_ref(gpl::BV, p->b1_w, nullptr, 64, 105, blob);
-    pack_layer_ref(gpl::B2, p->b2_w, p->b2_b, 32, 64, blob);
-    pack_layer_ref(gpl::V1, p->v1_w, p->v1_b, 32, 32, blob);
-    pack_layer_ref(gpl::V2, p->v2_w, p->v2_b, 32, 32, blob);
-    pack_layer_ref(gpl::R1, p->r1_w, p->r1_b, 32, 96, blob);
-    pack_layer_ref(gpl::R2, p->r2_w, p->r2_b, 16, 32, blob);
-    for (int h = 0; h < 2; ++h)
-        for (int r = 0; r < 8; ++r) {
-            blob[gpl::D4_W + h * 8 + r] = p->d4_w[2 * r + h];
-            for (int o = 0; o < 3; ++o) blob[gpl::R3_W + o * 16 + h * 8 + r] = p->r3_w[o * 16 + 2 * r + h];
-        }
-    blob[gpl::D4_B] = p->d4_b[0];
-    for (int o = 0; o < 3; ++o) blob[gpl::R3_B + o] = p->r3_b[o];
-    return GPNERF_OK;
-}
+int gpnerf_pack_head(const GpnerfHeadParams* p, float* blob) { return pack_head_fp32(ORDER_GPL, p, blob); }
+int gpnerf_pack_head_ref(const GpnerfHeadParams* p, float* blob) { return pack_head_fp32(ORDER_GPR, p, blob); }
 
 int64_t gpnerf_head_blob_split_floats(void) { return gph::BLOB_WORDS; }
 
 int gpnerf_pack_head_split(const GpnerfHeadParams* p, float* blob) {
-    if (!p || !blob) return GPNERF_E_ARG;
-    const float* const* all = reinterpret_cast<const float* const*>(p);
-    for (size_t i = 0; i < sizeof(GpnerfHeadParams) / sizeof(float*); ++i)
-        if (!all[i]) return GPNERF_E_ARG;
+    if (!head_params_ok(p) || !blob) return GPNERF_E_ARG;
     memset(blob, 0, sizeof(float) * gph::BLOB_WORDS);
-    struct Spec { int L; const float *W, *b; int n_out, n_in; };
-    const Spec specs[] = {{gpl::GEO, p->geo_w, p->geo_b, 64, 128}, {gpl::D1, p->d1_w, p->d1_b, 64, 134}, {gpl::D2, p->d2_w, p->d2_b, 32, 64},
-                          {gpl::D3, p->d3_w, p->d3_b, 16, 32},    {gpl::BS, p->b1_w, p->b1_b, 64, 105}, {gpl::BV, p->b1_w, nullptr, 64, 105},
-                          {gpl::B2, p->b2_w, p->b2_b, 32, 64},    {gpl::V1, p->v1_w, p->v1_b, 32, 32},  {gpl::V2, p->v2_w, p->v2_b, 32, 32},
-                          {gpl::R1, p->r1_w, p->r1_b, 32, 96},    {gpl::R2, p->r2_w, p->r2_b, 16, 32}};
     uint16_t* halfs = reinterpret_cast<uint16_t*>(blob);
-    for (const Spec& sp : specs) {
+    for (const HeadLayer& sp : HEAD_LAYERS) {
+        const float* W = p->*sp.W;
         for (int m = 0; m < gph::MT[sp.L]; ++m) {
             for (int st = 0; st < gph::NS[sp.L]; ++st) {
                 const size_t base = ((size_t)gph::w_off(sp.L) + (size_t)(m * gph::NS[sp.L] + st) * gph::STEP_WORDS) * 2;   // in halfs
                 for (int lane = 0; lane < 64; ++lane)
                     for (int j = 0; j < 8; ++j) {
                         const int row = 32 * m + (lane & 31), h = lane >> 5, c = gph::col_of(sp.L, st, j, h);
-                        const float v = (row < sp.n_out && c >= 0 && c < sp.n_in) ? sp.W[(size_t)row * sp.n_in + c] * pack_scale(sp.L, c) : 0.f;
+                        const float v = (row < sp.n_out && col_ok(c, sp.n_in)) ? W[(size_t)row * sp.n_in + c] * pack_scale(sp.L, c) : 0.f;
                         const _Float16 hi = f16_rtz(v);
                         const _Float16 lo = (_Float16)(v - (float)hi);
                         uint16_t hb, lb;
@@ -4028,21 +4036,10 @@ int gpnerf_pack_head_split(const GpnerfHeadParams* p, float* blob) {
                         halfs[base + 512 + lane * 8 + j] = lb;
                     }
             }
-            float* bt = blob + gph::b_off(sp.L) + m * 32;
-            for (int h = 0; h < 2; ++h)
-                for (int r = 0; r < 16; ++r) {
-                    const int row = 32 * m + gpl::ft(r, h);
-                    bt[h * 16 + r] = (sp.b && row < sp.n_out) ? sp.b[row] * PACK_LOG2E : 0.f;
-                }
+            pack_bias_tile(sp.b ? p->*sp.b : nullptr, sp.n_out, m, gpl::ft, true, blob + gph::b_off(sp.L) + m * 32);
         }
     }
-    for (int h = 0; h < 2; ++h)
-        for (int r = 0; r < 8; ++r) {
-            blob[gph::D4_W + h * 8 + r] = p->d4_w[gpl::ft(r, h)] * PACK_LN2;
-            for (int o = 0; o < 3; ++o) blob[gph::R3_W + o * 16 + h * 8 + r] = p->r3_w[o * 16 + gpl::ft(r, h)] * PACK_LN2;
-        }
-    blob[gph::D4_B] = p->d4_b[0];
-    for (int o = 0; o < 3; ++o) blob[gph::R3_B + o] = p->r3_b[o];
+    pack_tails(p, gpl::ft, PACK_LN2, blob + gph::D4_W);
     return GPNERF_OK;
 }
 
@@ -4082,7 +4079,7 @@ int gpnerf_render_fused(const GpnerfFrame* f, const float* rays, int64_t n_rays,
     int n_cus = 0;
     if (device_ready(&n_cus) != GPNERF_OK) return GPNERF_E_DEVICE;
     const RenderPlan p = plan_call(n_rays, n_samples, flags, n_cus, facts, workspace ? workspace_bytes : 0);
-    if (flags & GPNERF_FLAG_OCC_CULL) k.voxel[0] = k.voxel[1] = k.voxel[2] = 0.005f;   // demo_render.py:91 `xyz / 0.005`
+    if (flags & GPNERF_FLAG_OCC_CULL) use_demo_voxel(k);
 
     char* const ws = static_cast<char*>(workspace);
     auto at = [ws](const Region& r, size_t inner = 0) -> char* { return r.bytes ? ws + r.off + inner : nullptr; };
@@ -4387,7 +4384,7 @@ static int launch_lattice(const GpnerfFrame* f, const float* axis_x, const float
         return GPNERF_E_ARG;
     FrameK k;
     if (!to_framek(f, k, true, true)) return GPNERF_E_ARG;
-    if (!inside) k.voxel[0] = k.voxel[1] = k.voxel[2] = 0.005f;     // demo_render.py:91 `xyz / 0.005`, as under GPNERF_FLAG_OCC_CULL
+    if (!inside) use_demo_voxel(k);     // as under GPNERF_FLAG_OCC_CULL
     int n_cus = 0;
     if (device_ready(&n_cus) != GPNERF_OK) return GPNERF_E_DEVICE;
     LatticeArgs a;
@@ -4403,13 +4400,9 @@ static int launch_lattice(const GpnerfFrame* f, const float* axis_x, const float
     a.n_kept = reinterpret_cast<unsigned long long*>(n_kept);
     a.inside = inside;
     if (n_kept && !zero_async(n_kept, sizeof(int64_t), stream)) return GPNERF_E_LAUNCH;
-    // one workgroup per CU (the head image fills most of its LDS), persistent over the tiles
-    const long wgs = (a.n_tiles + LAT_WAVES - 1) / LAT_WAVES;
-    const unsigned grid = (unsigned)(wgs < n_cus ? wgs : n_cus);
-    if (inside)
-        hipLaunchKernelGGL(density_lattice_kernel<true>, dim3(grid), dim3(LAT_WAVES * 64), sizeof(float) * gpl::BLOB_FLOATS, S_(stream), a);
-    else
-        hipLaunchKernelGGL(density_lattice_kernel<false>, dim3(grid), dim3(LAT_WAVES * 64), sizeof(float) * gpl::BLOB_FLOATS, S_(stream), a);
+    const auto kernel = inside ? density_lattice_kernel<true> : density_lattice_kernel<false>;
+    hipLaunchKernelGGL(kernel, dim3(full_grid(a.n_tiles, n_cus, LAT_WAVES)), dim3(LAT_WAVES * 64), sizeof(float) * gpl::BLOB_FLOATS,
+                       S_(stream), a);
     return launch_status();
 }
 
@@ -4434,7 +4427,7 @@ int gpnerf_query_points(const GpnerfFrame* f, const float* pts, int64_t n_points
     if (!to_framek(f, k, true, true)) return GPNERF_E_ARG;
     if (n_points == 0) return GPNERF_OK;
     if (!pts || !raw) return GPNERF_E_ARG;
-    if (flags & GPNERF_FLAG_OCC_CULL) k.voxel[0] = k.voxel[1] = k.voxel[2] = 0.005f;   // demo_render.py:91 `xyz / 0.005`
+    if (flags & GPNERF_FLAG_OCC_CULL) use_demo_voxel(k);
     int n_cus = 0;
     if (device_ready(&n_cus) != GPNERF_OK) return GPNERF_E_DEVICE;
     QueryArgs a;
@@ -4452,13 +4445,9 @@ int gpnerf_query_points(const GpnerfFrame* f, const float* pts, int64_t n_points
     a.pad = lattice ? lattice[6] : 0.0;
     a.raw = raw;
     a.alpha = alpha;
-    // one workgroup per CU (the head image fills most of its LDS), persistent over the tiles
-    const long wgs = (a.n_tiles + QRY_WAVES - 1) / QRY_WAVES;
-    const unsigned grid = (unsigned)(wgs < n_cus ? wgs : n_cus);
-    if (flags & GPNERF_FLAG_DENSITY_ONLY)
-        hipLaunchKernelGGL(field_points_kernel<false>, dim3(grid), dim3(QRY_WAVES * 64), sizeof(float) * gpl::BLOB_FLOATS, S_(stream), a);
-    else
-        hipLaunchKernelGGL(field_points_kernel<true>, dim3(grid), dim3(QRY_WAVES * 64), sizeof(float) * gpl::BLOB_FLOATS, S_(stream), a);
+    const auto kernel = (flags & GPNERF_FLAG_DENSITY_ONLY) ? field_points_kernel<false> : field_points_kernel<true>;
+    hipLaunchKernelGGL(kernel, dim3(full_grid(a.n_tiles, n_cus, QRY_WAVES)), dim3(QRY_WAVES * 64), sizeof(float) * gpl::BLOB_FLOATS,
+                       S_(stream), a);
     return launch_status();
 }
 

@@ -103,6 +103,24 @@ def test_order_and_determinism(dense):
     assert empty["raw"].shape == (0, 4) and empty["rgb"].shape == (0, 3) and empty["alpha"].shape == (0,)
 
 
+def test_density_only_sigma_is_the_full_querys_at_the_tile_edges(dense):
+    """field_points_kernel<false> against <true> where a tile is ragged: a lone tail lane, one exact tile, a tile plus a one-point
+    tail, three tiles with a ragged tail -- there the first tile lies far outside the volumes (all 32 lanes' features zero: the
+    ELU(bias) exit) and the other two do not."""
+    N = dense.pts.shape[0]
+    hot = int(dense.raw[:, 3].argmax())                                # a point with sigma > 0: point 0, or the second tile's first
+    for n in (1, 32, 33, 95):
+        first = 32 if n == 95 else 0
+        idx = (hot - first + torch.arange(n, device=DEV)) % N
+        pts = dense.pts.index_select(0, idx).contiguous()
+        pts[:first] += 1000.0
+        dens = F.query_points(dense.fr, pts, want=("sigma",))
+        full = F.query_points(dense.fr, pts, want=("rgb", "sigma"))
+        assert dens["sigma"].shape == (n,) and torch.equal(dens["sigma"], full["sigma"]), n
+        assert float(full["sigma"][first]) > 0, n
+        assert not bool(full["sigma"][:first].any()), "no view sees the far points: sigma must be exactly 0"
+
+
 def test_many_rounds_of_wavefronts(dense):
     """>= 2 M points (many rounds of the persistent workgroups): the 131 072 sample points 16 times, shuffled"""
     reps = 16

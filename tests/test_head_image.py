@@ -420,3 +420,41 @@ def test_split_head_image_reproduces_the_reference_head(pkg, oracle, syn):
     ref = oracle.head_forward(head, vol, feat, mask)
     err = np.abs(got - ref).max()
     assert err < 3e-5, err          # hi/lo split keeps ~22 significant bits: fp32-class accuracy
+
+
+# ---- the three images and the layout table, byte for byte -----------------------------------------------------------------
+def packed_hashes(L):
+    """SHA-256 of the three packed images and of gpnerf_head_layout's table for one seeded GpnerfHeadParams: RandomState(0),
+    standard normal, L.HEAD_FIELDS order (weight, then bias), L.HEAD_SHAPES shapes."""
+    import hashlib
+    lib = L.lib()
+    rs = np.random.RandomState(0)
+    params, keep = L.GpnerfHeadParams(), []
+    for short, _ in L.HEAD_FIELDS:
+        n_out, n_in = L.HEAD_SHAPES[short]
+        for fld, shape in (("_w", (n_out, n_in)), ("_b", (n_out,))):
+            a = np.ascontiguousarray(rs.standard_normal(shape), np.float32)
+            keep.append(a)
+            setattr(params, short + fld, a.ctypes.data_as(L.FP))
+    out = {}
+    for name, pack, n in (("gpnerf_pack_head", lib.gpnerf_pack_head, lib.gpnerf_head_blob_floats()),
+                          ("gpnerf_pack_head_ref", lib.gpnerf_pack_head_ref, lib.gpnerf_head_blob_floats()),
+                          ("gpnerf_pack_head_split", lib.gpnerf_pack_head_split, lib.gpnerf_head_blob_split_floats())):
+        blob = np.full(n, np.nan, np.float32)           # the packers own every word, padding included
+        assert pack(C.byref(params), blob.ctypes.data_as(L.FP)) == 0
+        out[name] = hashlib.sha256(blob.tobytes()).hexdigest()
+    table = (C.c_int32 * 48)()
+    assert lib.gpnerf_head_layout(table) == 0
+    out["gpnerf_head_layout"] = hashlib.sha256(np.array(list(table), "<i4").tobytes()).hexdigest()
+    return out
+
+
+def test_packed_images_and_layout_table_are_the_recorded_bytes(pkg):
+    """The emulations above read the images the way the kernels do, so they would not notice a change in a padding word or in
+    a slot no kernel reads.  tests/golden/head/blob_sha256.json holds the hashes recorded before the packers were moved onto one
+    layer table; the packers are host code built without fused multiply-adds, so the bytes do not depend on the machine."""
+    import json
+    import os
+    with open(os.path.join(os.path.dirname(__file__), "golden", "head", "blob_sha256.json")) as f:
+        want = json.load(f)
+    assert packed_hashes(pkg._lib) == want
