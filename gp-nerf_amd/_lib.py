@@ -140,6 +140,12 @@ DIST_MAX_THRESHOLDS, DIST_DOUBLES = 4, 10
 RASTER_DRAWN, RASTER_SKIPPED_VERTEX, RASTER_SKIPPED_AREA, RASTER_PIXELS = range(4)
 SILHOUETTE_COVERED, SILHOUETTE_GT, SILHOUETTE_BOTH, SILHOUETTE_EITHER, SILHOUETTE_IGNORED, SILHOUETTE_COUNTS = range(6)
 RASTER_MAX_VIEWS, RASTER_MAX_ATTRS = 8, 4
+# gpnerf_mesh_simplify_count's stats, the workspace's status word and its values (include/gpnerf_hip.h GPNERF_SIMPLIFY_*)
+SIMPLIFY_STATS = ("vertices_out", "faces_out", "faces_invalid", "faces_collapsed", "faces_cancelled", "faces_duplicate", "clusters_clamped",
+                  "clusters_dropped")
+SIMPLIFY_HDR_STATUS = 12
+SIMPLIFY_COUNTING, SIMPLIFY_COUNTED, SIMPLIFY_EMITTED, SIMPLIFY_MISMATCH = 1, 2, 3, 4
+SIMPLIFY_MAX_CELLS = 1 << 26
 
 # every symbol include/gpnerf_hip.h declares: (restype, argtypes)
 SYMBOLS = {
@@ -249,6 +255,11 @@ SYMBOLS = {
     "gpnerf_mesh_interpolate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, DP, C.c_int32, C.c_int32, C.c_int32,
                                           C.c_double, C.c_void_p, C.c_int32, FP, C.c_void_p, C.c_void_p]),
     "gpnerf_silhouette_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "gpnerf_mesh_simplify_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.POINTER(C.c_int32)]),
+    "gpnerf_mesh_simplify_count": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, FP, C.c_float, C.POINTER(C.c_int32), C.c_void_p,
+                                             C.c_size_t, C.c_void_p, C.c_void_p]),
+    "gpnerf_mesh_simplify_emit": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_size_t, C.c_int64, C.c_int64,
+                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gpnerf_head_layout": (C.c_int, [C.POINTER(C.c_int32)]),
     "gpnerf_strerror": (C.c_char_p, [C.c_int]),
     "gpnerf_rays_per_tile": (C.c_int32, []),

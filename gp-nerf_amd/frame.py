@@ -932,16 +932,113 @@ def mesh_normals(cube, vertices, step=None):
     return normals
 
 
+def parse_simplify(value, what="simplify"):
+    """extract_mesh(simplify=...) / Renderer(mesh_simplify=...) / GPNERF_MESH_SIMPLIFY -> None (off) or the cell edge in lattice steps, a
+    float > 0: off is None, False, 0, "0" or ""; anything else that is not a finite number > 0 is refused."""
+    if value is None or value is False:
+        return None
+    if isinstance(value, str):
+        text = value.strip()
+        if text in ("", "0"):
+            return None
+        try:
+            value = float(text)
+        except ValueError:
+            raise L.GpnerfError(f"{what}: expected 0 or a cell edge in lattice steps > 0, got {text!r}") from None
+    if isinstance(value, bool) or not isinstance(value, (int, float, np.integer, np.floating)):
+        raise L.GpnerfError(f"{what}: expected None or a cell edge in lattice steps > 0, got {value!r}")
+    value = float(value)
+    if value == 0.0:
+        return None
+    if not (value > 0.0 and np.isfinite(value)):
+        raise L.GpnerfError(f"{what}: expected None or a cell edge in lattice steps > 0, got {value!r}")
+    return value
+
+
+def simplify_grid(vmin, vmax, cell):
+    """The grid simplify_mesh lays over a mesh whose box it was not given: lo = float32(floor(min) - cell / 4), cells =
+    ceil((max - lo) / cell) + 1 per axis, in float64 on the host from the float32 box (the quarter cell keeps vertices with integer
+    coordinates -- marching cubes' -- off the cell planes when cell is an integer; the extra cell holds max when it lies on one)."""
+    vmin, vmax = np.asarray(vmin, dtype=np.float64), np.asarray(vmax, dtype=np.float64)
+    lo = (np.floor(vmin) - float(cell) / 4.0).astype(np.float32)
+    cells = np.ceil((vmax - lo.astype(np.float64)) / float(cell)).astype(np.int64) + 1
+    return lo, [int(c) for c in cells]
+
+
+def simplify_mesh(vertices, faces, cell, lo=None, cells=None, want_map=False):
+    """gpnerf_mesh_simplify_count + gpnerf_mesh_simplify_emit: quadric vertex clustering of a device mesh (vertices float32 [n,3], faces
+    int32 [m,3]) over cubic cells of edge `cell` -- cubes in the vertices' units; for marching cubes' index units on the reference's
+    cubic voxels that is geometric --: (vertices float32 [n',3], faces int32 [m',3], stats int64 [8] (_lib.SIMPLIFY_STATS names them),
+    vertex_map int32 [n] or None), all on the device.  include/gpnerf_hip.h states the definition.
+    lo (3 floats) and cells (3 ints, product <= 2^26): the grid; with either omitted the box comes from vertices.amin / amax, one
+    more host read (24 bytes), by simplify_grid's rule -- a mesh with a vertex that is not finite needs the grid given.  The other
+    host read is the two output sizes.  The workspace comes from torch's caching allocator per call and goes back when the call
+    returns."""
+    lib = L.lib()
+    for t, name in ((vertices, "vertices"), (faces, "faces")):
+        if not isinstance(t, torch.Tensor):
+            raise L.GpnerfError(f"simplify_mesh: {name} must be a device tensor (mesh_to_device uploads a Mesh)")
+        _require_gpu(t, f"simplify_mesh: {name}")
+    if vertices.dtype != torch.float32 or vertices.dim() != 2 or vertices.shape[1] != 3 or not vertices.is_contiguous():
+        raise L.GpnerfError(f"simplify_mesh: expected contiguous float32 vertices [n,3], got {vertices.dtype} {tuple(vertices.shape)}")
+    if faces.dtype != torch.int32 or faces.dim() != 2 or faces.shape[1] != 3 or not faces.is_contiguous():
+        raise L.GpnerfError(f"simplify_mesh: expected contiguous int32 faces [m,3], got {faces.dtype} {tuple(faces.shape)}")
+    if faces.device != vertices.device:
+        raise L.GpnerfError("simplify_mesh: vertices and faces are on different devices")
+    cell = float(cell)
+    if not (cell > 0.0 and np.isfinite(cell) and np.float32(cell) > 0 and np.isfinite(np.float32(cell))):
+        raise L.GpnerfError(f"simplify_mesh: cell must be > 0 and finite, got {cell!r}")
+    dev = vertices.device
+    nv, nf = int(vertices.shape[0]), int(faces.shape[0])
+    if lo is None or cells is None:
+        if nv == 0:
+            lo, cells = np.zeros(3, dtype=np.float32), [1, 1, 1]
+        else:
+            box = torch.stack([vertices.amin(0), vertices.amax(0)]).cpu().numpy()
+            if not np.isfinite(box).all():
+                raise L.GpnerfError("simplify_mesh: a vertex is not finite; give lo and cells")
+            lo, cells = simplify_grid(box[0], box[1], cell)
+    lo = np.asarray(lo, dtype=np.float32).ravel()
+    cells = [int(c) for c in np.asarray(cells).ravel()]
+    if lo.shape != (3,) or len(cells) != 3 or not np.isfinite(lo).all():
+        raise L.GpnerfError(f"simplify_mesh: lo is 3 finite floats and cells 3 integers, got {lo!r} and {cells!r}")
+    if min(cells) < 1 or cells[0] * cells[1] * cells[2] > L.SIMPLIFY_MAX_CELLS:
+        raise L.GpnerfError(f"simplify_mesh: cells {cells} refused (each >= 1, product <= 2^26): choose a larger cell")
+    c_lo, c_cells = (C.c_float * 3)(*lo.tolist()), (C.c_int32 * 3)(*cells)
+    nbytes = int(lib.gpnerf_mesh_simplify_workspace_bytes(nv, nf, c_cells))
+    if nbytes <= 0:
+        raise L.GpnerfError(f"simplify_mesh: sizes refused ({nv} vertices, {nf} faces, cells {cells})")
+    ws = torch.empty((nbytes,), device=dev, dtype=torch.uint8)
+    stats = torch.empty((len(L.SIMPLIFY_STATS),), device=dev, dtype=torch.int64)
+    st = _stream_ptr(dev)
+    vp, fp = (vertices.data_ptr() if nv else None), (faces.data_ptr() if nf else None)
+    L.check(lib.gpnerf_mesh_simplify_count(vp, nv, fp, nf, c_lo, cell, c_cells, ws.data_ptr(), ws.numel(), stats.data_ptr(), st),
+            "gpnerf_mesh_simplify_count")
+    n_out_v, n_out_f = (int(v) for v in stats[:2].cpu().tolist())
+    out_v = torch.empty((n_out_v, 3), device=dev, dtype=torch.float32)
+    out_f = torch.empty((n_out_f, 3), device=dev, dtype=torch.int32)
+    vmap = torch.empty((nv,), device=dev, dtype=torch.int32) if want_map else None
+    L.check(lib.gpnerf_mesh_simplify_emit(vp, nv, fp, nf, ws.data_ptr(), ws.numel(), n_out_v, n_out_f, out_v.data_ptr() if n_out_v else None,
+                                          out_f.data_ptr() if n_out_f else None, vmap.data_ptr() if vmap is not None and nv else None, st),
+            "gpnerf_mesh_simplify_emit")
+    return out_v, out_f, stats, vmap
+
+
 def extract_mesh(frame, voxel_size, bounds_min, Rh, Th, neg_ray=False, iso=1.0 / 50.0, host=None, clean=None, fill_cavities=None,
-                 normals=False, lattice=None):
+                 normals=False, lattice=None, simplify=None):
     """The geometry mode of demo_render.py's render_rays (:166-175, 249-311, 366-376) on the device: the box of the occupied voxels,
     the lattice, the alpha cube and its marching-cubes mesh.  Two host reads: the box (6 values) and the mesh counts (2).
     Returns {"cube" (device [X+20,Y+20,Z+20]), "vertices", "faces" (device), "axes", "can_bounds", "n_kept" (device int64),
     "lattice" (lattice_of(axes): query_points at the vertices as they come)}.
     clean (cube_clean's `keep`: "largest" or N) and fill_cavities (None: filled whenever clean is given): marching cubes then runs on
     the cleaned cube -- "cube" stays the untouched one -- and "clean_stats" (device int64 [6]) is added; normals: "normals" (device
-    [nv,3], mesh_normals of the cube the mesh was made from, scaled by 1 / voxel size) is added.  With all three off no further launch
-    is enqueued.
+    [nv,3], mesh_normals of the cube the mesh was made from, scaled by 1 / voxel size) is added.  simplify: a number k > 0, the edge in
+    lattice steps of the cubic cells of simplify_mesh, which runs behind marching cubes on the index-unit vertices with lo = (-1/2,
+    -1/2, -1/2) and cells = ceil(dim / k) + 1 (for an integer k the lattice planes, on which marching-cubes vertices have two integer
+    coordinates, never sit on a cell boundary); "vertices" and "faces" are then the simplified mesh, "normals" are taken at ITS
+    vertices, "simplify_stats" (device int64 [8], _lib.SIMPLIFY_STATS) is added, and the call has one more host read (the two sizes).
+    The cells are cubes in index units: geometric on cubic voxels, as the reference's are.  With all four off no further launch is
+    enqueued.
     lattice: a ready (cube, axes, n_kept) -- the dense renderer's hull-carved cube (density_lattice(inside=...)) -- in place of the
     box, the lattice and the occupancy-culled cube; cleaning, marching cubes, normals and "lattice" are then the same code.  The box
     read does not happen and "can_bounds" is left out."""
@@ -959,6 +1056,11 @@ def extract_mesh(frame, voxel_size, bounds_min, Rh, Th, neg_ray=False, iso=1.0 /
     if clean is not None or fill:
         surface, res["clean_stats"], _ = cube_clean(cube, iso, keep=clean, fill_cavities=fill)
     res["vertices"], res["faces"] = marching_cubes(surface, iso)
+    k = parse_simplify(simplify, "extract_mesh: simplify")
+    if k is not None:
+        cells = [int(np.ceil(d / k)) + 1 for d in surface.shape]
+        res["vertices"], res["faces"], res["simplify_stats"], _ = simplify_mesh(res["vertices"], res["faces"], k, lo=(-0.5, -0.5, -0.5),
+                                                                                cells=cells)
     if normals:
         res["normals"] = mesh_normals(surface, res["vertices"], step=np.asarray(vs, dtype=np.float64).ravel()[:3])
     return res

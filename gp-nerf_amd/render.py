@@ -57,7 +57,7 @@ class Renderer(nn.Module):
     def __init__(self, encoder, nerfhead, is_train=False, neg_ray_train=False, neg_ray_val=False, n_rays=1024,
                  n_samples=64, voxel_size=(0.005, 0.005, 0.005), chunk=64, mesh_th=-1, early_term=None, term_eps=1e-5,
                  progressive=False, split_f16=None, sharded_outputs="all", shard_group=None, encoder_graph=None, fold_levels=None, reserve_cus=None,
-                 mesh_colors=None, mesh_clean=None, mesh_normals=None):
+                 mesh_colors=None, mesh_clean=None, mesh_normals=None, mesh_simplify=None):
         super().__init__()
         self.encoder = encoder
         self.nerfhead = nerfhead
@@ -120,6 +120,10 @@ class Renderer(nn.Module):
         # carries vertex_normals, the cube's gradient at the vertices (gpnerf_mesh_normals).  Both off by default.
         self.mesh_clean = parse_mesh_clean(os.environ.get("GPNERF_MESH_CLEAN", "0") if mesh_clean is None else mesh_clean)
         self.mesh_normals = (os.environ.get("GPNERF_MESH_NORMALS", "0") == "1") if mesh_normals is None else bool(mesh_normals)
+        # mesh_simplify (GPNERF_MESH_SIMPLIFY = unset / 0 (off) or k > 0): the mesh is simplified on the device by quadric vertex
+        # clustering over cubic cells of k lattice steps (gpnerf_mesh_simplify_*) before normals and colours are taken.  Off by default.
+        self.mesh_simplify = F_.parse_simplify(os.environ.get("GPNERF_MESH_SIMPLIFY", "0") if mesh_simplify is None else mesh_simplify,
+                                               "mesh_simplify / GPNERF_MESH_SIMPLIFY")
 
     # ---- helpers the reference exposes as methods (stage entry points) ----------------------------
     def _neg_ray(self, batch):
@@ -302,6 +306,16 @@ class Renderer(nn.Module):
                 # keeps its two clocks (libs/trainers/BaseTrainer.py:276 sums rtime into the reported render time)
                 "etime": etime, "rtime": max(0.0, (t4 - te) - etime)}
 
+    @staticmethod
+    def _mesh_stats(m):
+        """extract_mesh's device counts as one dict: gpnerf_cube_clean's six (_lib.CUBE_STATS) with mesh_clean, the simplification's
+        eight (_lib.SIMPLIFY_STATS) with mesh_simplify; None with both off."""
+        stats = None
+        for key, names in (("clean_stats", L.CUBE_STATS), ("simplify_stats", L.SIMPLIFY_STATS)):
+            if key in m:
+                stats = {**(stats or {}), **dict(zip(names, m[key].cpu().tolist()))}
+        return stats
+
     def render_mesh(self, batch):
         """The inference renderer's geometry mode (demo_render.py:166-175, 249-311, 366-376, use_rgbhead False) on the device: returns
         `mesh` (mesh.Mesh: vertices in index units of the padded cube, as mcubes gives them), `cube` (the padded alpha cube,
@@ -313,8 +327,10 @@ class Renderer(nn.Module):
         vertices), `cube` stays the untouched alpha cube, and `mesh_stats` holds gpnerf_cube_clean's six counts as a dict (_lib.CUBE_STATS)
         -- at most one more small host read per call (48 bytes).  With mesh_normals, the mesh carries vertex_normals: unit normals
         from the gradient of the cube the mesh was made from, scaled by 1 / voxel_size per axis (geometric normals on an anisotropic
-        lattice), in the vertices' frame (the cube's index axes).  With both off, extract_mesh enqueues exactly the launches it
-        did before there were these options."""
+        lattice), in the vertices' frame (the cube's index axes).  With mesh_simplify = k, the mesh is the quadric vertex clustering
+        of that surface over cubic cells of k lattice steps (frame.simplify_mesh: one more host read, the two sizes); normals and
+        colours are taken at the simplified vertices, and `mesh_stats` gains the eight counts of _lib.SIMPLIFY_STATS.  With all of them
+        off, extract_mesh enqueues exactly the launches it did before there were these options."""
         dev = batch["src_imgs"].device
         torch.cuda.synchronize(dev)
         te = time.time()
@@ -331,7 +347,8 @@ class Renderer(nn.Module):
         frame.build_occupancy()
         ev[2].record()
         m = F_.extract_mesh(frame, self.voxel_size, batch["bounds"][0, 0], batch["Rh"][0], batch["Th"][0], neg_ray=self._neg_ray(batch),
-                            iso=M_.ISO_REFERENCE, host=box_host, clean=self.mesh_clean, normals=self.mesh_normals)
+                            iso=M_.ISO_REFERENCE, host=box_host, clean=self.mesh_clean, normals=self.mesh_normals,
+                            simplify=self.mesh_simplify)
         colours = None
         if self.mesh_colors:
             colours = F_.query_points(frame, m["vertices"], neg_ray=self._neg_ray(batch), want=("rgb",), lattice=m["lattice"])["rgb"]
@@ -339,7 +356,7 @@ class Renderer(nn.Module):
         cube = m["cube"].cpu().numpy()
         mesh = M_.Mesh(m["vertices"].cpu().numpy(), m["faces"].cpu().numpy(), colours.cpu().numpy() if colours is not None else None,
                        m["normals"].cpu().numpy() if "normals" in m else None)
-        stats = dict(zip(L.CUBE_STATS, m["clean_stats"].cpu().tolist())) if "clean_stats" in m else None
+        stats = self._mesh_stats(m)
         t4 = time.time()
         etime = ev[0].elapsed_time(ev[1]) * 1e-3
         t_frame, t_mesh = ev[1].elapsed_time(ev[2]) * 1e-3, ev[2].elapsed_time(ev[3]) * 1e-3
@@ -363,8 +380,8 @@ class Renderer(nn.Module):
               [1,2,3] -- the axes are frame.dataset_lattice_axes' and the hull is carved on the device (gpnerf_visual_hull): the
               loader neither builds the 12 B/point `pts` array nor carves.
         Returns `cube` (the padded alpha cube, float32 numpy), `mesh` (mesh.Mesh, vertices in index units of the padded cube), `axes`
-        (three host float32 arrays), `n_inside` (kept points), `time_slots`, `etime`, `rtime`, and `mesh_stats` with mesh_clean.
-        mesh_clean / mesh_normals / mesh_colors act as in render_mesh.  Host reads: the constants (with the axes or the cameras) before
+        (three host float32 arrays), `n_inside` (kept points), `time_slots`, `etime`, `rtime`, and `mesh_stats` with mesh_clean or
+        mesh_simplify.  mesh_clean / mesh_normals / mesh_colors / mesh_simplify act as in render_mesh.  Host reads: the constants (with the axes or the cameras) before
         the encoder, the mesh counts, and the results."""
         dev = batch["src_imgs"].device
         have_a = "pts" in batch and "inside" in batch
@@ -409,7 +426,7 @@ class Renderer(nn.Module):
         neg = self._neg_ray(batch)
         cube, n_kept = F_.density_lattice(frame, axes, neg_ray=neg, pad=F_.MESH_PAD, inside=inside)
         m = F_.extract_mesh(frame, self.voxel_size, None, None, None, neg_ray=neg, iso=self.mesh_th, host=[vs_host], clean=self.mesh_clean,
-                            normals=self.mesh_normals, lattice=(cube, axes, n_kept))
+                            normals=self.mesh_normals, lattice=(cube, axes, n_kept), simplify=self.mesh_simplify)
         colours = None
         if self.mesh_colors:
             colours = F_.query_points(frame, m["vertices"], neg_ray=neg, want=("rgb",), lattice=m["lattice"])["rgb"]
@@ -417,7 +434,7 @@ class Renderer(nn.Module):
         cube_np = m["cube"].cpu().numpy()
         mesh = M_.Mesh(m["vertices"].cpu().numpy(), m["faces"].cpu().numpy(), colours.cpu().numpy() if colours is not None else None,
                        m["normals"].cpu().numpy() if "normals" in m else None)
-        stats = dict(zip(L.CUBE_STATS, m["clean_stats"].cpu().tolist())) if "clean_stats" in m else None
+        stats = self._mesh_stats(m)
         n_inside = int(n_kept.cpu().item())
         t4 = time.time()
         etime = ev[0].elapsed_time(ev[1]) * 1e-3

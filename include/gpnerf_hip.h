@@ -739,6 +739,90 @@ int gpnerf_mesh_interpolate(const int32_t* face_id, const float* vertices, int64
                             const float* background, float* out, void* stream);
 int gpnerf_silhouette_stats(const int32_t* face_id, const uint8_t* masks, int32_t n_views, int32_t H, int32_t W, int64_t* out, void* stream);
 
+/* ---- simplifying a mesh by quadric vertex clustering (gpnerf_simplify.hip): the vertices of a cubic cell collapse to one point, the
+ * minimiser of the cell's plane quadric, regularised toward the cell's centre and kept inside the cell.  A mesh at the lattice's
+ * resolution (one face per lattice step) comes out at the resolution the caller's cell asks for.  Both calls: kernel launches only,
+ * on the caller's stream; nothing allocated, nothing waited for; every launch sized from the arguments alone; every data-dependent
+ * length stays in the workspace; both capture into a HIP graph and replay with the same bits; the result is a function of the
+ * inputs alone and of no launch geometry or arrival order (integer atomics for counts and cursors, no float atomic).
+ * vertices: device float [n_vertices][3]; faces: device int32 [n_faces][3]; both counts 0 to 2^31 - 1 (a pointer may be NULL where its
+ * count is 0); lo: HOST float [3], finite; cell: float, > 0 and finite; cells: HOST int32 [3], each >= 1, product <= 2^26.
+ *
+ * THE DEFINITION
+ *   1. the cell of a vertex v: q_k = floorf((v_k - lo_k) / cell), a float32 subtraction, an IEEE float32 division and a floor, nothing
+ *      fused.  The vertex is IN THE GRID iff its coordinates are finite and 0 <= q_k < cells_k on all axes; its cell's linear index
+ *      is (q_x cells_y + q_y) cells_z + q_z.
+ *   2. a face is VALID iff its three indices are in [0, n_vertices) and its three vertices are in the grid.  Invalid faces are
+ *      dropped and counted, never clamped.
+ *   3. a cell is OCCUPIED iff a valid face has a vertex in it; the occupied cells, numbered in ascending linear index, are the
+ *      CLUSTERS.
+ *   4. the quadric of a cluster, float64 on the float32 vertices widened.  Per valid face with corners p0, p1, p2: a = p1 - p0,
+ *      b = p2 - p0, n = (a_y b_z - a_z b_y, a_z b_x - a_x b_z, a_x b_y - a_y b_x), l = sqrt((n_x n_x + n_y n_y) + n_z n_z); a face with
+ *      l == 0 contributes nothing; u = n / l, w = 0.5 l, d = -((u_x p0_x + u_y p0_y) + u_z p0_z), wu = w u, wd = w d; the nine terms
+ *      wu_x u_x, wu_x u_y, wu_x u_z, wu_y u_y, wu_y u_z, wu_z u_z (A's upper triangle) and wd u_x, wd u_y, wd u_z (b).  A face
+ *      contributes to every DISTINCT cluster among its three, once per cluster.
+ *      THE ORDER OF THE SUM: with the cluster's faces sorted by ascending index as entries 0 .. k-1, 64 partial sums start at 0 and
+ *      partial j adds entries j, j + 64, ... in order; the sum is ((partial 0 + partial 1) + partial 2) + ... + partial 63.  (For
+ *      k <= 64 that is the plain ascending sum.)
+ *   5. the position of a cluster in cell (q_x, q_y, q_z), float64: c_k = lo_k + (q_k + 0.5) cell; lambda = (1e-3 ((A_xx + A_yy) + A_zz))
+ *      / 3.  If lambda == 0 the position is c.  Otherwise x = c - s where (A + lambda I) s = r, r_i = ((A_ix c_x + A_iy c_y) + A_iz c_z)
+ *      + b_i -- the minimiser of the quadric plus lambda |x - c|^2; the matrix is symmetric positive definite with condition number
+ *      <= about 3 / 1e-3 -- by Cholesky: l00 = sqrt(m00), l10 = m10 / l00, l20 = m20 / l00, l11 = sqrt(m11 - l10 l10), l21 = (m21 - l20
+ *      l10) / l11, l22 = sqrt((m22 - l20 l20) - l21 l21); y0 = r0 / l00, y1 = (r1 - l10 y0) / l11, y2 = ((r2 - l20 y0) - l21 y1) / l22;
+ *      s2 = y2 / l22, s1 = (y1 - l21 s2) / l11, s0 = ((y0 - l10 s1) - l20 s2) / l00.  (An x that is not finite -- a quadric that
+ *      overflowed -- is replaced by c.)  x is then clamped per axis to the cell's closed box [lo_k + q_k cell, lo_k + (q_k + 1) cell]
+ *      (float64); a cluster whose x the clamp changed is counted as CLAMPED; x is rounded to float32 once.
+ *   6. every valid face's indices are mapped to cluster ids, corner order kept.  A face with two equal ids is COLLAPSED and dropped.
+ *      The others are grouped by their sorted id triple; the parity of a face is the sign of the permutation that sorts its triple;
+ *      a group with P faces of parity + and N of parity - has net = P - N.  2 min(P, N) of its faces are counted as CANCELLED
+ *      (opposite faces of a sheet that folded shut).  If net == 0 nothing of the group is kept; otherwise exactly one face is: the
+ *      lowest original index among those whose parity has the sign of net, and the |net| - 1 others are counted as DUPLICATE.
+ *      Output faces are in ascending original index.  (n_faces = out + invalid + collapsed + cancelled + duplicate.)
+ *   7. a cluster that no output face references is DROPPED; the others, in ascending cell order, are the output vertices, and the
+ *      output faces carry their numbers.  vertex_map[v] = the output vertex of the cluster in v's cell, -1 for a vertex that is not in
+ *      the grid or whose cell is no cluster or a dropped one.
+ * Every input vertex of a valid face lies within sqrt(3) cell of the position of its cluster (the clamp), up to float32 rounding
+ * of the coordinates.
+ *
+ * gpnerf_mesh_simplify_count does everything that decides and leaves the maps in the workspace; stats: device int64
+ * [GPNERF_SIMPLIFY_STATS], set by the call.  The caller reads VERTICES_OUT and FACES_OUT (the one host read), sizes out_vertices
+ * float [n][3] and out_faces int32 [m][3], and calls gpnerf_mesh_simplify_emit with the same mesh and workspace; vertex_map: device
+ * int32 [n_vertices] or NULL.  Emit reads nothing back: its first launch compares the four sizes it was given with those counted ON
+ * THE DEVICE; when they differ, or the workspace holds no finished count, nothing is written and the workspace's 64-bit word
+ * GPNERF_SIMPLIFY_HDR_STATUS is GPNERF_SIMPLIFY_MISMATCH (after a good emit: GPNERF_SIMPLIFY_EMITTED).
+ * Launches of count: a clear; a lane per vertex (cells); a lane per face (validity, occupancy); a three-launch integer scan of the
+ * cells; a lane per face (cluster ids, list lengths); a scan; a lane per face (lists filled by cursor); a lane per (face, corner)
+ * that places the face in the cluster's list at the number of smaller faces there -- quadratic in a list's length, but spread over
+ * as many lanes as the list has entries --; a wavefront per cluster (quadric in the order above, position); a lane per face that
+ * walks the shortest of its three clusters' lists for its group (verdict); two scans (face and vertex numbers); one lane (stats).
+ * workspace: gpnerf_mesh_simplify_workspace_bytes(n_vertices, n_faces, cells) bytes (host arithmetic only; 0 for what the calls
+ * refuse) = 256 + 5 a(4 nv) + a(8 (nv + 1)) + a(12 nv) + a(4 nf) + 3 a(12 nf) + a(4 C) + a(8 ceil(max(C, nf, nv + 1) / 2048)), with
+ * C = cells_x cells_y cells_z and a() rounding up to a multiple of 256.  It carries the maps from count to emit and nothing else.
+ * GPNERF_E_ARG, before anything is launched: null lo, cells, workspace or stats; null vertices with n_vertices > 0 or faces with
+ * n_faces > 0; a count that is negative or >= 2^31; a cell that is not > 0 and finite; a lo that is not finite; a cells entry < 1 or
+ * a product > 2^26; a workspace under the formula (emit: under the formula at C = 1); emit: output sizes that are negative or exceed
+ * the input's, a null output whose size is > 0. */
+#define GPNERF_SIMPLIFY_VERTICES_OUT 0
+#define GPNERF_SIMPLIFY_FACES_OUT 1
+#define GPNERF_SIMPLIFY_FACES_INVALID 2
+#define GPNERF_SIMPLIFY_FACES_COLLAPSED 3
+#define GPNERF_SIMPLIFY_FACES_CANCELLED 4
+#define GPNERF_SIMPLIFY_FACES_DUPLICATE 5
+#define GPNERF_SIMPLIFY_CLUSTERS_CLAMPED 6
+#define GPNERF_SIMPLIFY_CLUSTERS_DROPPED 7
+#define GPNERF_SIMPLIFY_STATS 8
+#define GPNERF_SIMPLIFY_HDR_STATUS 12
+#define GPNERF_SIMPLIFY_COUNTING 1
+#define GPNERF_SIMPLIFY_COUNTED 2
+#define GPNERF_SIMPLIFY_EMITTED 3
+#define GPNERF_SIMPLIFY_MISMATCH 4
+size_t gpnerf_mesh_simplify_workspace_bytes(int64_t n_vertices, int64_t n_faces, const int32_t* cells);
+int gpnerf_mesh_simplify_count(const float* vertices, int64_t n_vertices, const int32_t* faces, int64_t n_faces, const float* lo, float cell,
+                               const int32_t* cells, void* workspace, size_t workspace_bytes, int64_t* stats, void* stream);
+int gpnerf_mesh_simplify_emit(const float* vertices, int64_t n_vertices, const int32_t* faces, int64_t n_faces, void* workspace,
+                              size_t workspace_bytes, int64_t n_out_vertices, int64_t n_out_faces, float* out_vertices, int32_t* out_faces,
+                              int32_t* vertex_map, void* stream);
+
 /* ---- per-frame sparse convolution pyramid (gpnerf_volume.hip), replacing the external spconv v1.2.1 calls of
  * libs/nerfheads/networks/SparseConvNet.py:22-111 (SubMConv3d / SparseConv3d + BatchNorm1d + ReLU, .dense()).
  * A sparse tensor is: features [M][C] fp32, coords [M][3] int32 (d,h,w), and a dense int32 index grid [D][H][W]
