@@ -193,6 +193,34 @@ def test_render_fused_rejects_bad_arguments_on_the_host(pkg):
     assert lib.gpnerf_strerror(-1) == b"invalid argument"
 
 
+def test_frames_just_inside_the_addressing_limits_are_accepted(pkg):
+    """The accepted neighbour of every refusal above: gpnerf_query_points checks the frame (all levels, images and feature maps)
+    before its n_points == 0 early-out, so with no points it says whether to_framek() takes a frame without touching a pointer.
+    tests/test_gpu_limits.py runs the kernels on these shapes.  The folded levels' limits (256 bytes per voxel) are not a refusal
+    -- a render call ignores folded volumes beyond them -- so no entry point reports them; the GPU tests cover their acceptance."""
+    L = pkg._lib
+    lib = L.lib()
+
+    def query(frame):
+        frame.head_blob_ref = 0x1000
+        return lib.gpnerf_query_points(C.byref(frame), None, 0, 0, None, None, None, None)
+
+    assert query(_frame(L)) == 0
+    for refused, accepted in (
+            (dict(dhw=(4096, 4096, 8)), dict(dhw=(4095, 4097, 2))),                     # D*H = 2^24 - 1; 2^32 - 256 bytes
+            (dict(dhw=(8, 8, 1 << 17)), dict(dhw=(8, 8, (1 << 17) - 1))),               # an x-row of 2^24 - 128 bytes
+            (dict(dhw=(1024, 1024, 1024)), dict(dhw=(16, 16, (1 << 17) - 1))),          # a level of 2^32 - 32768 bytes
+            (dict(dhw=(4095, 4097, 3)), dict(dhw=(4095, 4097, 2))),                     # (the level's bytes alone decide)
+            (dict(img=(8, 1 << 20)), dict(img=(8, (1 << 20) - 1))),                     # an image row of 2^24 - 16 bytes
+            (dict(img=(257, (1 << 20) - 1)), dict(img=(256, (1 << 20) - 1))),           # an image of 2^32 - 4096 bytes
+            (dict(img=(1 << 24, 1)), dict(img=((1 << 24) - 1, 16))),                    # 2^24 - 1 image rows; 2^32 - 256 bytes
+            (dict(feat=(1 << 12, 1 << 13)), dict(feat=(256, (1 << 17) - 1))),           # feature maps of 2^32 - 32768 bytes per view
+            (dict(feat=(8, 1 << 17)), dict(feat=(8, (1 << 17) - 1))),                   # a feature row of 2^24 - 128 bytes
+            (dict(feat=(1 << 24, 1)), dict(feat=((1 << 24) - 1, 2)))):                  # 2^24 - 1 feature rows; 2^32 - 256 bytes
+        assert query(_frame(L, **refused)) == -1, refused
+        assert query(_frame(L, **accepted)) == 0, accepted
+
+
 def test_fold_volumes_rejects_bad_arguments_on_the_host(pkg):
     """gpnerf_fold_volumes checks its arguments before it touches the device: the frame, its head image, the coarse levels
     (GPNERF_FOLD_FIRST_LEVEL..) and their output pointers; the finer levels' entries are not looked at."""
