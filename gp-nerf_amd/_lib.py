@@ -146,6 +146,15 @@ SIMPLIFY_STATS = ("vertices_out", "faces_out", "faces_invalid", "faces_collapsed
 SIMPLIFY_HDR_STATUS = 12
 SIMPLIFY_COUNTING, SIMPLIFY_COUNTED, SIMPLIFY_EMITTED, SIMPLIFY_MISMATCH = 1, 2, 3, 4
 SIMPLIFY_MAX_CELLS = 1 << 26
+# gpnerf_mesh_adjacency's stats, the vertex flags, gpnerf_mesh_adjacency_layout's offsets and gpnerf_mesh_smooth's flag and limits
+# (include/gpnerf_hip.h GPNERF_TOPOLOGY_* / GPNERF_VERTEX_* / GPNERF_ADJACENCY_* / GPNERF_SMOOTH_*)
+TOPOLOGY_STATS = ("faces_used", "faces_dropped", "vertices_referenced", "edges", "boundary_edges", "nonmanifold_edges", "inconsistent_edges",
+                  "euler", "boundary_vertices", "max_valence")
+VERTEX_REFERENCED, VERTEX_BOUNDARY = 1, 2
+ADJACENCY_START, ADJACENCY_NEIGHBOURS, ADJACENCY_VERTEX_FLAGS = range(3)
+SMOOTH_PIN_BOUNDARY = 1
+SMOOTH_MAX_ITERATIONS = 10000
+ADJACENCY_MAX_FACES = ((1 << 31) - 1) // 3
 
 # every symbol include/gpnerf_hip.h declares: (restype, argtypes)
 SYMBOLS = {
@@ -260,6 +269,11 @@ SYMBOLS = {
                                              C.c_size_t, C.c_void_p, C.c_void_p]),
     "gpnerf_mesh_simplify_emit": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_size_t, C.c_int64, C.c_int64,
                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gpnerf_mesh_adjacency_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64]),
+    "gpnerf_mesh_adjacency_layout": (C.c_int, [C.c_int64, C.c_int64, C.POINTER(C.c_int64)]),
+    "gpnerf_mesh_adjacency": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "gpnerf_mesh_smooth": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_size_t, C.c_int32, C.c_double, C.c_double, C.c_uint32, C.c_void_p,
+                                     C.c_void_p]),
     "gpnerf_head_layout": (C.c_int, [C.POINTER(C.c_int32)]),
     "gpnerf_strerror": (C.c_char_p, [C.c_int]),
     "gpnerf_rays_per_tile": (C.c_int32, []),

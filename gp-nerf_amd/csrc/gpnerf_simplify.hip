@@ -22,10 +22,11 @@ namespace {
 
 #include "gpnerf_diag.h"       // the lab's hook points, empty in the product (csrc/nodiag/)
 
+#include "gpnerf_scan.h"       // the three-launch integer scan (shared with gpnerf_meshtopo.hip): SCAN_CHUNK, scan_launch
+
+struct SimplifyScan;           // names this file's instances of the scan kernels
+
 constexpr int THREADS = 256;
-constexpr int SCAN_ITEMS = 8;                            // per thread
-constexpr int SCAN_CHUNK = THREADS * SCAN_ITEMS;         // 2048 items per block of the scans
-constexpr int TOP_THREADS = 1024;
 constexpr int64_t MAX_CELLS = (int64_t)1 << 26;
 constexpr int64_t MAX_COUNT = ((int64_t)1 << 31) - 1;
 constexpr long long SIMPLIFY_MAGIC = 0x53494d5031ll;     // "SIMP1"
@@ -164,79 +165,6 @@ __global__ __launch_bounds__(THREADS) void face_mark_kernel(const int32_t* __res
         invalid = !ok;
     }
     wave_count(invalid, &w.hdr[H_INVALID]);
-}
-
-// ---------------------------------------------------------------- integer scans (any association gives the same sums)
-
-// the items at or beyond *n_dev (when given) count as 0
-DEV int scan_item(const int32_t* __restrict__ in, long i, long n, long n_live) { return (i < n && i < n_live) ? in[i] : 0; }
-
-__global__ __launch_bounds__(THREADS) void scan_sums_kernel(const int32_t* __restrict__ in, long n, const long long* n_dev, long long* bsum) {
-    __shared__ long long s_sum[THREADS];
-    const int t = threadIdx.x;
-    const long n_live = n_dev ? (long)*n_dev : n, i0 = (long)blockIdx.x * SCAN_CHUNK + (long)t * SCAN_ITEMS;
-    long long sum = 0;
-    for (int k = 0; k < SCAN_ITEMS; ++k) sum += scan_item(in, i0 + k, n, n_live);
-    s_sum[t] = sum;
-    __syncthreads();
-    for (int s = THREADS / 2; s > 0; s >>= 1) {
-        if (t < s) s_sum[t] += s_sum[t + s];
-        __syncthreads();
-    }
-    if (t == 0) bsum[blockIdx.x] = s_sum[0];
-}
-
-// one workgroup: the block sums become their exclusive prefix, the total goes to the header
-__global__ __launch_bounds__(TOP_THREADS) void scan_top_kernel(long long* bsum, long nb, long long* total_out) {
-    __shared__ long long s_sum[TOP_THREADS];
-    const int t = threadIdx.x;
-    const long per = (nb + TOP_THREADS - 1) / TOP_THREADS, b0 = min((long)t * per, nb), b1 = min(b0 + per, nb);
-    long long sum = 0;
-    for (long b = b0; b < b1; ++b) sum += bsum[b];
-    s_sum[t] = sum;
-    __syncthreads();
-    for (int off = 1; off < TOP_THREADS; off <<= 1) {    // inclusive scan over the threads, ten doubling steps
-        const long long left = t >= off ? s_sum[t - off] : 0;
-        __syncthreads();
-        s_sum[t] += left;
-        __syncthreads();
-    }
-    long long before = s_sum[t] - sum;
-    const long long total = s_sum[TOP_THREADS - 1];
-    for (long b = b0; b < b1; ++b) {
-        const long long c = bsum[b];
-        bsum[b] = before;
-        before += c;
-    }
-    if (t == 0) *total_out = total;
-}
-
-// MODE 0: out64[i] = the exclusive prefix.  MODE 1: `in` holds flags and out32 (which may be `in`) receives the prefix where the flag
-// is set and -1 elsewhere; inverse[prefix] = i where given.
-template <int MODE>
-__global__ __launch_bounds__(THREADS) void scan_apply_kernel(const int32_t* in, long n, const long long* n_dev, const long long* __restrict__ bsum,
-                                                             long long* out64, int32_t* out32, int32_t* inverse) {
-    __shared__ long long s_sum[THREADS];
-    const int t = threadIdx.x;
-    const long n_live = n_dev ? (long)*n_dev : n, i0 = (long)blockIdx.x * SCAN_CHUNK + (long)t * SCAN_ITEMS;
-    int item[SCAN_ITEMS];
-    long long sum = 0;
-    for (int k = 0; k < SCAN_ITEMS; ++k) { item[k] = scan_item(in, i0 + k, n, n_live); sum += item[k]; }
-    s_sum[t] = sum;
-    __syncthreads();                                     // (every item of the block has been read: out32 may alias in)
-    long long before = bsum[blockIdx.x];
-    for (int k = 0; k < t; ++k) before += s_sum[k];
-    for (int k = 0; k < SCAN_ITEMS; ++k) {
-        const long i = i0 + k;
-        if (i < n) {
-            if (MODE == 0) out64[i] = before;
-            else {
-                out32[i] = item[k] ? (int32_t)before : -1;
-                if (inverse && item[k]) inverse[before] = (int32_t)i;
-            }
-        }
-        before += item[k];
-    }
 }
 
 // ---------------------------------------------------------------- clusters and their face lists
@@ -469,14 +397,11 @@ hipStream_t S_(void* s) { return reinterpret_cast<hipStream_t>(s); }
 int launch_status() { return hipGetLastError() == hipSuccess ? GPNERF_OK : GPNERF_E_LAUNCH; }
 unsigned blocks_for(int64_t n, int per) { return (unsigned)((n + per - 1) / per); }
 
-// the three launches of a scan over n items (n >= 1, host-known)
+// a scan over n items (n >= 1, host-known) with the workspace's block sums
 template <int MODE>
 void scan(const int32_t* in, int64_t n, const long long* n_dev, const Ws& w, long long* total_out, long long* out64, int32_t* out32,
           int32_t* inverse, hipStream_t st) {
-    const unsigned nb = blocks_for(n, SCAN_CHUNK);
-    hipLaunchKernelGGL(scan_sums_kernel, dim3(nb), dim3(THREADS), 0, st, in, (long)n, n_dev, w.bsum);
-    hipLaunchKernelGGL(scan_top_kernel, dim3(1), dim3(TOP_THREADS), 0, st, w.bsum, (long)nb, total_out);
-    hipLaunchKernelGGL(scan_apply_kernel<MODE>, dim3(nb), dim3(THREADS), 0, st, in, (long)n, n_dev, (const long long*)w.bsum, out64, out32, inverse);
+    scan_launch<SimplifyScan, MODE>(in, n, n_dev, w.bsum, total_out, out64, out32, inverse, st);
 }
 
 }  // namespace

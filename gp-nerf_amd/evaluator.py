@@ -251,11 +251,17 @@ class MeshEvaluator:
     reads the slots in one copy and adds `silhouette_iou`, `silhouette_precision`, `silhouette_recall` (means over views and
     frames; the border band is left out) and their per-frame lists, and saves `<result_path>/silhouette_metrics.npy` (a structured
     array: frame_index, the three means, and the per-view values).  An output without `axes` -- the inference renderer's
-    render_mesh, whose mesh is not in the cameras' frame -- raises a GpnerfError naming the key.  Off, nothing changes."""
+    render_mesh, whose mesh is not in the cameras' frame -- raises a GpnerfError naming the key.  Off, nothing changes.
+    topology (off by default; needs neither scan nor masks): `evaluate` uploads the frame's mesh and enqueues frame.mesh_topology, a
+    slot of ten counts (_lib.TOPOLOGY_STATS) per frame, no host read.  `summarize()` reads the slots in one copy and adds
+    `watertight_frames` (how many frames' meshes are closed and oriented), `topology_<name>` for the edge counts and `euler` (means
+    over the frames) and their per-frame lists, and saves `<result_path>/topology_metrics.npy` (a structured array: frame_index, the
+    ten counts, closed, oriented, watertight)."""
     PAD = 10                              # if_nerf_mesh.py:20, the np.pad(cube, 10) of BaseRender.py:269
 
     def __init__(self, result_path, mesh_th, export_mesh=False, metric_samples=100000, metric_thresholds=(0.005, 0.01, 0.02),
-                 metric_max_dist=float("inf"), metric_device=None, metric_cell_cap=None, metric_entry_cap=None, silhouette=False):
+                 metric_max_dist=float("inf"), metric_device=None, metric_cell_cap=None, metric_entry_cap=None, silhouette=False,
+                 topology=False):
         self.mesh_th = mesh_th
         self.export_mesh = bool(export_mesh)
         self.result_path = result_path
@@ -267,14 +273,16 @@ class MeshEvaluator:
         self._slots, self._frames = [], []
         self.silhouette = bool(silhouette)
         self._sil_slots, self._sil_frames = [], []
+        self.topology = bool(topology)
+        self._topo_slots, self._topo_frames = [], []
 
     SILHOUETTE_KEYS = ("hull_masks", "hull_Ks", "hull_RTs")
 
     @property
     def has_mesh_metrics(self):
-        """True once a frame with `gt_mesh` (or, with silhouette on, with masks and cameras) has been evaluated and not yet summarized
+        """True once a frame with `gt_mesh` (or, with silhouette on, with masks and cameras; or any frame with topology on) has been evaluated and not yet summarized
         (evaluate_loop asks)"""
-        return bool(self._slots) or bool(self._sil_slots)
+        return bool(self._slots) or bool(self._sil_slots) or bool(self._topo_slots)
 
     def _enqueue_silhouette(self, output, batch):
         from . import frame as F
@@ -325,6 +333,11 @@ class MeshEvaluator:
             self._frames.append(self._scalar(batch["frame_index"]))
         if self.silhouette and all(k in batch for k in self.SILHOUETTE_KEYS):
             self._enqueue_silhouette(output, batch)
+        if self.topology:
+            from . import frame as F
+            v, f = F.mesh_to_device(output["mesh"], torch.device(self.metric_device if self.metric_device is not None else "cuda:0"))
+            self._topo_slots.append(F.mesh_topology(f, int(v.shape[0])))
+            self._topo_frames.append(self._scalar(batch["frame_index"]))
 
     def _summarize_silhouettes(self):
         """the silhouette slots -> (means, per-frame lists), silhouette_metrics.npy written; resets them"""
@@ -354,13 +367,37 @@ class MeshEvaluator:
         self._sil_slots, self._sil_frames = [], []
         return metrics, per_frame
 
+    TOPOLOGY_MEANS = ("edges", "boundary_edges", "nonmanifold_edges", "inconsistent_edges", "euler")
+
+    def _summarize_topology(self):
+        """the topology slots -> (means, per-frame lists), topology_metrics.npy written; resets them"""
+        from . import frame as F
+        host = torch.stack(self._topo_slots).cpu().numpy()     # the one read
+        rows = [F.read_mesh_topology(h) for h in host]
+        per_frame = {f"topology_{k}": [r[k] for r in rows] for k in self.TOPOLOGY_MEANS}
+        per_frame["watertight"] = [bool(r["watertight"]) for r in rows]
+        per_frame["topology_frame_index"] = list(self._topo_frames)
+        metrics = {f"topology_{k}": float(np.mean(per_frame[f"topology_{k}"])) for k in self.TOPOLOGY_MEANS}
+        metrics["watertight_frames"] = int(sum(per_frame["watertight"]))
+        table = np.zeros(len(rows), dtype=[("frame_index", "i8")] + [(k, "i8") for k in L.TOPOLOGY_STATS] +
+                         [(k, "?") for k in ("closed", "oriented", "watertight")])
+        table["frame_index"] = self._topo_frames
+        for k in table.dtype.names[1:]:
+            table[k] = [r[k] for r in rows]
+        os.makedirs(self.result_path, exist_ok=True)
+        np.save(os.path.join(self.result_path, "topology_metrics.npy"), table)      # a structured array: one row per frame
+        print(f"watertight_frames: {metrics['watertight_frames']} of {len(rows)}")
+        self._topo_slots, self._topo_frames = [], []
+        return metrics, per_frame
+
     def summarize(self):
-        if self._sil_slots:
-            sil, sil_frames = self._summarize_silhouettes()
+        if self._sil_slots or self._topo_slots:
+            parts = ([self._summarize_silhouettes()] if self._sil_slots else []) + ([self._summarize_topology()] if self._topo_slots else [])
             metrics = self._summarize_mesh_metrics() if self._slots else {"per_frame": {}}
             per_frame = metrics.pop("per_frame")
-            metrics.update(sil)
-            per_frame.update(sil_frames)
+            for means, frames in parts:
+                metrics.update(means)
+                per_frame.update(frames)
             metrics["per_frame"] = per_frame
             return metrics
         return self._summarize_mesh_metrics()

@@ -1024,8 +1024,131 @@ def simplify_mesh(vertices, faces, cell, lo=None, cells=None, want_map=False):
     return out_v, out_f, stats, vmap
 
 
+def parse_smooth(value, what="smooth"):
+    """extract_mesh(smooth=...) / Renderer(mesh_smooth=...) / GPNERF_MESH_SMOOTH -> None (off) or the number of Taubin iterations, an int
+    in [1, 10 000]: off is None, False, 0, "0" or ""; anything else that is not such a whole number is refused."""
+    if value is None or value is False:
+        return None
+    if isinstance(value, str):
+        text = value.strip()
+        if text in ("", "0"):
+            return None
+        try:
+            value = int(text)
+        except ValueError:
+            raise L.GpnerfError(f"{what}: expected 0 or a number of iterations in [1, {L.SMOOTH_MAX_ITERATIONS}], got {text!r}") from None
+    if isinstance(value, (float, np.floating)) and np.isfinite(value) and float(value) == int(value):
+        value = int(value)
+    if isinstance(value, bool) or not isinstance(value, (int, np.integer)):
+        raise L.GpnerfError(f"{what}: expected None or a number of iterations in [1, {L.SMOOTH_MAX_ITERATIONS}], got {value!r}")
+    value = int(value)
+    if value == 0:
+        return None
+    if not 1 <= value <= L.SMOOTH_MAX_ITERATIONS:
+        raise L.GpnerfError(f"{what}: expected None or a number of iterations in [1, {L.SMOOTH_MAX_ITERATIONS}], got {value!r}")
+    return value
+
+
+class MeshAdjacency:
+    """gpnerf_mesh_adjacency's result, all on the device: `stats` int64 [10] (_lib.TOPOLOGY_STATS names them), and three views into
+    `workspace`: `start` int64 [n_vertices + 1], `neighbours` int32 [6 n_faces] of which start[n_vertices] entries are in use (vertex
+    v's unique neighbours in ascending index at start[v] .. start[v + 1]) and `vertex_flags` uint8 [n_vertices]
+    (_lib.VERTEX_REFERENCED | _lib.VERTEX_BOUNDARY).  smooth_mesh takes it as `adjacency`."""
+
+    def __init__(self, faces, n_vertices, workspace, stats, offsets):
+        self.faces, self.n_vertices, self.n_faces, self.workspace, self.stats = faces, int(n_vertices), int(faces.shape[0]), workspace, stats
+        view = lambda off, nbytes, dt: workspace[off:off + nbytes].view(dt)
+        self.start = view(offsets[L.ADJACENCY_START], 8 * (self.n_vertices + 1), torch.int64)
+        self.neighbours = view(offsets[L.ADJACENCY_NEIGHBOURS], 24 * self.n_faces, torch.int32)
+        self.vertex_flags = view(offsets[L.ADJACENCY_VERTEX_FLAGS], self.n_vertices, torch.uint8)
+
+
+def _adjacency_faces(faces, n_vertices, what):
+    if not isinstance(faces, torch.Tensor):
+        raise L.GpnerfError(f"{what}: faces must be a device tensor (mesh_to_device uploads a Mesh)")
+    _require_gpu(faces, f"{what}: faces")
+    if faces.dtype != torch.int32 or faces.dim() != 2 or faces.shape[1] != 3 or not faces.is_contiguous():
+        raise L.GpnerfError(f"{what}: expected contiguous int32 faces [m,3], got {faces.dtype} {tuple(faces.shape)}")
+    if isinstance(n_vertices, bool) or not isinstance(n_vertices, (int, np.integer)) or n_vertices < 0:
+        raise L.GpnerfError(f"{what}: n_vertices must be an integer >= 0, got {n_vertices!r}")
+    return int(n_vertices), int(faces.shape[0])
+
+
+def mesh_adjacency(faces, n_vertices):
+    """gpnerf_mesh_adjacency on device faces (int32 [m,3]) of a mesh of n_vertices vertices -> MeshAdjacency: the unique edges' classes
+    counted, every vertex's unique neighbours in ascending index, the vertex flags.  include/gpnerf_hip.h states the definition.
+    Nothing is read back; the workspace's size is a formula of the two counts."""
+    lib = L.lib()
+    nv, nf = _adjacency_faces(faces, n_vertices, "mesh_adjacency")
+    nbytes = int(lib.gpnerf_mesh_adjacency_workspace_bytes(nv, nf))
+    offsets = (C.c_int64 * 3)()
+    if nbytes <= 0 or lib.gpnerf_mesh_adjacency_layout(nv, nf, offsets) != 0:
+        raise L.GpnerfError(f"mesh_adjacency: sizes refused ({nv} vertices, {nf} faces; at most {L.ADJACENCY_MAX_FACES} faces)")
+    dev = faces.device
+    ws = torch.empty((nbytes,), device=dev, dtype=torch.uint8)
+    stats = torch.empty((len(L.TOPOLOGY_STATS),), device=dev, dtype=torch.int64)
+    L.check(lib.gpnerf_mesh_adjacency(faces.data_ptr() if nf else None, nf, nv, ws.data_ptr(), ws.numel(), stats.data_ptr(), _stream_ptr(dev)),
+            "gpnerf_mesh_adjacency")
+    return MeshAdjacency(faces, nv, ws, stats, [int(o) for o in offsets])
+
+
+def mesh_topology(faces, n_vertices):
+    """the topology counts of a device mesh: mesh_adjacency(faces, n_vertices).stats, device int64 [10]; read_mesh_topology names them"""
+    return mesh_adjacency(faces, n_vertices).stats
+
+
+def read_mesh_topology(stats):
+    """mesh_topology's stats on the host (a tensor or array of 10) -> dict of the _lib.TOPOLOGY_STATS names, plus `closed` (no boundary
+    and no non-manifold edge), `oriented` (no inconsistent and no non-manifold edge) and `watertight` (both).  Connected components and
+    the genus are not counted."""
+    row = np.asarray(stats.detach().cpu() if isinstance(stats, torch.Tensor) else stats).astype(np.int64).reshape(-1)
+    if row.shape != (len(L.TOPOLOGY_STATS),):
+        raise L.GpnerfError(f"read_mesh_topology: expected {len(L.TOPOLOGY_STATS)} counts, got {row.shape}")
+    res = {k: int(v) for k, v in zip(L.TOPOLOGY_STATS, row)}
+    res["closed"] = res["boundary_edges"] == 0 and res["nonmanifold_edges"] == 0
+    res["oriented"] = res["inconsistent_edges"] == 0 and res["nonmanifold_edges"] == 0
+    res["watertight"] = res["closed"] and res["oriented"]
+    return res
+
+
+def smooth_mesh(vertices, faces=None, adjacency=None, iterations=10, lam=0.5, mu=-0.53, pin_boundary=True):
+    """gpnerf_mesh_smooth: Taubin's lambda | mu filter on a device mesh -> new device vertices float32 [n,3]; the faces are untouched.
+    One iteration is a Jacobi pass with factor lam and one with factor mu over every vertex's unique neighbours, summed in float64 in
+    ascending neighbour index (include/gpnerf_hip.h): the result does not depend on the order of the faces and is bit-reproducible.
+    adjacency: a MeshAdjacency of this mesh to reuse; without one it is built from `faces` (int32 [m,3]).  pin_boundary (default): the
+    vertices on a boundary or non-manifold edge stay where they are.  lam in (0, 1], mu in [-1, 0], iterations in [0, 10 000] (0: a
+    copy).  Nothing is read back."""
+    lib = L.lib()
+    if not isinstance(vertices, torch.Tensor):
+        raise L.GpnerfError("smooth_mesh: vertices must be a device tensor (mesh_to_device uploads a Mesh)")
+    _require_gpu(vertices, "smooth_mesh: vertices")
+    if vertices.dtype != torch.float32 or vertices.dim() != 2 or vertices.shape[1] != 3 or not vertices.is_contiguous():
+        raise L.GpnerfError(f"smooth_mesh: expected contiguous float32 vertices [n,3], got {vertices.dtype} {tuple(vertices.shape)}")
+    nv = int(vertices.shape[0])
+    if isinstance(iterations, bool) or not isinstance(iterations, (int, np.integer)) or not 0 <= iterations <= L.SMOOTH_MAX_ITERATIONS:
+        raise L.GpnerfError(f"smooth_mesh: iterations must be an integer in [0, {L.SMOOTH_MAX_ITERATIONS}], got {iterations!r}")
+    lam, mu = float(lam), float(mu)
+    if not (0.0 < lam <= 1.0) or not (-1.0 <= mu <= 0.0):
+        raise L.GpnerfError(f"smooth_mesh: lam must be in (0, 1] and mu in [-1, 0], got {lam!r} and {mu!r}")
+    if adjacency is None:
+        if faces is None:
+            raise L.GpnerfError("smooth_mesh: give faces or an adjacency")
+        _adjacency_faces(faces, nv, "smooth_mesh")
+        if faces.device != vertices.device:
+            raise L.GpnerfError("smooth_mesh: vertices and faces are on different devices")
+        adjacency = mesh_adjacency(faces, nv)
+    elif not isinstance(adjacency, MeshAdjacency) or adjacency.n_vertices != nv or adjacency.workspace.device != vertices.device:
+        raise L.GpnerfError(f"smooth_mesh: adjacency must be a MeshAdjacency of a mesh of {nv} vertices on {vertices.device}")
+    out = torch.empty_like(vertices)
+    ws = adjacency.workspace
+    L.check(lib.gpnerf_mesh_smooth(vertices.data_ptr() if nv else None, nv, ws.data_ptr(), ws.numel(), int(iterations), lam, mu,
+                                   L.SMOOTH_PIN_BOUNDARY if pin_boundary else 0, out.data_ptr() if nv else None, _stream_ptr(vertices.device)),
+            "gpnerf_mesh_smooth")
+    return out
+
+
 def extract_mesh(frame, voxel_size, bounds_min, Rh, Th, neg_ray=False, iso=1.0 / 50.0, host=None, clean=None, fill_cavities=None,
-                 normals=False, lattice=None, simplify=None):
+                 normals=False, lattice=None, simplify=None, smooth=None, topology=False):
     """The geometry mode of demo_render.py's render_rays (:166-175, 249-311, 366-376) on the device: the box of the occupied voxels,
     the lattice, the alpha cube and its marching-cubes mesh.  Two host reads: the box (6 values) and the mesh counts (2).
     Returns {"cube" (device [X+20,Y+20,Z+20]), "vertices", "faces" (device), "axes", "can_bounds", "n_kept" (device int64),
@@ -1037,8 +1160,11 @@ def extract_mesh(frame, voxel_size, bounds_min, Rh, Th, neg_ray=False, iso=1.0 /
     -1/2, -1/2) and cells = ceil(dim / k) + 1 (for an integer k the lattice planes, on which marching-cubes vertices have two integer
     coordinates, never sit on a cell boundary); "vertices" and "faces" are then the simplified mesh, "normals" are taken at ITS
     vertices, "simplify_stats" (device int64 [8], _lib.SIMPLIFY_STATS) is added, and the call has one more host read (the two sizes).
-    The cells are cubes in index units: geometric on cubic voxels, as the reference's are.  With all four off no further launch is
-    enqueued.
+    The cells are cubes in index units: geometric on cubic voxels, as the reference's are.  smooth: a number n > 0 of Taubin
+    iterations (smooth_mesh at its defaults: lam 0.5, mu -0.53, open borders pinned), which run behind marching cubes and simplify and
+    in front of the normals, which are then taken at the smoothed vertices; topology: the mesh's topology counts.  With either,
+    "topology_stats" (device int64 [10], _lib.TOPOLOGY_STATS: of the mesh as returned -- smoothing moves no face) is added, the
+    adjacency is built once, and no host read is added.  With all six off no further launch is enqueued.
     lattice: a ready (cube, axes, n_kept) -- the dense renderer's hull-carved cube (density_lattice(inside=...)) -- in place of the
     box, the lattice and the occupancy-culled cube; cleaning, marching cubes, normals and "lattice" are then the same code.  The box
     read does not happen and "can_bounds" is left out."""
@@ -1061,6 +1187,12 @@ def extract_mesh(frame, voxel_size, bounds_min, Rh, Th, neg_ray=False, iso=1.0 /
         cells = [int(np.ceil(d / k)) + 1 for d in surface.shape]
         res["vertices"], res["faces"], res["simplify_stats"], _ = simplify_mesh(res["vertices"], res["faces"], k, lo=(-0.5, -0.5, -0.5),
                                                                                 cells=cells)
+    n_smooth = parse_smooth(smooth, "extract_mesh: smooth")
+    if n_smooth is not None or topology:
+        adjacency = mesh_adjacency(res["faces"], int(res["vertices"].shape[0]))
+        res["topology_stats"] = adjacency.stats
+        if n_smooth is not None:
+            res["vertices"] = smooth_mesh(res["vertices"], adjacency=adjacency, iterations=n_smooth)
     if normals:
         res["normals"] = mesh_normals(surface, res["vertices"], step=np.asarray(vs, dtype=np.float64).ravel()[:3])
     return res

@@ -91,7 +91,8 @@ class Mesh:
     """vertices float64 [nv,3], faces int64 [nf,3] (trimesh's names), vertex_colors float32 [nv,3] in [0, 1] or None, vertex_normals
     float32 [nv,3] or None; export() writes a binary little-endian PLY.  The vertices are marching cubes' (one per crossed lattice edge)
     or, with the renderer's mesh_simplify, one per occupied cell of the clustering grid (frame.simplify_mesh), still in index units of
-    the cube; colours and normals belong to whichever vertices the mesh carries."""
+    the cube, and with mesh_smooth moved by Taubin's filter (frame.smooth_mesh); colours and normals belong to whichever vertices the
+    mesh carries."""
 
     def __init__(self, vertices, faces, vertex_colors=None, vertex_normals=None):
         self.vertices = np.ascontiguousarray(vertices, dtype=np.float64).reshape(-1, 3)

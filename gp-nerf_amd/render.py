@@ -57,7 +57,7 @@ class Renderer(nn.Module):
     def __init__(self, encoder, nerfhead, is_train=False, neg_ray_train=False, neg_ray_val=False, n_rays=1024,
                  n_samples=64, voxel_size=(0.005, 0.005, 0.005), chunk=64, mesh_th=-1, early_term=None, term_eps=1e-5,
                  progressive=False, split_f16=None, sharded_outputs="all", shard_group=None, encoder_graph=None, fold_levels=None, reserve_cus=None,
-                 mesh_colors=None, mesh_clean=None, mesh_normals=None, mesh_simplify=None):
+                 mesh_colors=None, mesh_clean=None, mesh_normals=None, mesh_simplify=None, mesh_smooth=None, mesh_topology=None):
         super().__init__()
         self.encoder = encoder
         self.nerfhead = nerfhead
@@ -124,6 +124,12 @@ class Renderer(nn.Module):
         # clustering over cubic cells of k lattice steps (gpnerf_mesh_simplify_*) before normals and colours are taken.  Off by default.
         self.mesh_simplify = F_.parse_simplify(os.environ.get("GPNERF_MESH_SIMPLIFY", "0") if mesh_simplify is None else mesh_simplify,
                                                "mesh_simplify / GPNERF_MESH_SIMPLIFY")
+        # mesh_smooth (GPNERF_MESH_SMOOTH = unset / 0 (off) or n > 0): n iterations of Taubin's lambda | mu filter on the device
+        # (gpnerf_mesh_smooth) behind marching cubes and the simplification, before normals and colours are taken.  mesh_topology
+        # (GPNERF_MESH_TOPOLOGY=1): `mesh_stats` gains the mesh's topology counts (gpnerf_mesh_adjacency).  Both off by default.
+        self.mesh_smooth = F_.parse_smooth(os.environ.get("GPNERF_MESH_SMOOTH", "0") if mesh_smooth is None else mesh_smooth,
+                                           "mesh_smooth / GPNERF_MESH_SMOOTH")
+        self.mesh_topology = (os.environ.get("GPNERF_MESH_TOPOLOGY", "0") == "1") if mesh_topology is None else bool(mesh_topology)
 
     # ---- helpers the reference exposes as methods (stage entry points) ----------------------------
     def _neg_ray(self, batch):
@@ -309,9 +315,10 @@ class Renderer(nn.Module):
     @staticmethod
     def _mesh_stats(m):
         """extract_mesh's device counts as one dict: gpnerf_cube_clean's six (_lib.CUBE_STATS) with mesh_clean, the simplification's
-        eight (_lib.SIMPLIFY_STATS) with mesh_simplify; None with both off."""
+        eight (_lib.SIMPLIFY_STATS) with mesh_simplify, the topology's ten (_lib.TOPOLOGY_STATS) with mesh_smooth or mesh_topology; None
+        with all of them off."""
         stats = None
-        for key, names in (("clean_stats", L.CUBE_STATS), ("simplify_stats", L.SIMPLIFY_STATS)):
+        for key, names in (("clean_stats", L.CUBE_STATS), ("simplify_stats", L.SIMPLIFY_STATS), ("topology_stats", L.TOPOLOGY_STATS)):
             if key in m:
                 stats = {**(stats or {}), **dict(zip(names, m[key].cpu().tolist()))}
         return stats
@@ -329,8 +336,10 @@ class Renderer(nn.Module):
         from the gradient of the cube the mesh was made from, scaled by 1 / voxel_size per axis (geometric normals on an anisotropic
         lattice), in the vertices' frame (the cube's index axes).  With mesh_simplify = k, the mesh is the quadric vertex clustering
         of that surface over cubic cells of k lattice steps (frame.simplify_mesh: one more host read, the two sizes); normals and
-        colours are taken at the simplified vertices, and `mesh_stats` gains the eight counts of _lib.SIMPLIFY_STATS.  With all of them
-        off, extract_mesh enqueues exactly the launches it did before there were these options."""
+        colours are taken at the simplified vertices, and `mesh_stats` gains the eight counts of _lib.SIMPLIFY_STATS.  With mesh_smooth
+        = n the vertices then go through n Taubin iterations (frame.smooth_mesh; no host read) before normals and colours are taken,
+        and with it or mesh_topology `mesh_stats` gains the ten counts of _lib.TOPOLOGY_STATS.  With all of them off, extract_mesh
+        enqueues exactly the launches it did before there were these options."""
         dev = batch["src_imgs"].device
         torch.cuda.synchronize(dev)
         te = time.time()
@@ -348,7 +357,7 @@ class Renderer(nn.Module):
         ev[2].record()
         m = F_.extract_mesh(frame, self.voxel_size, batch["bounds"][0, 0], batch["Rh"][0], batch["Th"][0], neg_ray=self._neg_ray(batch),
                             iso=M_.ISO_REFERENCE, host=box_host, clean=self.mesh_clean, normals=self.mesh_normals,
-                            simplify=self.mesh_simplify)
+                            simplify=self.mesh_simplify, smooth=self.mesh_smooth, topology=self.mesh_topology)
         colours = None
         if self.mesh_colors:
             colours = F_.query_points(frame, m["vertices"], neg_ray=self._neg_ray(batch), want=("rgb",), lattice=m["lattice"])["rgb"]
@@ -380,8 +389,8 @@ class Renderer(nn.Module):
               [1,2,3] -- the axes are frame.dataset_lattice_axes' and the hull is carved on the device (gpnerf_visual_hull): the
               loader neither builds the 12 B/point `pts` array nor carves.
         Returns `cube` (the padded alpha cube, float32 numpy), `mesh` (mesh.Mesh, vertices in index units of the padded cube), `axes`
-        (three host float32 arrays), `n_inside` (kept points), `time_slots`, `etime`, `rtime`, and `mesh_stats` with mesh_clean or
-        mesh_simplify.  mesh_clean / mesh_normals / mesh_colors / mesh_simplify act as in render_mesh.  Host reads: the constants (with the axes or the cameras) before
+        (three host float32 arrays), `n_inside` (kept points), `time_slots`, `etime`, `rtime`, and `mesh_stats` with mesh_clean,
+        mesh_simplify, mesh_smooth or mesh_topology.  mesh_clean / mesh_normals / mesh_colors / mesh_simplify / mesh_smooth / mesh_topology act as in render_mesh.  Host reads: the constants (with the axes or the cameras) before
         the encoder, the mesh counts, and the results."""
         dev = batch["src_imgs"].device
         have_a = "pts" in batch and "inside" in batch
@@ -426,7 +435,8 @@ class Renderer(nn.Module):
         neg = self._neg_ray(batch)
         cube, n_kept = F_.density_lattice(frame, axes, neg_ray=neg, pad=F_.MESH_PAD, inside=inside)
         m = F_.extract_mesh(frame, self.voxel_size, None, None, None, neg_ray=neg, iso=self.mesh_th, host=[vs_host], clean=self.mesh_clean,
-                            normals=self.mesh_normals, lattice=(cube, axes, n_kept), simplify=self.mesh_simplify)
+                            normals=self.mesh_normals, lattice=(cube, axes, n_kept), simplify=self.mesh_simplify, smooth=self.mesh_smooth,
+                            topology=self.mesh_topology)
         colours = None
         if self.mesh_colors:
             colours = F_.query_points(frame, m["vertices"], neg_ray=neg, want=("rgb",), lattice=m["lattice"])["rgb"]

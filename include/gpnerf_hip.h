@@ -823,6 +823,90 @@ int gpnerf_mesh_simplify_emit(const float* vertices, int64_t n_vertices, const i
                               size_t workspace_bytes, int64_t n_out_vertices, int64_t n_out_faces, float* out_vertices, int32_t* out_faces,
                               int32_t* vertex_map, void* stream);
 
+/* ---- the adjacency of a mesh, its topology counts and Taubin smoothing (gpnerf_meshtopo.hip): the unique undirected edges of a
+ * triangle mesh with their classes, the counts that say whether it is closed and oriented, every vertex's unique neighbours as a
+ * CSR, and the lambda | mu filter over that CSR (Taubin 1995: a shrinking pass followed by an inflating one, which smooths the
+ * staircase of a marching-cubes surface without shrinking the body the way plain Laplacian smoothing does).  All calls: kernel
+ * launches only, on the caller's stream; nothing allocated, nothing waited for; every launch sized from the arguments alone; every
+ * data-dependent length stays in the workspace; both capture into a HIP graph and replay with the same bits; the result is a
+ * function of the inputs alone and of no launch geometry, arrival order or order of the faces (integer atomics for counts and
+ * cursors, no float atomic; the smoothing has no atomic at all).
+ * faces: device int32 [n_faces][3]; n_vertices 0 to 2^31 - 1; n_faces 0 to 715 827 882 (3 n_faces < 2^31: a half-edge's number fits
+ * 31 bits); faces may be NULL where n_faces is 0.  Vertex coordinates play no part in the adjacency or the counts.
+ *
+ * THE DEFINITION
+ *   1. a face is USABLE iff its three indices are in [0, n_vertices) and pairwise distinct.  The others are dropped and counted,
+ *      never clamped (the rasteriser's and the simplifier's rule).
+ *   2. a usable face (a, b, c) contributes the directed HALF-EDGES a -> b, b -> c, c -> a.  An EDGE is a distinct unordered pair
+ *      {lo < hi}; its fwd is the number of half-edges lo -> hi, its bwd the number of half-edges hi -> lo, its multiplicity m = fwd + bwd.
+ *      m == 1: BOUNDARY.  m == 2 and fwd == bwd == 1: manifold and consistently oriented.  m == 2 otherwise: INCONSISTENT.
+ *      m >= 3: NON-MANIFOLD.
+ *   3. the stats, int64 [GPNERF_TOPOLOGY_STATS], every one written by the call: FACES_USED, FACES_DROPPED, VERTICES_REFERENCED (by a
+ *      usable face), EDGES, BOUNDARY_EDGES, NONMANIFOLD_EDGES, INCONSISTENT_EDGES, EULER = VERTICES_REFERENCED - EDGES + FACES_USED,
+ *      BOUNDARY_VERTICES (the vertices on a boundary or non-manifold edge), MAX_VALENCE (the largest number of neighbours).  The mesh
+ *      is CLOSED iff it has no boundary and no non-manifold edge, ORIENTED iff no inconsistent and no non-manifold edge, WATERTIGHT iff
+ *      both.  Connected components and the genus are not counted: a label propagation over a mesh needs a data-dependent number of
+ *      launches or a device-wide loop, and the floaters are dealt with on the cube (gpnerf_cube_clean).
+ *   4. the ADJACENCY, a CSR inside the workspace at gpnerf_mesh_adjacency_layout's byte offsets: start int64 [n_vertices + 1] (start[0]
+ *      = 0), neighbours int32 with a capacity of 6 n_faces of which start[n_vertices] = 2 EDGES entries are in use -- vertex v's
+ *      neighbours, the other ends of its edges, each once, in ASCENDING index at start[v] .. start[v + 1] --, and vertex_flags uint8
+ *      [n_vertices]: GPNERF_VERTEX_REFERENCED | GPNERF_VERTEX_BOUNDARY (on a boundary or non-manifold edge).
+ *   5. SMOOTHING.  One ITERATION is two Jacobi passes, the first with factor t = lam, the second with t = mu.  A pass reads the old
+ *      positions and writes new ones for every vertex i that has k >= 1 neighbours and is not pinned: per coordinate, in float64 on
+ *      the float32 positions widened, nothing fused: s = 0.0; for the neighbours j in ascending index s = s + x_j; then
+ *      x_i' = float32(x_i + t (s / k - x_i)).  Every other vertex is copied as it is.  PINNED, with GPNERF_SMOOTH_PIN_BOUNDARY: the
+ *      vertices flagged GPNERF_VERTEX_BOUNDARY.  A vertex no usable face references has no neighbour and never moves.  Values that
+ *      are not finite propagate as IEEE has them.  iterations == 0 is a copy.  The order of the sum is the neighbours' index, not
+ *      the faces' order: shuffling a mesh's faces changes no bit of the adjacency or of the smoothed vertices.
+ *
+ * gpnerf_mesh_adjacency fills the workspace and sets stats (device).  Launches: a clear; a lane per face (usable?, one integer atomic
+ * per half-edge on the list length of its lower vertex); a three-launch integer scan (64-bit starts); a lane per face (lists filled
+ * by cursor with the keys (hi, 3 face + corner, direction)); a lane per half-edge that walks the list of its lower vertex and counts
+ * the half-edges of its edge by direction and those of them with a smaller key -- the one with none is the edge's head: it classifies
+ * the edge and adds 1 to both ends' degrees; no sorted copy of the lists is needed, since nothing but these counts is read from
+ * them, and the faces used and the edges are counted by the two scans (a third of the half-edges, half the neighbour entries) --; a scan; a lane per half-edge (heads fill both ends' neighbour lists by cursor); a lane per half-edge (heads
+ * place both entries at the number of smaller entries in their list: the ascending order); a lane per vertex (counts over the
+ * vertices); one lane (stats).  The two walks are quadratic in a vertex's number of half-edges / neighbours but spread over as many
+ * lanes: nothing at a valence of 6, and the hub of a fan of 3 000 triangles costs 6 000 x 6 000 + 3 001 x 3 001 short steps.
+ * gpnerf_mesh_smooth(vertices float [n_vertices][3] -> out_vertices float [n_vertices][3], which may be the same array) runs 2
+ * iterations launches of a lane per vertex on a workspace gpnerf_mesh_adjacency filled for a mesh of n_vertices vertices; when the
+ * workspace holds no finished adjacency of that many vertices the launches write nothing.  Between the passes the positions live in
+ * the workspace as two float4 arrays (a neighbour is one 16-byte load); the first pass reads `vertices`, the last writes
+ * `out_vertices`.  lam, mu: double.  flags: 0 or GPNERF_SMOOTH_PIN_BOUNDARY.
+ * workspace: gpnerf_mesh_adjacency_workspace_bytes(n_vertices, n_faces) bytes (host arithmetic only, from the worst-case capacities
+ * -- 3 n_faces half-edges, 6 n_faces neighbour entries, two float4 position arrays --, so that no host read is needed anywhere; 0
+ * for what the calls refuse) = 256 + 2 a(8 (nv + 1)) + a(nv) + 2 a(16 nv) + 2 a(4 (nv + 1)) + 2 a(4 nv) + a(8 ceil((nv + 1) / 2048))
+ * + 2 a(24 nf) + a(3 nf), with a() rounding up to a multiple of 256.  gpnerf_mesh_adjacency_layout (host only): offsets[
+ * GPNERF_ADJACENCY_START / _NEIGHBOURS / _VERTEX_FLAGS] = the byte offsets of the three arrays of 4. inside the workspace, each a
+ * multiple of 256.
+ * GPNERF_E_ARG, before anything is launched: a null workspace, stats or offsets; null faces with n_faces > 0; null vertices or
+ * out_vertices with n_vertices > 0; a count that is negative or beyond the limits above; a workspace under the formula (smooth:
+ * under the formula at n_faces = 0); smooth: lam outside (0, 1], mu outside [-1, 0], either not finite, iterations outside
+ * [0, 10 000], an unknown flag. */
+#define GPNERF_TOPOLOGY_FACES_USED 0
+#define GPNERF_TOPOLOGY_FACES_DROPPED 1
+#define GPNERF_TOPOLOGY_VERTICES_REFERENCED 2
+#define GPNERF_TOPOLOGY_EDGES 3
+#define GPNERF_TOPOLOGY_BOUNDARY_EDGES 4
+#define GPNERF_TOPOLOGY_NONMANIFOLD_EDGES 5
+#define GPNERF_TOPOLOGY_INCONSISTENT_EDGES 6
+#define GPNERF_TOPOLOGY_EULER 7
+#define GPNERF_TOPOLOGY_BOUNDARY_VERTICES 8
+#define GPNERF_TOPOLOGY_MAX_VALENCE 9
+#define GPNERF_TOPOLOGY_STATS 10
+#define GPNERF_VERTEX_REFERENCED 1
+#define GPNERF_VERTEX_BOUNDARY 2
+#define GPNERF_ADJACENCY_START 0
+#define GPNERF_ADJACENCY_NEIGHBOURS 1
+#define GPNERF_ADJACENCY_VERTEX_FLAGS 2
+#define GPNERF_SMOOTH_PIN_BOUNDARY 1u
+size_t gpnerf_mesh_adjacency_workspace_bytes(int64_t n_vertices, int64_t n_faces);
+int gpnerf_mesh_adjacency_layout(int64_t n_vertices, int64_t n_faces, int64_t* offsets);
+int gpnerf_mesh_adjacency(const int32_t* faces, int64_t n_faces, int64_t n_vertices, void* workspace, size_t workspace_bytes, int64_t* stats,
+                          void* stream);
+int gpnerf_mesh_smooth(const float* vertices, int64_t n_vertices, void* workspace, size_t workspace_bytes, int32_t iterations, double lam,
+                       double mu, uint32_t flags, float* out_vertices, void* stream);
+
 /* ---- per-frame sparse convolution pyramid (gpnerf_volume.hip), replacing the external spconv v1.2.1 calls of
  * libs/nerfheads/networks/SparseConvNet.py:22-111 (SubMConv3d / SparseConv3d + BatchNorm1d + ReLU, .dense()).
  * A sparse tensor is: features [M][C] fp32, coords [M][3] int32 (d,h,w), and a dense int32 index grid [D][H][W]
