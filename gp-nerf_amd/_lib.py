@@ -155,6 +155,12 @@ ADJACENCY_START, ADJACENCY_NEIGHBOURS, ADJACENCY_VERTEX_FLAGS = range(3)
 SMOOTH_PIN_BOUNDARY = 1
 SMOOTH_MAX_ITERATIONS = 10000
 ADJACENCY_MAX_FACES = ((1 << 31) - 1) // 3
+# gpnerf_mesh_voxelize's rules and stats, gpnerf_voxel_stats' row (include/gpnerf_hip.h GPNERF_VOXEL_*)
+VOXEL_PARITY, VOXEL_NONZERO = range(2)
+VOXEL_RULES = {"parity": VOXEL_PARITY, "nonzero": VOXEL_NONZERO}
+VOXEL_STATS = ("used", "skipped_vertex", "skipped_area", "crossings", "open_columns", "occupied")
+VOXEL_A, VOXEL_B, VOXEL_BOTH, VOXEL_EITHER, VOXEL_COUNTS = range(5)
+VOXEL_MAX_POINTS = 1 << 28
 
 # every symbol include/gpnerf_hip.h declares: (restype, argtypes)
 SYMBOLS = {
@@ -274,6 +280,13 @@ SYMBOLS = {
     "gpnerf_mesh_adjacency": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "gpnerf_mesh_smooth": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_size_t, C.c_int32, C.c_double, C.c_double, C.c_uint32, C.c_void_p,
                                      C.c_void_p]),
+    "gpnerf_mesh_voxelize_workspace_bytes": (C.c_size_t, [C.c_int64, C.POINTER(C.c_int32), C.c_int32]),
+    "gpnerf_mesh_voxelize": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, DP, C.POINTER(C.c_int32), C.c_int32, C.c_void_p, C.c_size_t,
+                                       C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gpnerf_voxel_from_cube": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_float, C.c_void_p, C.c_void_p]),
+    "gpnerf_voxel_unpack": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_void_p, C.c_void_p]),
+    "gpnerf_voxel_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_void_p, C.c_void_p]),
+    "gpnerf_voxel_contains": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), DP, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "gpnerf_head_layout": (C.c_int, [C.POINTER(C.c_int32)]),
     "gpnerf_strerror": (C.c_char_p, [C.c_int]),
     "gpnerf_rays_per_tile": (C.c_int32, []),

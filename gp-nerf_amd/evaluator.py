@@ -256,12 +256,21 @@ class MeshEvaluator:
     slot of ten counts (_lib.TOPOLOGY_STATS) per frame, no host read.  `summarize()` reads the slots in one copy and adds
     `watertight_frames` (how many frames' meshes are closed and oriented), `topology_<name>` for the edge counts and `euler` (means
     over the frames) and their per-frame lists, and saves `<result_path>/topology_metrics.npy` (a structured array: frame_index, the
-    ten counts, closed, oriented, watertight)."""
+    ten counts, closed, oriented, watertight).
+    volume (off by default; the third standard reconstruction number beside Chamfer and normal consistency, and the one that compares
+    solids): a batch with `gt_mesh` and an output with `axes` make `evaluate` voxelise both meshes on the frame's padded cube lattice
+    (frame.voxelize_mesh, rule `volume_rule`: "nonzero" unites a scan's separate parts, "parity" is indifferent to orientation) -- the
+    predicted mesh as it is exported, in index units (lo 0, step 1), the scan with lo = axes[a][0] - PAD * step_a and the axes' steps,
+    to_lattice_frame's -- and enqueue frame.voxel_stats into a slot: no host read.  `summarize()` reads the slots in one copy and adds
+    `volume_iou`, `volume_pred`, `volume_gt` (the volumes in the axes' unit cubed; means over the frames) and
+    `volume_open_columns_pred` / `_gt` (lattice columns through which a mesh leaks: more than 0 says it is not closed, and its volume
+    is not to be trusted there), their per-frame lists, and saves `<result_path>/volume_metrics.npy`.  A `gt_mesh` with an output
+    that has no `axes` raises a GpnerfError naming the key.  Off, nothing changes."""
     PAD = 10                              # if_nerf_mesh.py:20, the np.pad(cube, 10) of BaseRender.py:269
 
     def __init__(self, result_path, mesh_th, export_mesh=False, metric_samples=100000, metric_thresholds=(0.005, 0.01, 0.02),
                  metric_max_dist=float("inf"), metric_device=None, metric_cell_cap=None, metric_entry_cap=None, silhouette=False,
-                 topology=False):
+                 topology=False, volume=False, volume_rule="nonzero"):
         self.mesh_th = mesh_th
         self.export_mesh = bool(export_mesh)
         self.result_path = result_path
@@ -275,6 +284,10 @@ class MeshEvaluator:
         self._sil_slots, self._sil_frames = [], []
         self.topology = bool(topology)
         self._topo_slots, self._topo_frames = [], []
+        self.volume, self.volume_rule = bool(volume), str(volume_rule)
+        if self.volume_rule not in L.VOXEL_RULES:
+            raise L.GpnerfError(f"MeshEvaluator: volume_rule is 'parity' or 'nonzero', got {volume_rule!r}")
+        self._vol_slots, self._vol_frames, self._vol_cells = [], [], []
 
     SILHOUETTE_KEYS = ("hull_masks", "hull_Ks", "hull_RTs")
 
@@ -282,7 +295,60 @@ class MeshEvaluator:
     def has_mesh_metrics(self):
         """True once a frame with `gt_mesh` (or, with silhouette on, with masks and cameras; or any frame with topology on) has been evaluated and not yet summarized
         (evaluate_loop asks)"""
-        return bool(self._slots) or bool(self._sil_slots) or bool(self._topo_slots)
+        return bool(self._slots) or bool(self._sil_slots) or bool(self._topo_slots) or bool(self._vol_slots)
+
+    def _enqueue_volume(self, output, batch):
+        from . import frame as F
+        if "axes" not in output:
+            raise L.GpnerfError("MeshEvaluator(volume=True): the output has no 'axes', so the scan cannot be put on the frame's lattice "
+                                "(the inference renderer's render_mesh; the dense renderer's geometry mode returns axes)")
+        dev = torch.device(self.metric_device if self.metric_device is not None else "cuda:0")
+        ax = [np.asarray(a.detach().cpu() if hasattr(a, "detach") else a, dtype=np.float64).reshape(-1) for a in output["axes"]]
+        step = np.array([(a[-1] - a[0]) / (len(a) - 1) if len(a) > 1 else 1.0 for a in ax])      # to_lattice_frame's
+        lo = np.array([a[0] for a in ax]) - self.PAD * step
+        dims = tuple(len(a) + 2 * self.PAD for a in ax)
+        pv, pf = F.mesh_to_device(output["mesh"], dev)
+        gv, gf = F.mesh_to_device(batch["gt_mesh"], dev)
+        pred = F.voxelize_mesh(pv, pf, (0.0, 0.0, 0.0), (1.0, 1.0, 1.0), dims, rule=self.volume_rule)
+        gt = F.voxelize_mesh(gv, gf, lo, step, dims, rule=self.volume_rule)
+        slot = torch.empty((L.VOXEL_COUNTS + 2,), device=dev, dtype=torch.int64)         # the four counts, then each side's open columns
+        F.voxel_stats(pred, gt, out=slot[:L.VOXEL_COUNTS])
+        at = L.VOXEL_STATS.index("open_columns")
+        slot[L.VOXEL_COUNTS:].copy_(torch.stack([pred.stats[at], gt.stats[at]]))
+        self._vol_slots.append(slot)
+        self._vol_frames.append(self._scalar(batch["frame_index"]))
+        self._vol_cells.append(step.copy())
+
+    def _summarize_volumes(self):
+        """the volume slots -> (means, per-frame lists), volume_metrics.npy written; resets them"""
+        from . import frame as F
+        host = torch.stack(self._vol_slots).cpu().numpy()      # the one read
+        rows = [F.read_volume_metrics(h[:L.VOXEL_COUNTS], step) for h, step in zip(host, self._vol_cells)]
+        per_frame = {"volume_iou": [r["iou"] for r in rows], "volume_pred": [r["volume_a"] for r in rows], "volume_gt": [r["volume_b"] for r in rows],
+                     "volume_precision": [r["precision"] for r in rows], "volume_recall": [r["recall"] for r in rows],
+                     "volume_open_columns_pred": [int(h[L.VOXEL_COUNTS]) for h in host],
+                     "volume_open_columns_gt": [int(h[L.VOXEL_COUNTS + 1]) for h in host]}
+        metrics = {k: float(np.mean(v)) for k, v in per_frame.items()}
+        per_frame["volume_frame_index"] = list(self._vol_frames)
+        names = ("pred", "gt", "both", "either")
+        table = np.zeros(len(rows), dtype=[("frame_index", "i8")] + [(f"points_{k}", "i8") for k in names] +
+                         [("open_columns_pred", "i8"), ("open_columns_gt", "i8"), ("cell_volume", "f8")] +
+                         [(k, "f8") for k in ("iou", "precision", "recall", "volume_pred", "volume_gt")])
+        table["frame_index"] = self._vol_frames
+        for i, k in enumerate(names):
+            table[f"points_{k}"] = host[:, i]
+        table["open_columns_pred"], table["open_columns_gt"] = host[:, L.VOXEL_COUNTS], host[:, L.VOXEL_COUNTS + 1]
+        table["cell_volume"] = [float(np.prod(step)) for step in self._vol_cells]
+        for k in ("iou", "precision", "recall", "volume_pred", "volume_gt"):
+            table[k] = per_frame[f"volume_{k}" if not k.startswith("volume") else k]
+        os.makedirs(self.result_path, exist_ok=True)
+        np.save(os.path.join(self.result_path, "volume_metrics.npy"), table)        # a structured array: one row per frame
+        print(f"volume_iou: {metrics['volume_iou']}")
+        for side in ("pred", "gt"):
+            if metrics[f"volume_open_columns_{side}"] > 0:
+                print(f"volume: the {side} mesh is not closed ({metrics[f'volume_open_columns_' + side]} open columns per frame)")
+        self._vol_slots, self._vol_frames, self._vol_cells = [], [], []
+        return metrics, per_frame
 
     def _enqueue_silhouette(self, output, batch):
         from . import frame as F
@@ -331,6 +397,8 @@ class MeshEvaluator:
                                               max_dist=self.metric_max_dist, device=self.metric_device, cell_cap=self.metric_cell_cap,
                                               entry_cap=self.metric_entry_cap))
             self._frames.append(self._scalar(batch["frame_index"]))
+            if self.volume:
+                self._enqueue_volume(output, batch)
         if self.silhouette and all(k in batch for k in self.SILHOUETTE_KEYS):
             self._enqueue_silhouette(output, batch)
         if self.topology:
@@ -391,8 +459,9 @@ class MeshEvaluator:
         return metrics, per_frame
 
     def summarize(self):
-        if self._sil_slots or self._topo_slots:
-            parts = ([self._summarize_silhouettes()] if self._sil_slots else []) + ([self._summarize_topology()] if self._topo_slots else [])
+        if self._sil_slots or self._topo_slots or self._vol_slots:
+            parts = (([self._summarize_silhouettes()] if self._sil_slots else []) + ([self._summarize_topology()] if self._topo_slots else []) +
+                     ([self._summarize_volumes()] if self._vol_slots else []))
             metrics = self._summarize_mesh_metrics() if self._slots else {"per_frame": {}}
             per_frame = metrics.pop("per_frame")
             for means, frames in parts:

@@ -1535,3 +1535,134 @@ def read_silhouette_metrics(host_counts):
     per["ignored"] = [int(v) for v in c[:, L.SILHOUETTE_IGNORED]]
     res["per_view"] = per
     return res
+
+
+# ---- voxelising a mesh: solid occupancy on a lattice, volume and volume IoU (csrc/gpnerf_voxelize.hip)
+
+def _voxel_dims(dims, what):
+    d = tuple(int(v) for v in dims)
+    if len(d) != 3 or min(d) < 1 or d[0] * d[1] * d[2] > L.VOXEL_MAX_POINTS:
+        raise L.GpnerfError(f"{what}: dims {d} refused (three entries, each >= 1, at most 2^28 points)")
+    return d
+
+
+def _voxel_lattice(lo, step, what):
+    lat = np.concatenate([np.asarray(lo, np.float64).ravel(), np.asarray(step, np.float64).ravel()])
+    if lat.shape != (6,) or not np.isfinite(lat).all() or not (lat[3:] > 0).all():
+        raise L.GpnerfError(f"{what}: lo and step must be three finite numbers each, step > 0, got {lat.tolist()}")
+    return np.ascontiguousarray(lat)
+
+
+class VoxelGrid:
+    """Packed solid occupancy on a lattice (the counterpart of the reference's libs/utils/voxels.py VoxelGrid, on lattice POINTS and on
+    the device).  bits: device uint32 [nx,ny,ceil(nz/32)], point k of column (i, j) in bit k & 31 of word k >> 5; dims: (nx, ny, nz);
+    lo, step: float64 [3], point (i, j, k) sits at lo + (i, j, k) * step; stats: voxelize_mesh's device int64 [6] (_lib.VOXEL_STATS)
+    or None for a grid that came from a cube."""
+
+    def __init__(self, bits, dims, lo=(0.0, 0.0, 0.0), step=(1.0, 1.0, 1.0), stats=None):
+        self.bits, self.dims, self.stats = bits, _voxel_dims(dims, "VoxelGrid"), stats
+        lat = _voxel_lattice(lo, step, "VoxelGrid")
+        self.lo, self.step = lat[:3].copy(), lat[3:].copy()
+
+    def _c_dims(self):
+        return (C.c_int32 * 3)(*self.dims)
+
+    @property
+    def occupied(self):
+        """the number of occupied points, device int64 [] (a view of stats where the grid has them; otherwise a popcount is enqueued)"""
+        if self.stats is not None:
+            return self.stats[L.VOXEL_STATS.index("occupied")]
+        return voxel_stats(self)[L.VOXEL_A]
+
+    @property
+    def cell_volume(self):
+        return float(self.step[0] * self.step[1] * self.step[2])
+
+    def dense(self):
+        """gpnerf_voxel_unpack: a device float32 cube [nx,ny,nz] of 0 / 1, which marching_cubes(iso=0.5) and cube_clean take"""
+        cube = torch.empty(self.dims, device=self.bits.device, dtype=torch.float32)
+        L.check(L.lib().gpnerf_voxel_unpack(self.bits.data_ptr(), self._c_dims(), cube.data_ptr(), _stream_ptr(self.bits.device)),
+                "gpnerf_voxel_unpack")
+        return cube
+
+    def contains(self, points):
+        """gpnerf_voxel_contains: device uint8 [n], 1 where the lattice point nearest to the point (device float32 [n,3]; rint per
+        axis, half to even) is inside the dims and occupied; 0 for points outside or not finite"""
+        if not isinstance(points, torch.Tensor):
+            raise L.GpnerfError("VoxelGrid.contains: points must be a device tensor")
+        pts = _points(points, "VoxelGrid.contains: points")
+        if pts.device != self.bits.device:
+            raise L.GpnerfError(f"VoxelGrid.contains: points on {pts.device}, the grid on {self.bits.device}")
+        n = int(pts.shape[0])
+        out = torch.empty((n,), device=self.bits.device, dtype=torch.uint8)
+        lat = np.concatenate([self.lo, self.step])
+        L.check(L.lib().gpnerf_voxel_contains(self.bits.data_ptr(), self._c_dims(), lat.ctypes.data_as(L.DP), pts.data_ptr() if n else None, n,
+                                              out.data_ptr() if n else None, _stream_ptr(self.bits.device)), "gpnerf_voxel_contains")
+        return out
+
+
+def voxelize_mesh(vertices, faces, lo, step, dims, rule="parity"):
+    """gpnerf_mesh_voxelize: the solid occupancy of a mesh on the lattice of dims = (nx, ny, nz) POINTS at lo + (i, j, k) * step, as a
+    VoxelGrid (bits and stats on the device, nothing read back).  vertices, faces: device float32 [nv,3] and int32 [nf,3]; or
+    faces=None and `vertices` a mesh.Mesh or a (vertices, faces) pair, which mesh_to_device uploads.  rule: "parity" (a point is
+    inside when an odd number of faces lie above it in its column: independent of the faces' order and orientation) or "nonzero" (the
+    signed count is not 0: overlapping closed parts unite).  include/gpnerf_hip.h states which face owns a column (half-open, exact)
+    and where it crosses; stats[_lib.VOXEL_STATS.index("open_columns")] > 0 says that the surface is not closed.  The workspace is
+    the per-stream scratch rasterize_mesh borrows."""
+    lib = L.lib()
+    if rule not in L.VOXEL_RULES:
+        raise L.GpnerfError(f"voxelize_mesh: rule is 'parity' or 'nonzero', got {rule!r}")
+    vertices, faces = _raster_mesh(vertices, faces, "voxelize_mesh")
+    d = _voxel_dims(dims, "voxelize_mesh")
+    lat = _voxel_lattice(lo, step, "voxelize_mesh")
+    cd = (C.c_int32 * 3)(*d)
+    nv, nf, dev = int(vertices.shape[0]), int(faces.shape[0]), vertices.device
+    nbytes = int(lib.gpnerf_mesh_voxelize_workspace_bytes(nf, cd, L.VOXEL_RULES[rule]))
+    if nbytes <= 0:
+        raise L.GpnerfError(f"voxelize_mesh: refused ({nf} faces, dims {d})")
+    ws = _workspace(dev, nbytes)
+    bits = torch.empty((d[0], d[1], (d[2] + 31) // 32), device=dev, dtype=torch.int32)
+    stats = torch.empty((len(L.VOXEL_STATS),), device=dev, dtype=torch.int64)
+    ptr = lambda t: t.data_ptr() if t.numel() else None
+    L.check(lib.gpnerf_mesh_voxelize(ptr(vertices), nv, ptr(faces), nf, lat.ctypes.data_as(L.DP), cd, L.VOXEL_RULES[rule], ws.data_ptr(),
+                                     ws.numel(), bits.data_ptr(), stats.data_ptr(), _stream_ptr(dev)), "gpnerf_mesh_voxelize")
+    return VoxelGrid(bits, d, lat[:3], lat[3:], stats)
+
+
+def voxelize_cube(cube, iso=1.0 / 50.0, lo=(0.0, 0.0, 0.0), step=(1.0, 1.0, 1.0)):
+    """gpnerf_voxel_from_cube: the VoxelGrid of cube > iso (device float32 [X,Y,Z]; the iso value as marching_cubes takes it).  lo, step:
+    the lattice the grid is said to live on (index units by default, the frame of marching_cubes' vertices)."""
+    dims = _cube_dims(cube, "voxelize_cube")
+    d = _voxel_dims(cube.shape, "voxelize_cube")
+    bits = torch.empty((d[0], d[1], (d[2] + 31) // 32), device=cube.device, dtype=torch.int32)
+    L.check(L.lib().gpnerf_voxel_from_cube(cube.data_ptr(), dims, float(iso), bits.data_ptr(), _stream_ptr(cube.device)), "gpnerf_voxel_from_cube")
+    return VoxelGrid(bits, d, lo, step)
+
+
+def voxel_stats(a, b=None, out=None):
+    """gpnerf_voxel_stats: device int64 [4] (_lib.VOXEL_A, _B, _BOTH, _EITHER: the occupied points of a, of b, of both, of either) of
+    two VoxelGrids of the same dims; b None: B = BOTH = 0, EITHER = A.  out: an int64 [4] slot to write into.  Nothing is read back."""
+    for g, name in ((a, "a"), (b, "b")):
+        if g is None and name == "b":
+            continue
+        if not isinstance(g, VoxelGrid):
+            raise L.GpnerfError(f"voxel_stats: {name} must be a VoxelGrid")
+        _require_gpu(g.bits, f"voxel_stats: {name}")
+    if b is not None and (b.dims != a.dims or b.bits.device != a.bits.device):
+        raise L.GpnerfError(f"voxel_stats: the grids differ (dims {a.dims} on {a.bits.device}, {b.dims} on {b.bits.device})")
+    dev = a.bits.device
+    if out is None:
+        out = torch.empty((L.VOXEL_COUNTS,), device=dev, dtype=torch.int64)
+    L.check(L.lib().gpnerf_voxel_stats(a.bits.data_ptr(), b.bits.data_ptr() if b is not None else None, a._c_dims(), out.data_ptr(),
+                                       _stream_ptr(dev)), "gpnerf_voxel_stats")
+    return out
+
+
+def read_volume_metrics(host_counts, step):
+    """voxel_stats' counts on the host ([4], array or tensor) and the lattice's steps -> {"volume_a", "volume_b": count x the product
+    of the steps, "iou" = both / either, "precision" = both / a, "recall" = both / b}; 0 / 0 is 1.0 (nothing where nothing is to be)."""
+    c = np.asarray(host_counts.detach().cpu() if isinstance(host_counts, torch.Tensor) else host_counts).astype(np.int64).reshape(L.VOXEL_COUNTS)
+    cell = float(np.prod(np.asarray(step, np.float64).ravel()[:3]))
+    ratio = lambda num, den: float(c[num]) / float(c[den]) if c[den] else 1.0
+    return {"volume_a": float(c[L.VOXEL_A]) * cell, "volume_b": float(c[L.VOXEL_B]) * cell, "iou": ratio(L.VOXEL_BOTH, L.VOXEL_EITHER),
+            "precision": ratio(L.VOXEL_BOTH, L.VOXEL_A), "recall": ratio(L.VOXEL_BOTH, L.VOXEL_B)}

@@ -907,6 +907,93 @@ int gpnerf_mesh_adjacency(const int32_t* faces, int64_t n_faces, int64_t n_verti
 int gpnerf_mesh_smooth(const float* vertices, int64_t n_vertices, void* workspace, size_t workspace_bytes, int32_t iterations, double lam,
                        double mu, uint32_t flags, float* out_vertices, void* stream);
 
+/* ---- voxelising a mesh (gpnerf_voxelize.hip): the SOLID occupancy of a triangle mesh on a lattice, packed one bit per lattice point,
+ * the counts that give its volume, and the small operations on packed cubes that go with it (from a density cube, back to a float
+ * cube, the popcounts of two cubes for a volumetric IoU, containment of points).  It is the one direction mesh -> lattice beside
+ * marching cubes' lattice -> mesh: voxelising the marching-cubes mesh of a cube on that cube's own lattice gives back cube > iso.
+ * All entry points: kernel launches only, on the caller's stream; nothing allocated, nothing waited for; every launch sized from the
+ * arguments alone; the one data-dependent length (the large-face list's) stays on the device; every call captures into a HIP graph
+ * and replays with the same bits; the result is a function of the inputs alone and of no launch geometry, of no order of the faces
+ * and, under rule PARITY, of no orientation of the faces (integer atomics only -- XOR of a bit, add of +-1, integer sums).
+ * A mesh is vertices: device float [n_vertices][3] and faces: device int32 [n_faces][3], both counts 0 to 2^31 - 1 (a pointer may be
+ * NULL where its count is 0).  lattice: HOST double [6] = lo[3], step[3], finite, step > 0.  dims: HOST int32 [3] = (nx, ny, nz), each
+ * >= 1, product <= 2^28 (marching cubes' limit).  Lattice point (i, j, k) sits at lo + (i, j, k) * step: these are lattice POINTS --
+ * what gpnerf_density_lattice samples and marching cubes reads --, not cell centres.  The ray axis is z: the cube's contiguous axis
+ * and a standing body's long axis, so it has the fewest columns.  A COLUMN is the nz points of one (i, j).
+ *
+ * THE DEFINITION (gpnerf_mesh_voxelize)
+ *   - a vertex: the float32 point widened to float64, u_a = (p_a - lo_a) / step_a per axis (subtract, then divide).  It is USABLE iff
+ *     u_x, u_y, u_z are finite and |u_x| <= 2^16 and |u_y| <= 2^16.  X = int64(rint(4096 u_x)), Y = int64(rint(4096 u_y)) (rint: half to
+ *     even): 1/4096 of a lattice step; Z = u_z stays float64.  Column (i, j) is the point (4096 i, 4096 j).  Differences are at most
+ *     2^29 and products at most 2^58: the rasteriser's bounds;
+ *   - a face (a, b, c) is SKIPPED FOR A VERTEX when an index is outside [0, n_vertices) or a vertex is not usable; otherwise it is
+ *     SKIPPED FOR ITS AREA when A = (Xb - Xa)(Yc - Ya) - (Yb - Ya)(Xc - Xa) (int64, exact) is 0 -- a face that is vertical in projection
+ *     bounds no column, so it contributes nothing, correctly --; otherwise it is USED;
+ *   - ownership, int64, HALF-OPEN: with P the column, Ea, Eb, Ec exactly as gpnerf_mesh_rasterize writes them -- the edge vectors
+ *     (dx, dy) are c - b, a - c, b - a, and Ek = dx (Py - Qy) - dy (Px - Qx) with Q the edge's first vertex (b, c, a) --, s = sign(A): the
+ *     face OWNS the column iff for each of the three edges either s Ek > 0, or Ek == 0 and (s dy < 0, or s dy == 0 and s dx > 0).  That
+ *     is: a column on an edge belongs to the face it enters when nudged by (eps, eps^2).  Two faces that share an edge never both own
+ *     a column on it unless they fold over each other there (where 0 or 2 is right), and of a fan of faces around a vertex exactly
+ *     one owns a column on the vertex;
+ *   - the crossing of an owned column, float64, unfused: wk = double(Ek) / double(A), z = (wa Za + wb Zb) + wc Zc,
+ *     kc = clamp(ceil(z), 0, nz): the number of the column's lattice points strictly below the crossing.  A column through a vertex
+ *     has two Ek == 0 and receives that vertex's Z exactly.  Nothing is clipped in z: faces above or below the lattice count;
+ *   - the occupancy of point (i, j, k).  Rule GPNERF_VOXEL_PARITY: the number of crossings of its column with kc > k is odd.  Rule
+ *     GPNERF_VOXEL_NONZERO: the sum of s over those crossings is not 0 -- overlapping closed parts unite instead of cancelling, which
+ *     scans made of separate parts need.  A column is OPEN when the same test over ALL its crossings (kc >= 0) is true: the surface
+ *     leaks there (a closed surface crosses every column an even number of times, with signs that cancel).
+ * Outputs.  bits: device uint32 [nx][ny][nzw], nzw = ceil(nz / 32): point k is bit (k & 31) of word (k >> 5); bits at or above nz are
+ * zero.  stats: device int64 [GPNERF_VOXEL_STATS], set by the call: faces USED, SKIPPED_VERTEX, SKIPPED_AREA (their sum is n_faces),
+ * CROSSINGS (the (face, column) pairs owned), OPEN_COLUMNS, OCCUPIED (points; times the product of the steps it is the volume).
+ * Launches: a clear; one lane per face, which walks the face's clipped column box -- the columns in [min X, max X] x [min Y, max Y]
+ * and in the lattice -- unless that box holds more than 256 columns (the rasteriser's threshold for its pixels, taken over untuned):
+ * such a face is appended to a list in the workspace (one counter add per wavefront); a launch of fixed grid that reads the list's
+ * length on the device and gives each listed face a wavefront, 64 columns per step; a resolve.  A crossing does ONE no-return atomic
+ * at place kc of its column's TOGGLE ROW of nz + 1 places in the workspace -- PARITY: the XOR of one bit, NONZERO: an int32 add of s --
+ * and never flips the points below it (nz / 32 atomics per crossing); the resolve takes the suffix XOR / suffix sum down each column,
+ * writes bits and counts OCCUPIED and OPEN_COLUMNS with one add per wavefront.
+ * workspace: gpnerf_mesh_voxelize_workspace_bytes(n_faces, dims, rule) bytes (host arithmetic only; 0 for what the call refuses) =
+ * 256 + align256(4 nx ny T) + align256(4 n_faces), T = nz / 32 + 1 (integer division) under PARITY and nz + 1 under NONZERO, align256
+ * rounding up to a multiple of 256: the header, the toggle rows, the list at its worst.  It carries nothing from call to call.
+ * GPNERF_E_ARG, before anything is launched: null lattice, dims, workspace, bits or stats; null vertices with n_vertices > 0 or faces
+ * with n_faces > 0; a count that is negative or >= 2^31; a dims entry < 1 or a product > 2^28; a lattice entry that is not finite or
+ * a step that is not > 0; a rule that is neither; a workspace under the formula.
+ *
+ * Packed cubes (bits as above; dims as above; GPNERF_E_ARG for a null pointer or bad dims):
+ * gpnerf_voxel_from_cube(cube, dims, iso, bits, stream): cube: device float [nx][ny][nz]; bits = cube > iso (false for a NaN), packed.
+ * gpnerf_voxel_unpack(bits, dims, cube, stream): cube: device float [nx][ny][nz], 1.0f where the bit is set and 0.0f elsewhere, so that
+ * a voxelised scan goes through gpnerf_mesh_count / _emit at iso 0.5 and through gpnerf_cube_clean.
+ * gpnerf_voxel_stats(a, b, dims, out, stream): out: device int64 [GPNERF_VOXEL_COUNTS], set by the call: the set bits of A, of B, of
+ * BOTH, of EITHER, by popcount over the words (two launches: a zero, a count with one add per wavefront and counter).  b may be NULL:
+ * B = BOTH = 0 and EITHER = A.  IoU = BOTH / EITHER, precision = BOTH / A, recall = BOTH / B.
+ * gpnerf_voxel_contains(bits, dims, lattice, points, n, out, stream): points: device float [n][3]; out: device uint8 [n].  A point maps
+ * to the index rint((p_a - lo_a) / step_a) per axis (float64, half to even): the nearest lattice point; out is 1 iff the three indices
+ * are inside dims and that point's bit is set; a coordinate that is not finite or an index outside gives 0.  0 <= n < 2^31; points
+ * and out may be NULL where n is 0 (nothing is launched). */
+#define GPNERF_VOXEL_PARITY 0
+#define GPNERF_VOXEL_NONZERO 1
+#define GPNERF_VOXEL_USED 0
+#define GPNERF_VOXEL_SKIPPED_VERTEX 1
+#define GPNERF_VOXEL_SKIPPED_AREA 2
+#define GPNERF_VOXEL_CROSSINGS 3
+#define GPNERF_VOXEL_OPEN_COLUMNS 4
+#define GPNERF_VOXEL_OCCUPIED 5
+#define GPNERF_VOXEL_STATS 6
+#define GPNERF_VOXEL_A 0
+#define GPNERF_VOXEL_B 1
+#define GPNERF_VOXEL_BOTH 2
+#define GPNERF_VOXEL_EITHER 3
+#define GPNERF_VOXEL_COUNTS 4
+size_t gpnerf_mesh_voxelize_workspace_bytes(int64_t n_faces, const int32_t* dims, int32_t rule);
+int gpnerf_mesh_voxelize(const float* vertices, int64_t n_vertices, const int32_t* faces, int64_t n_faces, const double* lattice,
+                         const int32_t* dims, int32_t rule, void* workspace, size_t workspace_bytes, uint32_t* bits, int64_t* stats,
+                         void* stream);
+int gpnerf_voxel_from_cube(const float* cube, const int32_t* dims, float iso, uint32_t* bits, void* stream);
+int gpnerf_voxel_unpack(const uint32_t* bits, const int32_t* dims, float* cube, void* stream);
+int gpnerf_voxel_stats(const uint32_t* a, const uint32_t* b, const int32_t* dims, int64_t* out, void* stream);
+int gpnerf_voxel_contains(const uint32_t* bits, const int32_t* dims, const double* lattice, const float* points, int64_t n, uint8_t* out,
+                          void* stream);
+
 /* ---- per-frame sparse convolution pyramid (gpnerf_volume.hip), replacing the external spconv v1.2.1 calls of
  * libs/nerfheads/networks/SparseConvNet.py:22-111 (SubMConv3d / SparseConv3d + BatchNorm1d + ReLU, .dense()).
  * A sparse tensor is: features [M][C] fp32, coords [M][3] int32 (d,h,w), and a dense int32 index grid [D][H][W]
