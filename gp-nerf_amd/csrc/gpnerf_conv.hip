@@ -32,6 +32,7 @@ typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 #define DEV __device__ __forceinline__
 #include "gpnerf_diag.h"       // the lab's hook points, empty in the product (csrc/nodiag/)
+#include "gpnerf_util.h"       // S_, launch_status
 
 constexpr int STEP_BYTES = 2048;     // one (chunk, output tile): 64 lanes x 8 halfs hi (1 KB) + the same for lo
 constexpr int PT = 2;                // 32-pixel tiles per wave
@@ -1211,9 +1212,6 @@ __global__ void __launch_bounds__(WAVES * 64) conv2d_exact_kernel(const ExactArg
     }
 }
 
-hipStream_t S_(void* s) { return reinterpret_cast<hipStream_t>(s); }
-int status() { return hipGetLastError() == hipSuccess ? GPNERF_OK : GPNERF_E_LAUNCH; }
-
 template <int KS, int STRIDE, bool NARROW>
 int launch_conv(const ConvArgs& a, int N, void* stream) {
     const int tiles = (a.Ho * a.Wo + WAVES * PT * 32 - 1) / (WAVES * PT * 32);
@@ -1228,12 +1226,12 @@ int launch_conv(const ConvArgs& a, int N, void* stream) {
         if (cot == 4) hipLaunchKernelGGL((conv2d_nhwc_kernel<KS, STRIDE, 4, NARROW, true>), grid, dim3(WAVES * 64), 0, S_(stream), a2);
         else if (cot == 2) hipLaunchKernelGGL((conv2d_nhwc_kernel<KS, STRIDE, 2, NARROW, true>), grid, dim3(WAVES * 64), 0, S_(stream), a2);
         else hipLaunchKernelGGL((conv2d_nhwc_kernel<KS, STRIDE, 1, NARROW, true>), grid, dim3(WAVES * 64), 0, S_(stream), a2);
-        return status();
+        return launch_status();
     }
     if (cot == 4) hipLaunchKernelGGL((conv2d_nhwc_kernel<KS, STRIDE, 4, NARROW>), grid, dim3(WAVES * 64), 0, S_(stream), a2);
     else if (cot == 2) hipLaunchKernelGGL((conv2d_nhwc_kernel<KS, STRIDE, 2, NARROW>), grid, dim3(WAVES * 64), 0, S_(stream), a2);
     else hipLaunchKernelGGL((conv2d_nhwc_kernel<KS, STRIDE, 1, NARROW>), grid, dim3(WAVES * 64), 0, S_(stream), a2);
-    return status();
+    return launch_status();
 }
 
 // rows per wave of the 3x3 kernel for an (Ho x Wo) output: images of at most sixteen 8-row tiles (64 x 64 and smaller) take 4-row tiles (threshold swept: 8: 1.165, 16: 1.147, 64: 1.203 ms per frame).
@@ -1259,7 +1257,7 @@ int launch_conv3x3_as(const ConvArgs& a, int N, int tiles, void* stream) {
     ConvArgs g = a;
     g.tile_h = tile_rows(RW); g.tile_w = TW;
     hipLaunchKernelGGL((conv3x3_s1_nhwc_kernel<COT, RW, STRIDE, KSPLIT, CAT, EXACT>), grid, dim3(WAVES * KSPLIT * 64), lds, S_(stream), g);
-    return status();
+    return launch_status();
 }
 
 int launch_conv3x3(const ConvArgs& a, int N, void* stream) {
@@ -1294,7 +1292,7 @@ int launch_stem_as(const ConvArgs& a, int N, void* stream) {
     ConvArgs g = a;
     g.tile_h = STEM_TH; g.tile_w = TW;
     hipLaunchKernelGGL((conv7x7_s2_stem_kernel<COT, EXACT>), grid, dim3(WAVES * 64), lds, S_(stream), g);
-    return status();
+    return launch_status();
 }
 int launch_stem(const ConvArgs& a, int N, void* stream) { return a.CT % 2 == 0 ? launch_stem_as<2>(a, N, stream) : launch_stem_as<1>(a, N, stream); }
 
@@ -1316,14 +1314,14 @@ int gpnerf_conv_pack_weight(const float* weight, int32_t cout, int32_t cin, int3
         const long total = (long)STEM_CHUNKS * CT * 512;
         hipLaunchKernelGGL(pack_stem_weight_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, S_(stream), weight, (int)cout, (int)cin, CT,
                            (int)exact, reinterpret_cast<uint16_t*>(packed));
-        return status();
+        return launch_status();
     }
     const int flat = cin < 8;
     const int CB = flat ? (ks * ks * cin + 15) / 16 : (cin + 15) / 16, CT = (cout + 31) / 32;
     const long total = (flat ? (long)CB : (long)ks * ks * CB) * CT * 512;
     hipLaunchKernelGGL(pack_conv_weight_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, S_(stream), weight, (int)cout,
                        (int)cin, (int)ks, CB, CT, flat, (int)exact, reinterpret_cast<uint16_t*>(packed));
-    return status();
+    return launch_status();
 }
 
 // workgroup tiles per image of a convolution's output (= rows per image of its `tile_stats`)
@@ -1406,7 +1404,7 @@ int gpnerf_conv2d_nhwc_exact(const float* x, int32_t n, int32_t h, int32_t w, in
     a.Ho = (h + 2 * pad - ks) / stride + 1; a.Wo = (w + 2 * pad - ks) / stride + 1;
     const int tiles = (a.Ho * a.Wo + WAVES * 32 - 1) / (WAVES * 32);
     hipLaunchKernelGGL(conv2d_exact_kernel, dim3((unsigned)tiles, (unsigned)n, (unsigned)((cout + 31) / 32)), dim3(WAVES * 64), 0, S_(stream), a);
-    return status();
+    return launch_status();
 }
 
 int64_t gpnerf_instance_norm_nhwc_scratch_bytes(int32_t n, int64_t hw, int32_t c) {
@@ -1430,7 +1428,7 @@ int gpnerf_instance_norm_act_nhwc(const float* x, const float* gamma, const floa
                        (int)c, nchunks, eps, table);
     hipLaunchKernelGGL(nhwc_norm_apply_kernel, dim3((unsigned)((elems + 255) / 256), (unsigned)n), dim3(256), 0, S_(stream), x,
                        (const float*)table, residual, (const float*)nullptr, (long)hw, (int)c, (int)act, out);
-    return status();
+    return launch_status();
 }
 
 int gpnerf_norm_apply_nhwc(const float* x, const float* table, const float* residual, const float* res_table, int32_t n, int64_t hw,
@@ -1440,7 +1438,7 @@ int gpnerf_norm_apply_nhwc(const float* x, const float* table, const float* resi
     const long elems = (long)hw * (c >> 2);
     hipLaunchKernelGGL(nhwc_norm_apply_kernel, dim3((unsigned)((elems + 255) / 256), (unsigned)n), dim3(256), 0, S_(stream), x, table,
                        residual, res_table, (long)hw, (int)c, (int)act, out);
-    return status();
+    return launch_status();
 }
 
 int gpnerf_upsample2x_nhwc(const float* x, int32_t n, int32_t h, int32_t w, int32_t c, float* out, void* stream) {
@@ -1449,7 +1447,7 @@ int gpnerf_upsample2x_nhwc(const float* x, int32_t n, int32_t h, int32_t w, int3
     const long total = (long)n * h * w * 4 * (c >> 2);
     hipLaunchKernelGGL(upsample2x_nhwc_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, S_(stream), x, (int)n, (int)h, (int)w,
                        (int)c, out);
-    return status();
+    return launch_status();
 }
 
 }  // extern "C"

@@ -17,6 +17,7 @@
 namespace {
 
 #include "gpnerf_diag.h"       // the lab's hook points, empty in the product (csrc/nodiag/)
+#include "gpnerf_util.h"       // S_, launch_status; wave_sum
 
 constexpr int HULL_MAX_VIEWS = 8, HULL_THREADS = 256;
 constexpr int64_t HULL_MAX_POINTS = (int64_t)1 << 28;
@@ -89,13 +90,10 @@ __global__ void __launch_bounds__(HULL_THREADS) visual_hull_kernel(const HullArg
         else for (int b = 0; b < run; ++b) a.inside[flat0 + b] = (uint8_t)(word >> (8 * b));
     }
     if (a.n_inside) {
-        for (int d = 32; d > 0; d >>= 1) nonzero += __shfl_xor(nonzero, d);
+        nonzero = wave_sum(nonzero);
         if ((threadIdx.x & 63) == 0 && nonzero) atomicAdd(a.n_inside, (unsigned long long)nonzero);
     }
 }
-
-hipStream_t S_(void* s) { return reinterpret_cast<hipStream_t>(s); }
-int launch_status() { return hipGetLastError() == hipSuccess ? GPNERF_OK : GPNERF_E_LAUNCH; }
 
 }  // namespace
 

@@ -37,6 +37,7 @@ constexpr float LOG2E = 1.44269504088896340736f;
 // this resolves to csrc/nodiag/gpnerf_diag.h on the product's include path; csrc/diag/Makefile builds the diagnostic libraries
 // with csrc/diag/gpnerf_diag.h instead (never loaded by the product).
 #include "gpnerf_diag.h"
+#include "gpnerf_util.h"       // align256, S_, launch_status
 
 DEV float fast_exp(float x) { return __builtin_amdgcn_exp2f(x * LOG2E); }       // v_exp_f32
 // nn.ELU(alpha=1) = x > 0 ? x : exp(x) - 1.  exp(x) - 1 >= x everywhere and has x's sign, so the select is the median
@@ -3397,7 +3398,6 @@ int pack_head_fp32(const HeadOrder& o, const GpnerfHeadParams* p, float* blob) {
 // workgroup and, when the caller lends a workspace, how many waves share the samples of one tile (split), minimising
 // rounds x step time x samples per unit.
 constexpr int GPNERF_MAX_SPLIT = 8;     // waves that may share one tile's samples
-size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 // the split geometry's partial composites: 16 floats per ray and segment
 size_t part_bytes(int64_t n_rays, int split) { return (size_t)n_rays * split * 16 * sizeof(float); }
 struct Geometry { int waves, split; };
@@ -3720,7 +3720,6 @@ bool launch_render(int sel, Loop loop, Colour colour, dim3 grid, dim3 block, hip
     return true;
 }
 
-hipStream_t S_(void* s) { return reinterpret_cast<hipStream_t>(s); }
 // The counters a launch sequence starts from (tile queues, list lengths, the guard's flags) are zeroed by a kernel of the library's
 // own, not by hipMemsetAsync: captured into a HIP graph, the memset node was not reliably ordered before the kernel node that
 // follows it (replays after the first found the previous replay's counters -- exhausted queues -- and rendered nothing;
@@ -3788,8 +3787,6 @@ int device_ready(int* cus) {
     if (cus) *cus = d.cus;
     return GPNERF_OK;
 }
-
-int launch_status() { return hipGetLastError() == hipSuccess ? GPNERF_OK : GPNERF_E_LAUNCH; }
 
 // GpnerfFrame -> kernel argument; need_vol / need_img say which tensors the launch will touch
 bool to_framek(const GpnerfFrame* f, FrameK& k, bool need_vol, bool need_img) {

@@ -22,6 +22,7 @@
 namespace {
 
 #include "gpnerf_diag.h"       // the lab's hook points, empty in the product (csrc/nodiag/)
+#include "gpnerf_util.h"       // align256, S_, launch_status
 
 constexpr int MC_THREADS = 256, MC_PER_THREAD = 4, MC_BLOCK = MC_THREADS * MC_PER_THREAD;    // points per scan block
 constexpr int MC_MAX_TRIS = 5;
@@ -466,7 +467,8 @@ __global__ void __launch_bounds__(256) cc_flatten_kernel(const long n, int* pare
     }
 }
 
-__device__ __forceinline__ long wave_sum(long v) {
+// (not gpnerf_util.h's wave_sum: a shuffle-down reduction, whose sum arrives in the wavefront's first lane only)
+__device__ __forceinline__ long wave_sum_lane0(long v) {
 #pragma unroll
     for (int d = 32; d > 0; d >>= 1) v += __shfl_down(v, d);
     return v;
@@ -484,7 +486,7 @@ __global__ void __launch_bounds__(256) cc_select_kernel(const long n, const int*
     if (!__any(root)) return;
     const long size = root ? (long)(count[i] & CC_COUNT) : 0;
     const bool kept = root && (mode == KEEP_ALL || (mode == KEEP_MIN && size >= min_points));
-    const long roots = wave_sum(root ? 1 : 0), points = wave_sum(size), kroots = wave_sum(kept ? 1 : 0), kpoints = wave_sum(kept ? size : 0);
+    const long roots = wave_sum_lane0(root ? 1 : 0), points = wave_sum_lane0(size), kroots = wave_sum_lane0(kept ? 1 : 0), kpoints = wave_sum_lane0(kept ? size : 0);
     unsigned long long key = root ? ((unsigned long long)size << 32) | (unsigned)~(unsigned)i : 0ull;
     if (mode == KEEP_LARGEST) {
 #pragma unroll
@@ -527,7 +529,7 @@ __global__ void __launch_bounds__(256) cc_apply_fill_kernel(const long n, const 
     const bool fill = r >= 0 && !(count[r] & CC_BOUNDARY);
     if (!__any(fill)) return;
     if (fill) out[i] = 1.0f;
-    const long cav = wave_sum(fill && r == (int)i ? 1 : 0), pts = wave_sum(fill ? 1 : 0);
+    const long cav = wave_sum_lane0(fill && r == (int)i ? 1 : 0), pts = wave_sum_lane0(fill ? 1 : 0);
     if (threadIdx.x % 64 == 0) {
         if (cav) atomicAdd((unsigned long long*)&stats[4], (unsigned long long)cav);
         atomicAdd((unsigned long long*)&stats[5], (unsigned long long)pts);
@@ -584,7 +586,6 @@ bool grid_of(const int32_t* dims, float iso, Grid& g) {
     return true;
 }
 
-constexpr size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 struct WsLayout { size_t loc, bsum, boff, total; long nb; };
 WsLayout layout_of(const Grid& g) {
     WsLayout w;
@@ -605,9 +606,6 @@ CleanLayout clean_layout_of(const Grid& g) {
     w.total = w.best + 256;
     return w;
 }
-
-hipStream_t S_(void* s) { return reinterpret_cast<hipStream_t>(s); }
-int launch_status() { return hipGetLastError() == hipSuccess ? GPNERF_OK : GPNERF_E_LAUNCH; }
 
 }  // namespace
 

@@ -22,6 +22,7 @@
 namespace {
 
 #include "gpnerf_diag.h"       // the lab's hook points, empty in the product (csrc/nodiag/)
+#include "gpnerf_util.h"       // align256, S_, launch_status, blocks_for
 
 constexpr int THREADS = 256;
 constexpr int BOX_BLOCKS_MAX = 1024;                     // partial boxes of the reduction
@@ -32,8 +33,6 @@ constexpr int64_t MAX_CELL_CAP = (int64_t)1 << 24, MAX_ENTRY_CAP = (int64_t)1 <<
 constexpr int32_t GRID_MAGIC = 0x47524431;               // "GRD1"
 constexpr int SAMPLE_CHUNK = 1024;                       // faces per block of the area scan (4 per thread)
 constexpr int TILE = 256;                                // faces per LDS tile of the brute-force form
-
-constexpr size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 struct GridLayout { size_t hdr, part, start, cursor, entries, tmp_face, tmp_cell, total; };
 
@@ -622,10 +621,6 @@ __global__ __launch_bounds__(STAT_THREADS) void distance_stats_kernel(const floa
     for (int k = 0; k < GPNERF_DIST_MAX_THRESHOLDS; ++k)
         out[GPNERF_DIST_WITHIN + k] = (k < th.n && finite + inf > 0.0) ? (double)s_cnt[3 + k][0] / (finite + inf) : nan;
 }
-
-hipStream_t S_(void* s) { return reinterpret_cast<hipStream_t>(s); }
-int launch_status() { return hipGetLastError() == hipSuccess ? GPNERF_OK : GPNERF_E_LAUNCH; }
-unsigned blocks_for(int64_t n, int per) { return (unsigned)((n + per - 1) / per); }
 
 }  // namespace
 

@@ -24,6 +24,7 @@
 namespace {
 
 #include "gpnerf_diag.h"       // the lab's hook points, empty in the product (csrc/nodiag/)
+#include "gpnerf_util.h"       // align256, S_, launch_status, blocks_for; wave_count
 #include "gpnerf_scan.h"       // the three-launch integer scan (shared with gpnerf_simplify.hip)
 
 struct TopoScan;               // names this file's instances of the scan kernels
@@ -41,8 +42,6 @@ typedef unsigned long long u64;
 enum { H_MAGIC, H_NV, H_NF, H_DONE, H_HALFEDGES, H_ENTRIES, H_BOUNDARY, H_NONMANIFOLD, H_INCONSISTENT,
        H_VREF, H_VBOUNDARY, H_MAX_VALENCE, H_WORDS };
 static_assert(H_WORDS <= 32, "the header's words");
-
-constexpr size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 // the formula of include/gpnerf_hip.h.  Everything gpnerf_mesh_smooth touches except the neighbours sits in front of the regions
 // sized by n_faces, and the neighbours come first among those: smooth, which is not told n_faces, finds its regions from n_vertices.
@@ -96,12 +95,6 @@ __host__ inline Ws ws_of(void* workspace, const Layout& l) {
 }
 
 bool sizes_ok(int64_t nv, int64_t nf) { return nv >= 0 && nf >= 0 && nv <= MAX_VERTICES && nf <= MAX_FACES; }
-
-// one add per wavefront: the number of its lanes for which pred holds.  Every lane of the wavefront must reach the call.
-DEV void wave_count(bool pred, long long* counter) {
-    const u64 m = __ballot(pred);
-    if (m && (threadIdx.x & 63) == (unsigned)(__ffsll((long long)m) - 1)) atomicAdd(reinterpret_cast<u64*>(counter), (u64)__popcll(m));
-}
 
 // a face's corners when it is usable: indices in [0, nv), pairwise distinct
 DEV bool usable_face(const int32_t* __restrict__ faces, long f, long nv, int32_t* c) {
@@ -322,10 +315,6 @@ __global__ __launch_bounds__(THREADS) void copy_kernel(const float* src, float* 
     const long i = (long)blockIdx.x * THREADS + threadIdx.x;
     if (i < n && adjacency_ok(w, nv)) dst[i] = src[i];
 }
-
-hipStream_t S_(void* s) { return reinterpret_cast<hipStream_t>(s); }
-int launch_status() { return hipGetLastError() == hipSuccess ? GPNERF_OK : GPNERF_E_LAUNCH; }
-unsigned blocks_for(int64_t n, int per) { return (unsigned)((n + per - 1) / per); }
 
 }  // namespace
 

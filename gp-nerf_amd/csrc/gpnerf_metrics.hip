@@ -21,6 +21,7 @@
 namespace {
 
 #include "gpnerf_diag.h"       // the lab's hook points, empty in the product (csrc/nodiag/)
+#include "gpnerf_util.h"       // align256, S_, launch_status
 
 constexpr int WIN = 7;                                   // skimage's default window
 constexpr int TILE_W = 32, TILE_H = 8;                   // windows per tile
@@ -29,8 +30,6 @@ constexpr int THREADS = TILE_W * TILE_H;                 // 256: one window per 
 constexpr int ST_OK = 0, ST_COUNT = 1, ST_EMPTY = 2, ST_SMALL = 3;
 // the header metrics_scan_kernel leaves for the two kernels behind it
 enum { HDR_X, HDR_Y, HDR_W, HDR_H, HDR_POP, HDR_STATUS, HDR_INTS = 8 };
-
-constexpr size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 struct Layout {
     int H, W, nblk, gtx, gty;                            // 64-pixel words per row; the grid of window tiles
@@ -245,9 +244,6 @@ __global__ __launch_bounds__(THREADS) void metrics_finish_kernel(int H, int gtx,
         out[GPNERF_METRICS_STATUS] = (double)status;
     }
 }
-
-hipStream_t S_(void* s) { return reinterpret_cast<hipStream_t>(s); }
-int launch_status() { return hipGetLastError() == hipSuccess ? GPNERF_OK : GPNERF_E_LAUNCH; }
 
 }  // namespace
 

@@ -11,11 +11,12 @@
 //     what the list's reader does with a pair is again a minimum per pixel;
 //   - the statistics are integer sums.
 //
-// Two tiers.  A body mesh at the project's lattice projects to triangles of about a pixel, so the first kernel gives every
-// (face, view) pair ONE lane, which projects the three vertices in float64, sets up the int64 edge functions and walks the face's
-// clipped pixel box with three additions per pixel.  A pair whose box holds more than LARGE_BOX pixels would hold its wavefront's
-// other 63 lanes up: it is appended to the list instead (one counter add per wavefront), and a second launch of fixed grid gives each
-// listed pair a whole wavefront, 64 pixels of the box per step.  The cameras travel in the kernel argument.
+// The two-tier walk of gpnerf_tri2d.h over a view's pixels, the vertices snapped to 1/256 pixel.  A body mesh at the project's
+// lattice projects to triangles of about a pixel, so the first kernel gives every (face, view) pair ONE lane, which projects the
+// three vertices in float64 and walks the face's clipped pixel box, i inside (a row's keys are contiguous in i); the pairs of more
+// than LARGE_BOX pixels go through the list to the second kernel.  What is the rasteriser's own: the projection, the inclusive edge
+// rule (covers), the perspective-correct depth and the key a covered pixel takes the minimum of.  The cameras travel in the kernel
+// argument.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -25,16 +26,18 @@
 namespace {
 
 #include "gpnerf_diag.h"       // the lab's hook points, empty in the product (csrc/nodiag/)
+#include "gpnerf_util.h"       // align256, S_, launch_status, blocks_for, sweep_blocks, mesh_ok; wave_count, wave_sum, stat_add
+#include "gpnerf_tri2d.h"      // Mesh, Snapped, Setup, Edges, setup_face, count_states, large_append, lane_walk, wave_walk; LARGE_*
 
 constexpr int MAX_VIEWS = 8, THREADS = 256, MAX_SIDE = 16384, MAX_ATTRS = 4;
-constexpr int LARGE_BOX = 256;                           // pixels in a clipped box above which a pair goes to the list (chosen, not tuned)
-constexpr int LARGE_BLOCKS = 1024;                       // the list reader's fixed grid: 4096 wavefronts
 constexpr int COUNT_BLOCKS_MAX = 256;                    // per view, of the silhouette count
-constexpr int64_t SNAP = 256;                            // sub-pixel units per pixel
+constexpr int SNAP_SHIFT = 8;                            // 256 sub-pixel units per pixel
 constexpr double GUARD = 1048576.0;                      // 2^20 pixels
 constexpr unsigned long long EMPTY = ~0ull;
 
-constexpr size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
+static_assert(GPNERF_RASTER_DRAWN == FACE_OK && GPNERF_RASTER_SKIPPED_VERTEX == FACE_BAD_VERTEX && GPNERF_RASTER_SKIPPED_AREA == FACE_NO_AREA,
+              "count_states adds a face under its state");
+using Setup8 = Setup<SNAP_SHIFT>;
 
 struct Layout { size_t hdr, keys, list, total; };
 
@@ -53,15 +56,6 @@ bool sizes_ok(int64_t n_faces, int n_views, int H, int W) {
 }
 
 struct Cams { double cam[MAX_VIEWS][21]; };              // K 3x3 row-major, RT 3x4 row-major: gpnerf_visual_hull's layout
-
-struct Mesh {
-    const float* vertices; const int32_t* faces;
-    long n_vertices, n_faces;
-};
-
-struct Snapped { int64_t X, Y; double z; };
-DEV int64_t lo_of(int64_t a, int64_t b) { return a < b ? a : b; }
-DEV int64_t hi_of(int64_t a, int64_t b) { return a > b ? a : b; }
 
 // one vertex in one view: the hull's projection (float64, multiply then add, unfused), the usable test, the snap to 1/256 pixel
 DEV bool project_vertex(const double* __restrict__ cam, const float* __restrict__ p, double z_near, Snapped& s) {
@@ -83,51 +77,20 @@ DEV bool project_vertex(const double* __restrict__ cam, const float* __restrict_
     return true;
 }
 
-enum FaceState { FACE_OK = 0, FACE_BAD_VERTEX = 1, FACE_NO_AREA = 2 };
-
-struct Setup {
-    Snapped a, b, c;
-    int64_t A;
-    int i0, i1, j0, j1;                                  // the clipped pixel box, inclusive; empty when i1 < i0 or j1 < j0
-};
-
-DEV FaceState setup_face(const Mesh& m, const double* __restrict__ cam, double z_near, long f, int H, int W, Setup& s) {
-    const int32_t ia = m.faces[3 * f], ib = m.faces[3 * f + 1], ic = m.faces[3 * f + 2];
-    if (ia < 0 || ib < 0 || ic < 0 || ia >= m.n_vertices || ib >= m.n_vertices || ic >= m.n_vertices) return FACE_BAD_VERTEX;
-    const bool ua = project_vertex(cam, m.vertices + 3 * (long)ia, z_near, s.a);
-    const bool ub = project_vertex(cam, m.vertices + 3 * (long)ib, z_near, s.b);
-    const bool uc = project_vertex(cam, m.vertices + 3 * (long)ic, z_near, s.c);
-    if (!(ua && ub && uc)) return FACE_BAD_VERTEX;
-    s.A = (s.b.X - s.a.X) * (s.c.Y - s.a.Y) - (s.b.Y - s.a.Y) * (s.c.X - s.a.X);
-    if (s.A == 0) return FACE_NO_AREA;
-    const int64_t x0 = lo_of(s.a.X, lo_of(s.b.X, s.c.X)), x1 = hi_of(s.a.X, hi_of(s.b.X, s.c.X));
-    const int64_t y0 = lo_of(s.a.Y, lo_of(s.b.Y, s.c.Y)), y1 = hi_of(s.a.Y, hi_of(s.b.Y, s.c.Y));
-    // pixel centres are the multiples of 256: ceil(x0 / 256) .. floor(x1 / 256), by arithmetic shifts, clipped to the image
-    s.i0 = (int)hi_of(0, (x0 + (SNAP - 1)) >> 8); s.i1 = (int)lo_of(W - 1, x1 >> 8);
-    s.j0 = (int)hi_of(0, (y0 + (SNAP - 1)) >> 8); s.j1 = (int)lo_of(H - 1, y1 >> 8);
-    return FACE_OK;
+// face f in the view of `cam`: its corners projected, A and the pixel box clipped to the image
+DEV FaceState raster_setup(const Mesh& m, const double* __restrict__ cam, double z_near, long f, int H, int W, Setup8& s) {
+    return setup_face(m, f, W, H, [&](const float* p, Snapped& v) { return project_vertex(cam, p, z_near, v); }, s);
 }
 
-// the three edge functions at pixel (i, j), each multiplied by sign(A): covered iff none is negative
-struct Edges { int64_t ea, eb, ec; };
-
-DEV Edges edges_at(const Setup& s, int i, int j) {
-    const int64_t px = SNAP * i, py = SNAP * j;
-    Edges e;
-    e.ea = (s.c.X - s.b.X) * (py - s.b.Y) - (s.c.Y - s.b.Y) * (px - s.b.X);
-    e.eb = (s.a.X - s.c.X) * (py - s.c.Y) - (s.a.Y - s.c.Y) * (px - s.c.X);
-    e.ec = (s.b.X - s.a.X) * (py - s.a.Y) - (s.b.Y - s.a.Y) * (px - s.a.X);
-    return e;
-}
-
-DEV bool covers(const Setup& s, const Edges& e) {
+// the edge functions each multiplied by sign(A): covered iff none is negative (a pixel exactly on an edge is covered)
+DEV bool covers(const Setup8& s, const Edges& e) {
     return s.A > 0 ? (e.ea >= 0 && e.eb >= 0 && e.ec >= 0) : (e.ea <= 0 && e.eb <= 0 && e.ec <= 0);
 }
 
 // perspective-correct depth terms of a covered pixel: wk = Ek / A, q = (wa / za + wb / zb) + wc / zc
 struct Persp { double ta, tb, tc, q; };                 // tk = wk / zk
 
-DEV Persp persp_of(const Setup& s, const Edges& e) {
+DEV Persp persp_of(const Setup8& s, const Edges& e) {
     const double A = (double)s.A;
     Persp p;
     p.ta = ((double)e.ea / A) / s.a.z;
@@ -137,12 +100,21 @@ DEV Persp persp_of(const Setup& s, const Edges& e) {
     return p;
 }
 
-DEV unsigned long long key_of(const Setup& s, const Edges& e, long f) {
+DEV unsigned long long key_of(const Setup8& s, const Edges& e, long f) {
     const float depth = (float)(1.0 / persp_of(s, e).q);
     return ((unsigned long long)__float_as_uint(depth) << 32) | (unsigned long long)(uint32_t)f;
 }
 
-DEV int wave_count(bool flag) { return __popcll(__ballot(flag)); }
+// what both walks do at a pixel of the face's box: a covered pixel takes the minimum of its key and the face's
+struct Draw {
+    const Setup8& s;
+    unsigned long long* view_keys;
+    int W;
+    long f;
+    DEV void operator()(int i, int j, const Edges e) const {
+        if (covers(s, e)) atomicMin(view_keys + (long)j * W + i, key_of(s, e, f));
+    }
+};
 
 // the keys, the list's length and the statistics start from a kernel of the library's own, not from memset nodes
 __global__ __launch_bounds__(THREADS) void raster_clear_kernel(unsigned long long* keys, long n_keys, unsigned long long* list_len,
@@ -162,52 +134,19 @@ __global__ __launch_bounds__(THREADS) void raster_faces_kernel(const Cams cams, 
     const int view = blockIdx.y;
     const long f = (long)blockIdx.x * THREADS + threadIdx.x;
     const bool live = f < m.n_faces;
-    Setup s;
+    Setup8 s;
     FaceState st = FACE_OK;
     long box = 0;
     if (live) {
-        st = setup_face(m, cams.cam[view], z_near, f, H, W, s);
-        if (st == FACE_OK && s.i1 >= s.i0 && s.j1 >= s.j0) box = (long)(s.i1 - s.i0 + 1) * (s.j1 - s.j0 + 1);
+        st = raster_setup(m, cams.cam[view], z_near, f, H, W, s);
+        if (st == FACE_OK) box = s.box();
     }
-    if (stats) {                                         // one add per wavefront and counter, and none for a zero
-        const int drawn = wave_count(live && st == FACE_OK), bad = wave_count(live && st == FACE_BAD_VERTEX);
-        const int flat = wave_count(live && st == FACE_NO_AREA);
-        if ((threadIdx.x & 63) == 0) {
-            if (drawn) atomicAdd(reinterpret_cast<unsigned long long*>(stats + 4 * view + GPNERF_RASTER_DRAWN), (unsigned long long)drawn);
-            if (bad) atomicAdd(reinterpret_cast<unsigned long long*>(stats + 4 * view + GPNERF_RASTER_SKIPPED_VERTEX), (unsigned long long)bad);
-            if (flat) atomicAdd(reinterpret_cast<unsigned long long*>(stats + 4 * view + GPNERF_RASTER_SKIPPED_AREA), (unsigned long long)flat);
-        }
-    }
-    // the large tier: the wavefront's pairs take consecutive places behind one add of their number
+    if (stats) count_states(live, st, stats + 4 * view);
     const bool large = box > LARGE_BOX;
-    const unsigned long long mask = __ballot(large);
-    if (mask) {
-        const int lane = threadIdx.x & 63;
-        const int leader = __ffsll((unsigned long long)mask) - 1;
-        unsigned long long base = 0;
-        if (lane == leader) base = atomicAdd(list_len, (unsigned long long)__popcll(mask));
-        base = __shfl(base, leader);
-        if (large) {
-            const unsigned long long at = base + (unsigned long long)__popcll(mask & ((1ull << lane) - 1ull));
-            if (at < (unsigned long long)m.n_faces * gridDim.y)        // (always: a pair is appended once)
-                list[at] = ((unsigned long long)view << 32) | (unsigned long long)(uint32_t)f;
-        }
-    }
+    const long long at = large_append(large, list_len, (unsigned long long)m.n_faces * gridDim.y);
+    if (at >= 0) list[at] = ((unsigned long long)view << 32) | (unsigned long long)(uint32_t)f;
     if (box == 0 || large) return;
-    unsigned long long* row_keys = keys + (long)view * H * W;
-    // the box, rows outside: the edge functions are linear, so a pixel to the right adds -256 dY and a row down adds 256 dX (int64: exact)
-    const Edges e0 = edges_at(s, s.i0, s.j0);
-    const int64_t ax = -SNAP * (s.c.Y - s.b.Y), bx = -SNAP * (s.a.Y - s.c.Y), cx = -SNAP * (s.b.Y - s.a.Y);
-    const int64_t ay = SNAP * (s.c.X - s.b.X), by = SNAP * (s.a.X - s.c.X), cy = SNAP * (s.b.X - s.a.X);
-    Edges row = e0;
-    for (int j = s.j0; j <= s.j1; ++j) {
-        Edges e = row;
-        for (int i = s.i0; i <= s.i1; ++i) {
-            if (covers(s, e)) atomicMin(row_keys + (long)j * W + i, key_of(s, e, f));
-            e.ea += ax; e.eb += bx; e.ec += cx;
-        }
-        row.ea += ay; row.eb += by; row.ec += cy;
-    }
+    lane_walk<INNER_I>(s, Draw{s, keys + (long)view * H * W, W, f});
 }
 
 // fixed grid: a wavefront per listed pair, 64 pixels of its box per step
@@ -224,16 +163,9 @@ __global__ __launch_bounds__(THREADS) void raster_large_kernel(const Cams cams, 
         const int view = (int)(pair >> 32);
         const long f = (long)(uint32_t)pair;
         if (view < 0 || view >= n_views || f >= m.n_faces) continue;      // (never: the list holds what the first kernel wrote)
-        Setup s;
-        if (setup_face(m, cams.cam[view], z_near, f, H, W, s) != FACE_OK || s.i1 < s.i0 || s.j1 < s.j0) continue;
-        const int bw = s.i1 - s.i0 + 1;
-        const long box = (long)bw * (s.j1 - s.j0 + 1);
-        unsigned long long* view_keys = keys + (long)view * H * W;
-        for (long k = lane; k < box; k += 64) {
-            const int j = s.j0 + (int)(k / bw), i = s.i0 + (int)(k % bw);
-            const Edges e = edges_at(s, i, j);
-            if (covers(s, e)) atomicMin(view_keys + (long)j * W + i, key_of(s, e, f));
-        }
+        Setup8 s;
+        if (raster_setup(m, cams.cam[view], z_near, f, H, W, s) != FACE_OK || s.i1 < s.i0 || s.j1 < s.j0) continue;
+        wave_walk<INNER_I>(s, lane, Draw{s, keys + (long)view * H * W, W, f});
     }
 }
 
@@ -251,7 +183,7 @@ __global__ __launch_bounds__(THREADS) void raster_resolve_kernel(const unsigned 
     }
     if (stats) {
         const int n = wave_count(covered);
-        if ((threadIdx.x & 63) == 0 && n) atomicAdd(reinterpret_cast<unsigned long long*>(stats + 4 * view + GPNERF_RASTER_PIXELS), (unsigned long long)n);
+        if ((threadIdx.x & 63) == 0) stat_add(stats + 4 * view, GPNERF_RASTER_PIXELS, n);
     }
 }
 
@@ -266,11 +198,11 @@ __global__ __launch_bounds__(THREADS) void raster_interpolate_kernel(const Cams 
     if (p >= hw) return;
     float* o = out + ((long)view * hw + p) * C;
     const int32_t f = face_id[(long)view * hw + p];
-    Setup s;
-    bool ok = f >= 0 && f < m.n_faces && setup_face(m, cams.cam[view], z_near, f, H, W, s) == FACE_OK;
+    Setup8 s;
+    bool ok = f >= 0 && f < m.n_faces && raster_setup(m, cams.cam[view], z_near, f, H, W, s) == FACE_OK;
     Edges e;
     if (ok) {
-        e = edges_at(s, (int)(p % W), (int)(p / W));
+        e = s.edges_at((int)(p % W), (int)(p / W));
         ok = covers(s, e);                               // a face id that is not this pixel's: background
     }
     if (!ok) {
@@ -306,25 +238,14 @@ __global__ __launch_bounds__(THREADS) void silhouette_count_kernel(const int32_t
         cnt[GPNERF_SILHOUETTE_EITHER] += cov || gt;
     }
     for (int k = 0; k < GPNERF_SILHOUETTE_COUNTS; ++k) {
-        int v = cnt[k];
-        for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d);
-        if ((threadIdx.x & 63) == 0 && v)
-            atomicAdd(reinterpret_cast<unsigned long long*>(out + GPNERF_SILHOUETTE_COUNTS * view + k), (unsigned long long)v);
+        const int v = wave_sum(cnt[k]);
+        if ((threadIdx.x & 63) == 0) stat_add(out + GPNERF_SILHOUETTE_COUNTS * view, k, v);
     }
 }
-
-hipStream_t S_(void* s) { return reinterpret_cast<hipStream_t>(s); }
-int launch_status() { return hipGetLastError() == hipSuccess ? GPNERF_OK : GPNERF_E_LAUNCH; }
-unsigned blocks_for(int64_t n, int per) { return (unsigned)((n + per - 1) / per); }
 
 void cams_of(const double* cams, int n_views, Cams& c) {
     for (int v = 0; v < MAX_VIEWS; ++v)
         for (int e = 0; e < 21; ++e) c.cam[v][e] = v < n_views ? cams[v * 21 + e] : 0.0;
-}
-
-bool mesh_ok(const float* vertices, int64_t n_vertices, const int32_t* faces, int64_t n_faces) {
-    return n_vertices >= 0 && n_vertices <= INT32_MAX && n_faces >= 0 && n_faces <= INT32_MAX && (vertices || n_vertices == 0) &&
-           (faces || n_faces == 0);
 }
 
 }  // namespace
@@ -352,8 +273,7 @@ int gpnerf_mesh_rasterize(const float* vertices, int64_t n_vertices, const int32
     const Mesh m = {vertices, faces, (long)n_vertices, (long)n_faces};
     const long hw = (long)H * W, n_keys = hw * n_views;
     long long* st = reinterpret_cast<long long*>(stats);
-    const unsigned clear_blocks = blocks_for(n_keys, THREADS) < 4096u ? blocks_for(n_keys, THREADS) : 4096u;
-    hipLaunchKernelGGL(raster_clear_kernel, dim3(clear_blocks), dim3(THREADS), 0, S_(stream), keys, n_keys, list_len, st, 4 * n_views);
+    hipLaunchKernelGGL(raster_clear_kernel, dim3(sweep_blocks(n_keys, THREADS)), dim3(THREADS), 0, S_(stream), keys, n_keys, list_len, st, 4 * n_views);
     if (n_faces > 0) {
         hipLaunchKernelGGL(raster_faces_kernel, dim3(blocks_for(n_faces, THREADS), (unsigned)n_views), dim3(THREADS), 0, S_(stream), c, m, z_near,
                            H, W, keys, list, list_len, st);
@@ -387,7 +307,7 @@ int gpnerf_silhouette_stats(const int32_t* face_id, const uint8_t* masks, int32_
     const long hw = (long)H * W;
     long long* o = reinterpret_cast<long long*>(out);
     hipLaunchKernelGGL(silhouette_zero_kernel, dim3(1), dim3(64), 0, S_(stream), o, GPNERF_SILHOUETTE_COUNTS * n_views);
-    const unsigned blocks = blocks_for(hw, THREADS) < (unsigned)COUNT_BLOCKS_MAX ? blocks_for(hw, THREADS) : (unsigned)COUNT_BLOCKS_MAX;
+    const unsigned blocks = sweep_blocks(hw, THREADS, COUNT_BLOCKS_MAX);
     hipLaunchKernelGGL(silhouette_count_kernel, dim3(blocks, (unsigned)n_views), dim3(THREADS), 0, S_(stream), face_id, masks, hw, o);
     return launch_status();
 }

@@ -21,6 +21,7 @@
 namespace {
 
 #include "gpnerf_diag.h"       // the lab's hook points, empty in the product (csrc/nodiag/)
+#include "gpnerf_util.h"       // align256, S_, launch_status, blocks_for; wave_count
 
 #include "gpnerf_scan.h"       // the three-launch integer scan (shared with gpnerf_meshtopo.hip): SCAN_CHUNK, scan_launch
 
@@ -37,8 +38,6 @@ typedef unsigned long long u64;
 enum { H_MAGIC, H_NV, H_NF, H_CLUSTERS, H_ENTRIES, H_OUT_V, H_OUT_F, H_INVALID, H_COLLAPSED, H_CANCELLED, H_DUPLICATE, H_CLAMPED,
        H_STATUS = GPNERF_SIMPLIFY_HDR_STATUS, H_CELLS, H_WORDS = H_CELLS + 3 };
 static_assert(H_CLAMPED + 1 == H_STATUS && H_WORDS <= 32, "the header's words");
-
-constexpr size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 struct Layout { size_t hdr, vcell, fclu, fkeep, cl_cell, cl_cnt, cl_fill, cl_start, cl_used, cl_pos, tmp, entries, cellmap, bsum, total;
                 int64_t scan_blocks; };
@@ -110,12 +109,6 @@ int64_t cells_of(int64_t nv, int64_t nf, const int32_t* cells) {
 }
 
 struct GridArgs { float lo[3]; float cell; int32_t cells[3]; };
-
-// one add per wavefront: the number of its lanes for which pred holds.  Every lane of the wavefront must reach the call.
-DEV void wave_count(bool pred, long long* counter) {
-    const u64 m = __ballot(pred);
-    if (m && (threadIdx.x & 63) == (unsigned)(__ffsll((long long)m) - 1)) atomicAdd(reinterpret_cast<u64*>(counter), (u64)__popcll(m));
-}
 
 // ---------------------------------------------------------------- clearing, cells, validity
 
@@ -392,10 +385,6 @@ __global__ __launch_bounds__(THREADS) void emit_map_kernel(Ws w, long nv, int32_
     const int32_t id = cell >= 0 ? w.cellmap[cell] : -1;
     vertex_map[v] = (id >= 0 && w.hdr[H_OUT_V] > 0) ? w.cl_used[id] : -1;          // (no output vertex: the cell map was never numbered)
 }
-
-hipStream_t S_(void* s) { return reinterpret_cast<hipStream_t>(s); }
-int launch_status() { return hipGetLastError() == hipSuccess ? GPNERF_OK : GPNERF_E_LAUNCH; }
-unsigned blocks_for(int64_t n, int per) { return (unsigned)((n + per - 1) / per); }
 
 // a scan over n items (n >= 1, host-known) with the workspace's block sums
 template <int MODE>

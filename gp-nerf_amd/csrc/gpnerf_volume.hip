@@ -18,6 +18,7 @@
 namespace {
 
 #include "gpnerf_diag.h"       // the lab's hook points, empty in the product (csrc/nodiag/)
+#include "gpnerf_util.h"       // S_, launch_status
 
 constexpr int KV = 27;
 
@@ -521,7 +522,6 @@ __global__ void dense_kernel(const float* __restrict__ feat, const int c, const 
     vol[cell * c + ch] = feat[(size_t)site * c + ch];
 }
 
-hipStream_t S_(void* s) { return reinterpret_cast<hipStream_t>(s); }
 // Buffers are (re)set by a kernel of the library's own rather than hipMemsetAsync: a memset node captured into a HIP graph was not
 // reliably ordered before the kernel node after it (gpnerf_kernels.hip, zero_words_kernel).  n_words 32-bit words of `value`.
 __global__ void __launch_bounds__(256) fill_words_kernel(unsigned* __restrict__ p, const long n_words, const unsigned value) {
@@ -537,7 +537,6 @@ bool fill_async(void* p, size_t bytes, unsigned value, void* stream) {     // by
                        static_cast<unsigned*>(p), n, value);
     return hipGetLastError() == hipSuccess;
 }
-int status() { return hipGetLastError() == hipSuccess ? GPNERF_OK : GPNERF_E_LAUNCH; }
 bool bad(const int32_t* dims) { return !dims || dims[0] < 1 || dims[1] < 1 || dims[2] < 1; }
 
 
@@ -701,7 +700,7 @@ int gpnerf_sparse_index(const int32_t* coords, const int32_t* m_dev, int32_t m_c
     if (!fill_async(grid, sizeof(int32_t) * (size_t)s.d * s.h * s.w, 0xFFFFFFFFu, stream)) return GPNERF_E_LAUNCH;
     if (m_cap == 0) return GPNERF_OK;
     hipLaunchKernelGGL(index_kernel, dim3((m_cap + 255) / 256), dim3(256), 0, S_(stream), coords, (const int*)m_dev, (int)m_cap, s, grid);
-    return status();
+    return launch_status();
 }
 
 int gpnerf_sparse_conv3(int32_t strided, const float* in, int32_t cin, const int32_t* in_grid, const int32_t* in_dims,
@@ -719,7 +718,7 @@ int gpnerf_sparse_conv3(int32_t strided, const float* in, int32_t cin, const int
     else
         hipLaunchKernelGGL(conv_kernel<false>, grid, block, 0, S_(stream), in, (int)cin, in_grid, s, out_coords, (const int*)m_dev,
                            (int)m_cap, weight, (int)cout, bn_scale, bn_shift, out);
-    return status();
+    return launch_status();
 }
 
 int64_t gpnerf_sparse_packed_weight_floats(int32_t cin) { return cin >= 8 && cin <= 32 && cin % 8 == 0 ? (int64_t)KV * (cin / 8) * 256 : 0; }
@@ -790,7 +789,7 @@ static int sparse_conv16(int32_t strided, const float* in, int32_t cin, const in
     if (strided) { if (cin == 32) GPNERF_LAUNCH16(true, 2); else GPNERF_LAUNCH16(true, 1); }
     else { if (cin == 32) GPNERF_LAUNCH16(false, 2); else GPNERF_LAUNCH16(false, 1); }
 #undef GPNERF_LAUNCH16
-    return status();
+    return launch_status();
 }
 
 int gpnerf_sparse_conv3_mfma(int32_t strided, const float* in, int32_t cin, const int32_t* in_grid, const int32_t* in_dims,
@@ -807,7 +806,7 @@ int gpnerf_sparse_conv3_mfma(int32_t strided, const float* in, int32_t cin, cons
     else
         hipLaunchKernelGGL(conv_mfma_kernel<false>, grid, block, 0, S_(stream), in, (int)cin, in_grid, s, out_coords, (const int*)m_dev,
                            (int)m_cap, packed_weight, (int)cout, bn_scale, bn_shift, out);
-    return status();
+    return launch_status();
 }
 
 int gpnerf_sparse_down_sites(const int32_t* in_coords, const int32_t* m_in_dev, int32_t m_in_cap, const int32_t* out_dims,
@@ -822,7 +821,7 @@ int gpnerf_sparse_down_sites(const int32_t* in_coords, const int32_t* m_in_dev, 
                        (int)m_in_cap, s, out_grid);
     hipLaunchKernelGGL(assign_kernel, dim3((unsigned)((cells + 256 * ASSIGN_PER - 1) / (256 * ASSIGN_PER))), dim3(256), 0, S_(stream), s, out_grid, (int*)m_out_dev,
                        (int)m_out_cap, out_coords);
-    return status();
+    return launch_status();
 }
 
 int gpnerf_sparse_merge_duplicates(float* feat, int32_t channels, const int32_t* coords, const int32_t* grid, int32_t m,
@@ -834,7 +833,7 @@ int gpnerf_sparse_merge_duplicates(float* feat, int32_t channels, const int32_t*
     hipLaunchKernelGGL(count_duplicates_kernel, dim3((m + 255) / 256), dim3(256), 0, S_(stream), coords, grid, (int)m, s, scratch);
     hipLaunchKernelGGL(merge_duplicates_kernel, dim3((m + 3) / 4), dim3(256), 0, S_(stream), feat, (int)channels, coords, grid,
                        (int)m, s, (const int32_t*)scratch);
-    return status();
+    return launch_status();
 }
 
 int gpnerf_zero_volume(float* vol_ndhwc, int32_t channels, const int32_t* dims, void* stream) {
@@ -855,7 +854,7 @@ int gpnerf_sparse_scatter_dense(const float* feat, int32_t channels, const int32
     if (m_cap == 0) return GPNERF_OK;
     hipLaunchKernelGGL(dense_kernel, dim3((m_cap + 7) / 8), dim3(256), 0, S_(stream), feat, (int)channels, coords, grid,
                        (const int*)m_dev, (int)m_cap, s, vol_ndhwc);
-    return status();
+    return launch_status();
 }
 
 int gpnerf_sparse_pyramid_plan(const GpnerfPyramid* p, void* stream) {
@@ -909,7 +908,7 @@ int gpnerf_sparse_pyramid_run(const GpnerfPyramid* p, const float* code, int32_t
             hipLaunchKernelGGL(subm_shared_rows_kernel, dim3((unsigned)((p->m0 + 7) / 8)), dim3(256), 0, S_(stream), in, (const float*)merged, (int)c.cin,
                                (const int32_t*)p->grid0, d0, p->coords0, (int)p->m0, (const int32_t*)p->dup_scratch, c.weight_raw, (int)c.cout,
                                c.bn_scale, c.bn_shift, out);
-        return status();
+        return launch_status();
     };
     float* cur = p->feat_a;
     float* other = p->feat_b;
@@ -966,7 +965,7 @@ int gpnerf_vertex_attention(const float* q, const float* kv, const float* wq, co
         else if (views == 2) hipLaunchKernelGGL(vertex_attention_mfma_kernel<2>, grid, block, 0, st, q, kv, wq, wk, wv, wfc, (int)n, (int)n_head, out);
         else if (views == 3) hipLaunchKernelGGL(vertex_attention_mfma_kernel<3>, grid, block, 0, st, q, kv, wq, wk, wv, wfc, (int)n, (int)n_head, out);
         else hipLaunchKernelGGL(vertex_attention_mfma_kernel<4>, grid, block, 0, st, q, kv, wq, wk, wv, wfc, (int)n, (int)n_head, out);
-        return hipGetLastError() == hipSuccess ? GPNERF_OK : GPNERF_E_LAUNCH;
+        return launch_status();
     }
     const int blocks = n < 2048 ? (n + 3) / 4 : 512;
     if (d_model <= 32 && kv_dim <= 32)
@@ -975,7 +974,7 @@ int gpnerf_vertex_attention(const float* q, const float* kv, const float* wq, co
     else
         hipLaunchKernelGGL(vertex_attention_kernel<64>, dim3((unsigned)blocks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), q,
                            kv, wq, wk, wv, wfc, (int)n, (int)d_model, (int)kv_dim, (int)n_head, (int)views, out);
-    return hipGetLastError() == hipSuccess ? GPNERF_OK : GPNERF_E_LAUNCH;
+    return launch_status();
 }
 
 }  // extern "C"

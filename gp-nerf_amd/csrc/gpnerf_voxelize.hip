@@ -14,11 +14,12 @@
 // A crossing never flips the column's prefix of points below it (nz / 32 atomics per crossing): the resolve pass takes the suffix
 // XOR / suffix sum of the toggle row once per column.
 //
-// Two tiers, the rasteriser's (gpnerf_raster.hip): the ray axis is z, so a face's work is the columns (i, j) its projection owns.  The
-// first kernel gives every face ONE lane, which maps the three vertices to lattice units in float64, sets up the int64 edge functions
-// and walks the face's clipped column box with three additions per column.  A face whose box holds more than LARGE_BOX columns would
-// hold its wavefront's other 63 lanes up: it is appended to the list instead (one counter add per wavefront), and a second launch of
-// fixed grid gives each listed face a whole wavefront, 64 columns of the box per step.
+// The two-tier walk of gpnerf_tri2d.h over the lattice's columns, the vertices snapped to 1/4096 step: the ray axis is z, so a
+// face's work is the columns (i, j) its projection owns.  The first kernel gives every face ONE lane, which maps the three vertices
+// to lattice units in float64 and walks the face's clipped column box, j inside (a column's toggles follow those of the column
+// before it in j); the faces of more than LARGE_BOX columns go through the list to the second kernel.  What is the voxeliser's own:
+// the lattice mapping, the (eps, eps^2) rule that gives a column exactly on an edge to ONE face (vox_owns), the crossing's height
+// and the toggle it makes.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -28,18 +29,17 @@
 namespace {
 
 #include "gpnerf_diag.h"       // the lab's hook points, empty in the product (csrc/nodiag/)
+#include "gpnerf_util.h"       // align256, S_, launch_status, blocks_for, sweep_blocks, mesh_ok; wave_sum, stat_add
+#include "gpnerf_tri2d.h"      // Mesh, Snapped, Setup, Edges, setup_face, count_states, large_append, lane_walk, wave_walk; LARGE_*
 
 constexpr int THREADS = 256;
-constexpr int LARGE_BOX = 256;                           // columns in a clipped box above which a face goes to the list: the rasteriser's
-                                                         // choice for its pixels, taken over as it is (chosen, not tuned)
-constexpr int LARGE_BLOCKS = 1024;                       // the list reader's fixed grid: 4096 wavefronts
-constexpr int SWEEP_BLOCKS_MAX = 4096;                   // of the grid-stride kernels (clear, resolve, pack, unpack, popcount)
-constexpr int64_t SNAP = 4096;                           // sub-column units per lattice step
-constexpr int SNAP_SHIFT = 12;
+constexpr int COUNT_BLOCKS_MAX = 256;                    // of the popcount of two cubes
+constexpr int SNAP_SHIFT = 12;                           // 4096 sub-column units per lattice step
 constexpr double GUARD = 65536.0;                        // 2^16 lattice steps
 constexpr int64_t MAX_POINTS = (int64_t)1 << 28;         // marching cubes' limit
 
-constexpr size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
+static_assert(GPNERF_VOXEL_USED == FACE_OK && GPNERF_VOXEL_SKIPPED_VERTEX == FACE_BAD_VERTEX && GPNERF_VOXEL_SKIPPED_AREA == FACE_NO_AREA,
+              "count_states adds a face under its state");
 
 struct Lattice {
     double lo[3], step[3];
@@ -86,17 +86,8 @@ Lattice lattice_of(const double* lattice, const int32_t* dims) {
     return g;
 }
 
-struct VoxMesh {
-    const float* vertices; const int32_t* faces;
-    long n_vertices, n_faces;
-};
-
-struct VoxVertex { int64_t X, Y; double Z; };
-DEV int64_t vox_lo(int64_t a, int64_t b) { return a < b ? a : b; }
-DEV int64_t vox_hi(int64_t a, int64_t b) { return a > b ? a : b; }
-
 // one vertex in lattice units: float64, subtract then divide; the usable test; the snap of x and y to 1/4096 step
-DEV bool vox_vertex(const Lattice& g, const float* __restrict__ p, VoxVertex& s) {
+DEV bool vox_vertex(const Lattice& g, const float* __restrict__ p, Snapped& s) {
     const double ux = ((double)p[0] - g.lo[0]) / g.step[0];
     const double uy = ((double)p[1] - g.lo[1]) / g.step[1];
     const double uz = ((double)p[2] - g.lo[2]) / g.step[2];
@@ -104,19 +95,9 @@ DEV bool vox_vertex(const Lattice& g, const float* __restrict__ p, VoxVertex& s)
     if (!(fabs(ux) <= GUARD) || !(fabs(uy) <= GUARD) || !(fabs(uz) < (double)INFINITY)) return false;
     s.X = (int64_t)rint(4096.0 * ux);
     s.Y = (int64_t)rint(4096.0 * uy);
-    s.Z = uz;
+    s.z = uz;
     return true;
 }
-
-enum VoxFaceState { VOX_FACE_OK = 0, VOX_FACE_BAD_VERTEX = 1, VOX_FACE_NO_AREA = 2 };
-
-struct VoxSetup {
-    VoxVertex a, b, c;
-    int64_t A;
-    int sgn;                                             // sign(A)
-    bool tie_a, tie_b, tie_c;                            // whether a column exactly ON the edge belongs to this face
-    int i0, i1, j0, j1;                                  // the clipped column box, inclusive; empty when i1 < i0 or j1 < j0
-};
 
 // a column on an edge with vector (dx, dy) belongs to the face it enters when nudged by (eps, eps^2): E changes by dx eps^2 - dy eps
 DEV bool vox_tie(int sgn, int64_t dx, int64_t dy) {
@@ -124,49 +105,37 @@ DEV bool vox_tie(int sgn, int64_t dx, int64_t dy) {
     return sy < 0 || (sy == 0 && sx > 0);
 }
 
-DEV VoxFaceState vox_setup(const VoxMesh& m, const Lattice& g, long f, VoxSetup& s) {
-    const int32_t ia = m.faces[3 * f], ib = m.faces[3 * f + 1], ic = m.faces[3 * f + 2];
-    if (ia < 0 || ib < 0 || ic < 0 || ia >= m.n_vertices || ib >= m.n_vertices || ic >= m.n_vertices) return VOX_FACE_BAD_VERTEX;
-    const bool ua = vox_vertex(g, m.vertices + 3 * (long)ia, s.a);
-    const bool ub = vox_vertex(g, m.vertices + 3 * (long)ib, s.b);
-    const bool uc = vox_vertex(g, m.vertices + 3 * (long)ic, s.c);
-    if (!(ua && ub && uc)) return VOX_FACE_BAD_VERTEX;
-    s.A = (s.b.X - s.a.X) * (s.c.Y - s.a.Y) - (s.b.Y - s.a.Y) * (s.c.X - s.a.X);
-    if (s.A == 0) return VOX_FACE_NO_AREA;
-    s.sgn = s.A > 0 ? 1 : -1;
-    s.tie_a = vox_tie(s.sgn, s.c.X - s.b.X, s.c.Y - s.b.Y);
-    s.tie_b = vox_tie(s.sgn, s.a.X - s.c.X, s.a.Y - s.c.Y);
-    s.tie_c = vox_tie(s.sgn, s.b.X - s.a.X, s.b.Y - s.a.Y);
-    const int64_t x0 = vox_lo(s.a.X, vox_lo(s.b.X, s.c.X)), x1 = vox_hi(s.a.X, vox_hi(s.b.X, s.c.X));
-    const int64_t y0 = vox_lo(s.a.Y, vox_lo(s.b.Y, s.c.Y)), y1 = vox_hi(s.a.Y, vox_hi(s.b.Y, s.c.Y));
-    // columns are the multiples of 4096: ceil(x0 / 4096) .. floor(x1 / 4096), by arithmetic shifts, clipped to the lattice
-    s.i0 = (int)vox_hi(0, (x0 + (SNAP - 1)) >> SNAP_SHIFT); s.i1 = (int)vox_lo(g.nx - 1, x1 >> SNAP_SHIFT);
-    s.j0 = (int)vox_hi(0, (y0 + (SNAP - 1)) >> SNAP_SHIFT); s.j1 = (int)vox_lo(g.ny - 1, y1 >> SNAP_SHIFT);
-    return VOX_FACE_OK;
+using VoxSetup = Setup<SNAP_SHIFT>;
+
+// face f: its corners in lattice units, A and the column box clipped to the lattice
+DEV FaceState vox_setup(const Mesh& m, const Lattice& g, long f, VoxSetup& s) {
+    return setup_face(m, f, g.nx, g.ny, [&](const float* p, Snapped& v) { return vox_vertex(g, p, v); }, s);
 }
 
-struct VoxEdges { int64_t ea, eb, ec; };
-
-DEV VoxEdges vox_edges_at(const VoxSetup& s, int i, int j) {
-    const int64_t px = SNAP * i, py = SNAP * j;
-    VoxEdges e;
-    e.ea = (s.c.X - s.b.X) * (py - s.b.Y) - (s.c.Y - s.b.Y) * (px - s.b.X);
-    e.eb = (s.a.X - s.c.X) * (py - s.c.Y) - (s.a.Y - s.c.Y) * (px - s.c.X);
-    e.ec = (s.b.X - s.a.X) * (py - s.a.Y) - (s.b.Y - s.a.Y) * (px - s.a.X);
-    return e;
-}
+// what a walk of face s needs beside its edge functions: the sign of A, and whether a column exactly ON an edge belongs to the face
+struct VoxTies {
+    int sgn;
+    bool tie_a, tie_b, tie_c;
+    DEV explicit VoxTies(const VoxSetup& s) {
+        sgn = s.A > 0 ? 1 : -1;
+        tie_a = vox_tie(sgn, s.c.X - s.b.X, s.c.Y - s.b.Y);
+        tie_b = vox_tie(sgn, s.a.X - s.c.X, s.a.Y - s.c.Y);
+        tie_c = vox_tie(sgn, s.b.X - s.a.X, s.b.Y - s.a.Y);
+    }
+};
 
 DEV bool vox_edge_in(int sgn, int64_t e, bool tie) { return e == 0 ? tie : ((e > 0) == (sgn > 0)); }
 
-DEV bool vox_owns(const VoxSetup& s, const VoxEdges& e) {
-    return vox_edge_in(s.sgn, e.ea, s.tie_a) && vox_edge_in(s.sgn, e.eb, s.tie_b) && vox_edge_in(s.sgn, e.ec, s.tie_c);
+// (& on ints, not &&: three tests and one branch per column, where && left the third test behind a branch of its own)
+DEV bool vox_owns(const VoxTies& t, const Edges& e) {
+    return (int)vox_edge_in(t.sgn, e.ea, t.tie_a) & (int)vox_edge_in(t.sgn, e.eb, t.tie_b) & (int)vox_edge_in(t.sgn, e.ec, t.tie_c);
 }
 
 // the crossing of an owned column: float64, unfused; the number of the column's lattice points strictly below it, 0 .. nz
-DEV int vox_crossing(const VoxSetup& s, const VoxEdges& e, int nz) {
+DEV int vox_crossing(const VoxSetup& s, const Edges& e, int nz) {
     const double A = (double)s.A;
     const double wa = (double)e.ea / A, wb = (double)e.eb / A, wc = (double)e.ec / A;
-    const double z = (wa * s.a.Z + wb * s.b.Z) + wc * s.c.Z;
+    const double z = (wa * s.a.z + wb * s.b.z) + wc * s.c.z;
     const double c = ceil(z);
     if (!(c > 0.0)) return 0;
     return c >= (double)nz ? nz : (int)c;
@@ -179,16 +148,21 @@ DEV void vox_toggle(uint32_t* toggles, const Lattice& g, int rule, int i, int j,
     else atomicAdd(reinterpret_cast<int*>(toggles) + col * toggle_row(g.nz, rule) + kc, sgn);
 }
 
-DEV int vox_wave_count(bool flag) { return __popcll(__ballot(flag)); }
-
-DEV long long vox_wave_sum(long long v) {
-    for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d);
-    return v;
-}
-
-DEV void vox_stat_add(long long* stats, int which, long long n) {
-    if (n) atomicAdd(reinterpret_cast<unsigned long long*>(stats + which), (unsigned long long)n);
-}
+// what both walks do at a column of the face's box: an owned column gets the toggle of its crossing, and is counted
+struct Cross {
+    const VoxSetup& s;
+    const VoxTies t;
+    const Lattice& g;
+    int rule;
+    uint32_t* toggles;
+    long long& crossings;
+    DEV void operator()(int i, int j, const Edges e) const {
+        if (vox_owns(t, e)) {
+            vox_toggle(toggles, g, rule, i, j, vox_crossing(s, e, g.nz), t.sgn);
+            ++crossings;
+        }
+    }
+};
 
 // the toggles, the list's length and the statistics start from a kernel of the library's own, not from memset nodes
 __global__ __launch_bounds__(THREADS) void voxelize_clear_kernel(uint32_t* toggles, long n_words, unsigned long long* list_len, long long* stats) {
@@ -201,65 +175,30 @@ __global__ __launch_bounds__(THREADS) void voxelize_clear_kernel(uint32_t* toggl
 }
 
 // one lane per face; every lane stays to the end (the counts are summed over the wavefront)
-__global__ __launch_bounds__(THREADS) void voxelize_faces_kernel(const VoxMesh m, const Lattice g, int rule, uint32_t* toggles, uint32_t* list,
+__global__ __launch_bounds__(THREADS) void voxelize_faces_kernel(const Mesh m, const Lattice g, int rule, uint32_t* toggles, uint32_t* list,
                                                                  unsigned long long* list_len, long long* stats) {
     const long f = (long)blockIdx.x * THREADS + threadIdx.x;
     const bool live = f < m.n_faces;
     const int lane = threadIdx.x & 63;
     VoxSetup s;
-    VoxFaceState st = VOX_FACE_OK;
+    FaceState st = FACE_OK;
     long box = 0;
     if (live) {
         st = vox_setup(m, g, f, s);
-        if (st == VOX_FACE_OK && s.i1 >= s.i0 && s.j1 >= s.j0) box = (long)(s.i1 - s.i0 + 1) * (s.j1 - s.j0 + 1);
+        if (st == FACE_OK) box = s.box();
     }
-    {                                                    // one add per wavefront and counter, and none for a zero
-        const int used = vox_wave_count(live && st == VOX_FACE_OK), bad = vox_wave_count(live && st == VOX_FACE_BAD_VERTEX);
-        const int flat = vox_wave_count(live && st == VOX_FACE_NO_AREA);
-        if (lane == 0) {
-            vox_stat_add(stats, GPNERF_VOXEL_USED, used);
-            vox_stat_add(stats, GPNERF_VOXEL_SKIPPED_VERTEX, bad);
-            vox_stat_add(stats, GPNERF_VOXEL_SKIPPED_AREA, flat);
-        }
-    }
-    // the large tier: the wavefront's faces take consecutive places behind one add of their number
+    count_states(live, st, stats);
     const bool large = box > LARGE_BOX;
-    const unsigned long long mask = __ballot(large);
-    if (mask) {
-        const int leader = __ffsll((unsigned long long)mask) - 1;
-        unsigned long long base = 0;
-        if (lane == leader) base = atomicAdd(list_len, (unsigned long long)__popcll(mask));
-        base = __shfl(base, leader);
-        if (large) {
-            const unsigned long long at = base + (unsigned long long)__popcll(mask & ((1ull << lane) - 1ull));
-            if (at < (unsigned long long)m.n_faces) list[at] = (uint32_t)f;     // (always: a face is appended once)
-        }
-    }
+    const long long at = large_append(large, list_len, (unsigned long long)m.n_faces);
+    if (at >= 0) list[at] = (uint32_t)f;
     long long crossings = 0;
-    if (box > 0 && !large) {
-        // the box, j inside (the toggles' contiguous direction): the edge functions are linear, so the next j adds 4096 dX and the
-        // next i subtracts 4096 dY (int64: exact)
-        const int64_t aj = SNAP * (s.c.X - s.b.X), bj = SNAP * (s.a.X - s.c.X), cj = SNAP * (s.b.X - s.a.X);
-        const int64_t ai = -SNAP * (s.c.Y - s.b.Y), bi = -SNAP * (s.a.Y - s.c.Y), ci = -SNAP * (s.b.Y - s.a.Y);
-        VoxEdges row = vox_edges_at(s, s.i0, s.j0);
-        for (int i = s.i0; i <= s.i1; ++i) {
-            VoxEdges e = row;
-            for (int j = s.j0; j <= s.j1; ++j) {
-                if (vox_owns(s, e)) {
-                    vox_toggle(toggles, g, rule, i, j, vox_crossing(s, e, g.nz), s.sgn);
-                    ++crossings;
-                }
-                e.ea += aj; e.eb += bj; e.ec += cj;
-            }
-            row.ea += ai; row.eb += bi; row.ec += ci;
-        }
-    }
-    crossings = vox_wave_sum(crossings);
-    if (lane == 0) vox_stat_add(stats, GPNERF_VOXEL_CROSSINGS, crossings);
+    if (box > 0 && !large) lane_walk<INNER_J>(s, Cross{s, VoxTies(s), g, rule, toggles, crossings});
+    crossings = wave_sum(crossings);
+    if (lane == 0) stat_add(stats, GPNERF_VOXEL_CROSSINGS, crossings);
 }
 
 // fixed grid: a wavefront per listed face, 64 columns of its box per step
-__global__ __launch_bounds__(THREADS) void voxelize_large_kernel(const VoxMesh m, const Lattice g, int rule, uint32_t* toggles,
+__global__ __launch_bounds__(THREADS) void voxelize_large_kernel(const Mesh m, const Lattice g, int rule, uint32_t* toggles,
                                                                  const uint32_t* __restrict__ list, const unsigned long long* __restrict__ list_len,
                                                                  long long* stats) {
     const int lane = threadIdx.x & 63;
@@ -271,20 +210,11 @@ __global__ __launch_bounds__(THREADS) void voxelize_large_kernel(const VoxMesh m
         const long f = (long)list[at];
         if (f >= m.n_faces) continue;                    // (never: the list holds what the first kernel wrote)
         VoxSetup s;
-        if (vox_setup(m, g, f, s) != VOX_FACE_OK || s.i1 < s.i0 || s.j1 < s.j0) continue;
-        const int bw = s.j1 - s.j0 + 1;
-        const long box = (long)bw * (s.i1 - s.i0 + 1);
-        for (long k = lane; k < box; k += 64) {
-            const int i = s.i0 + (int)(k / bw), j = s.j0 + (int)(k % bw);
-            const VoxEdges e = vox_edges_at(s, i, j);
-            if (vox_owns(s, e)) {
-                vox_toggle(toggles, g, rule, i, j, vox_crossing(s, e, g.nz), s.sgn);
-                ++crossings;
-            }
-        }
+        if (vox_setup(m, g, f, s) != FACE_OK || s.i1 < s.i0 || s.j1 < s.j0) continue;
+        wave_walk<INNER_J>(s, lane, Cross{s, VoxTies(s), g, rule, toggles, crossings});
     }
-    crossings = vox_wave_sum(crossings);
-    if (lane == 0) vox_stat_add(stats, GPNERF_VOXEL_CROSSINGS, crossings);
+    crossings = wave_sum(crossings);
+    if (lane == 0) stat_add(stats, GPNERF_VOXEL_CROSSINGS, crossings);
 }
 
 // within a word: bit b becomes the XOR of bits b .. 31
@@ -353,11 +283,11 @@ __global__ __launch_bounds__(THREADS) void voxelize_resolve_parity_kernel(const 
             }
         }
     }
-    occupied = vox_wave_sum(occupied);
-    open = vox_wave_sum(open);
+    occupied = wave_sum(occupied);
+    open = wave_sum(open);
     if (lane == 0) {
-        vox_stat_add(stats, GPNERF_VOXEL_OCCUPIED, occupied);
-        vox_stat_add(stats, GPNERF_VOXEL_OPEN_COLUMNS, open);
+        stat_add(stats, GPNERF_VOXEL_OCCUPIED, occupied);
+        stat_add(stats, GPNERF_VOXEL_OPEN_COLUMNS, open);
     }
 }
 
@@ -393,11 +323,11 @@ __global__ __launch_bounds__(THREADS) void voxelize_resolve_nonzero_kernel(const
         }
         if (lane == 0) open += (carry + counts[col * row]) != 0;
     }
-    occupied = vox_wave_sum(occupied);
-    open = vox_wave_sum(open);
+    occupied = wave_sum(occupied);
+    open = wave_sum(open);
     if (lane == 0) {
-        vox_stat_add(stats, GPNERF_VOXEL_OCCUPIED, occupied);
-        vox_stat_add(stats, GPNERF_VOXEL_OPEN_COLUMNS, open);
+        stat_add(stats, GPNERF_VOXEL_OCCUPIED, occupied);
+        stat_add(stats, GPNERF_VOXEL_OPEN_COLUMNS, open);
     }
 }
 
@@ -442,8 +372,8 @@ __global__ __launch_bounds__(THREADS) void voxel_counts_kernel(const uint32_t* _
         cnt[GPNERF_VOXEL_EITHER] += __popc(wa | wb);
     }
     for (int k = 0; k < GPNERF_VOXEL_COUNTS; ++k) {
-        const long long v = vox_wave_sum(cnt[k]);
-        if ((threadIdx.x & 63) == 0) vox_stat_add(out, k, v);
+        const long long v = wave_sum(cnt[k]);
+        if ((threadIdx.x & 63) == 0) stat_add(out, k, v);
     }
 }
 
@@ -464,19 +394,6 @@ __global__ __launch_bounds__(THREADS) void voxel_contains_kernel(const uint32_t*
         v = (uint8_t)((bits[col * ((g.nz + 31) / 32) + (k >> 5)] >> (k & 31)) & 1u);
     }
     out[p] = v;
-}
-
-hipStream_t S_(void* s) { return reinterpret_cast<hipStream_t>(s); }
-int launch_status() { return hipGetLastError() == hipSuccess ? GPNERF_OK : GPNERF_E_LAUNCH; }
-unsigned blocks_for(int64_t n, int per) { return (unsigned)((n + per - 1) / per); }
-unsigned sweep_blocks(int64_t items, int per) {         // a grid-stride launch over `items`, `per` of them per block and step
-    const int64_t b = (items + per - 1) / per;
-    return (unsigned)(b < 1 ? 1 : b > SWEEP_BLOCKS_MAX ? SWEEP_BLOCKS_MAX : b);
-}
-
-bool mesh_ok(const float* vertices, int64_t n_vertices, const int32_t* faces, int64_t n_faces) {
-    return n_vertices >= 0 && n_vertices <= INT32_MAX && n_faces >= 0 && n_faces <= INT32_MAX && (vertices || n_vertices == 0) &&
-           (faces || n_faces == 0);
 }
 
 }  // namespace
@@ -500,7 +417,7 @@ int gpnerf_mesh_voxelize(const float* vertices, int64_t n_vertices, const int32_
     uint32_t* toggles = reinterpret_cast<uint32_t*>(base + l.toggles);
     uint32_t* list = reinterpret_cast<uint32_t*>(base + l.list);
     const Lattice g = lattice_of(lattice, dims);
-    const VoxMesh m = {vertices, faces, (long)n_vertices, (long)n_faces};
+    const Mesh m = {vertices, faces, (long)n_vertices, (long)n_faces};
     const long n_cols = (long)g.nx * g.ny, n_words = n_cols * (long)toggle_row_host(g.nz, rule);
     long long* st = reinterpret_cast<long long*>(stats);
     hipLaunchKernelGGL(voxelize_clear_kernel, dim3(sweep_blocks(n_words, THREADS)), dim3(THREADS), 0, S_(stream), toggles, n_words, list_len, st);
@@ -542,7 +459,7 @@ int gpnerf_voxel_stats(const uint32_t* a, const uint32_t* b, const int32_t* dims
     const long n_words = (long)dims[0] * dims[1] * ((dims[2] + 31) / 32);
     long long* o = reinterpret_cast<long long*>(out);
     hipLaunchKernelGGL(voxel_counts_zero_kernel, dim3(1), dim3(64), 0, S_(stream), o);
-    const unsigned blocks = sweep_blocks(n_words, THREADS) < 256u ? sweep_blocks(n_words, THREADS) : 256u;
+    const unsigned blocks = sweep_blocks(n_words, THREADS, COUNT_BLOCKS_MAX);
     hipLaunchKernelGGL(voxel_counts_kernel, dim3(blocks), dim3(THREADS), 0, S_(stream), a, b, n_words, o);
     return launch_status();
 }

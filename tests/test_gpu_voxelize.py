@@ -56,6 +56,10 @@ def test_bits_and_stats_equal_the_restatement(name, rule):
     assert int(grid.occupied) == ref["stats"][5]
     if name == "box_nz9":
         assert ref["stats"].tolist() == [4, 0, 8, 30, 0, 60]
+    if name == "wide_large":                                  # (these two: every used face beyond the small tier, none of a square box)
+        assert ref["stats"].tolist() == [4, 0, 8, 720, 0, 5040]
+    if name == "wedge_large":
+        assert ref["stats"].tolist() == [4, 0, 0, 610, 0, 1315]
     if name == "box_nz33":
         assert ref["occ"][2, 3, 32] and ref["bits"][2, 3, 1] == 1, "the second word's one bit is set"
     if name == "box_nz64":

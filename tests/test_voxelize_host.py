@@ -210,6 +210,12 @@ def test_open_meshes_and_faces_outside_the_lattice():
         assert a["occ"][2:7, 3:6, :].all(), "a box through the whole lattice fills its columns"
         assert a["stats"][4] >= 2, "the lone face above makes its columns open (and fills them), the one below only open"
     assert vc.case("box_large", "parity")["ref"]["stats"].tolist() == [4, 0, 8, 1800, 0, 30 * 30 * 14]
+    for rule in ("parity", "nonzero"):
+        assert vc.case("wide_large", rule)["ref"]["stats"].tolist() == [4, 0, 8, 2 * 40 * 9, 0, 40 * 9 * 14]
+        w = vc.case("wedge_large", rule)
+        assert w["ref"]["stats"].tolist() == [4, 0, 0, 610, 0, 1315] and not w["ref"]["open"].any() and 1e-4 < w["ref"]["margin"] < 2e-4
+        turned = vc.voxelize_np(w["v"], w["f"][:, ::-1], w["lo"], w["step"], w["dims"], rule)
+        assert np.array_equal(turned["occ"], w["ref"]["occ"]), "occupancy does not change when every face is reversed"
     t = vc.case("tall", "parity")
     assert t["dims"][2] // 32 + 1 > 64
 

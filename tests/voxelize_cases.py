@@ -70,7 +70,8 @@ def unpack_bits(bits, nz):
 
 def voxelize_np(vertices, faces, lo, step, dims, rule="parity"):
     """-> dict(occ bool [nx,ny,nz], bits uint32 [nx,ny,nzw], stats int64 [6], open bool [nx,ny], margin: the least distance of a
-    crossing that is no vertex hit from a lattice index (inf when there is none))"""
+    crossing that is no vertex hit from a lattice index (inf when there is none), boxes int64 [used]: the columns in each used face's
+    clipped box, kc int64: the places 0 .. nz that hold a crossing)"""
     nx, ny, nz = (int(d) for d in dims)
     usable, X, Y, Z, _ = lattice_units(vertices, lo, step)
     fs, bad, flat, A = face_states(faces, len(usable), usable, X, Y)
@@ -80,7 +81,7 @@ def voxelize_np(vertices, faces, lo, step, dims, rule="parity"):
     a, b, c = tri[:, 0], tri[:, 1], tri[:, 2]
     count = np.zeros((nx, ny, nz + 1), np.int64)            # crossings at each place kc
     signed = np.zeros((nx, ny, nz + 1), np.int64)           # and the sum of their s
-    n_cross, margin = 0, np.inf
+    n_cross, margin, boxes = 0, np.inf, np.zeros(0, np.int64)
     if len(used):
         xs, ys = X[tri], Y[tri]
         i0 = np.maximum(0, -((-xs.min(axis=1)) // SNAP))
@@ -89,6 +90,7 @@ def voxelize_np(vertices, faces, lo, step, dims, rule="parity"):
         j1 = np.minimum(ny - 1, ys.max(axis=1) // SNAP)
         bw, bh = np.maximum(i1 - i0 + 1, 0), np.maximum(j1 - j0 + 1, 0)
         bw = np.where(bh > 0, bw, 0)
+        boxes = bw * bh
         for di in range(int(bw.max())):
             col = np.nonzero(bw > di)[0]
             for dj in range(int(bh[col].max())):
@@ -128,7 +130,7 @@ def voxelize_np(vertices, faces, lo, step, dims, rule="parity"):
         raise KeyError(rule)
     occ, open_ = S[:, :, 1:], S[:, :, 0]
     stats = np.array([len(used), int(bad.sum()), int(flat.sum()), n_cross, int(open_.sum()), int(occ.sum())], np.int64)
-    return dict(occ=occ, bits=pack_bits(occ), stats=stats, open=open_, margin=margin)
+    return dict(occ=occ, bits=pack_bits(occ), stats=stats, open=open_, margin=margin, boxes=boxes, kc=np.nonzero(count.sum(axis=(0, 1)))[0])
 
 
 def voxel_counts_np(a, b=None):
@@ -228,7 +230,8 @@ def field_mesh(name):
 
 BOX = ((2.0, 3.0, 1.5), (7.0, 6.0, 5.5))                     # faces exactly on lattice planes in x and y
 BOX_B = ((4.0, 4.0, 3.5), (9.0, 9.0, 7.5))                   # 100 points, 12 of them in BOX
-NAMES = ("box_nz9", "box_nz33", "box_nz64", "box_large", "both_tiers", "all_cases", "degenerate", "outside_xy", "above_below", "twice",
+LARGE_BOX = 256                                              # columns in a face's box above which the kernels take their second tier
+NAMES = ("box_nz9", "box_nz33", "box_nz64", "box_large", "wide_large", "wedge_large", "both_tiers", "all_cases", "degenerate", "outside_xy", "above_below", "twice",
          "two_boxes", "hemisphere", "zero_faces", "anisotropic", "tall")
 UNIT = ((0.0, 0.0, 0.0), (1.0, 1.0, 1.0))
 
@@ -243,6 +246,11 @@ def _case(name):
         return join(box_mesh((2.0, 3.0, 1.5), (7.0, 6.0, 70.5)), box_mesh((8.0, 1.0, 30.5), (11.0, 4.0, 63.5))) + UNIT + ((12, 10, 64),)
     if name == "box_large":                                   # lid and floor span 30 x 30 columns: the list and its device-side length
         return box_mesh((4.5, 5.5, 2.5), (34.5, 35.5, 16.5)) + UNIT + ((40, 40, 20),)
+    if name == "wide_large":                                  # lid and floor span 40 x 9 columns: a box whose two extents differ
+        return box_mesh((4.5, 5.5, 2.5), (44.5, 14.5, 16.5)) + UNIT + ((50, 20, 20),)
+    if name == "wedge_large":                                 # a tetrahedron: four large faces, none square, every one sloping in z
+        v = mm.f32([[3.3, 2.2, 1.5], [45.6, 4.1, 3.5], [20.2, 17.3, 2.5], [22.1, 9.4, 15.5]])
+        return (v, np.array([[0, 2, 1], [0, 1, 3], [1, 2, 3], [2, 0, 3]], np.int32)) + UNIT + ((50, 20, 20),)
     if name == "both_tiers":                                  # a sphere of small faces inside the large box, and one beside it
         return join(box_mesh((4.5, 5.5, 2.5), (34.5, 35.5, 16.5)), placed_sphere(2, 6.0, (20.3, 19.7, 10.2)),
                     placed_sphere(1, 1.9, (37.1, 2.3, 5.4))) + UNIT + ((40, 40, 20),)
@@ -288,6 +296,12 @@ def case(name, rule):
     lo, step = np.array(lo, np.float64), np.array(step, np.float64)
     ref = voxelize_np(v, f, lo, step, dims, rule)
     assert_preconditions(ref)
+    if name in ("wide_large", "wedge_large"):                 # the case is what it says: every used face goes through the list
+        assert len(ref["boxes"]) == 4 and (ref["boxes"] > LARGE_BOX).all(), ref["boxes"]
+    if name == "wide_large":
+        assert sorted(ref["boxes"].tolist()) == [360] * 4
+    if name == "wedge_large":                                 # and a crossing's place is interpolated, not one value per face
+        assert sorted(ref["boxes"].tolist()) == sorted([42 * 15, 42 * 7, 25 * 13, 19 * 15]) and len(ref["kc"]) > 4, (ref["boxes"], ref["kc"])
     for a in (v, f, lo, step, ref["occ"], ref["bits"], ref["stats"], ref["open"]):
         a.setflags(write=False)
     return dict(v=v, f=f, lo=lo, step=step, dims=tuple(int(d) for d in dims), ref=ref)
