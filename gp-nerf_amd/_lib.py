@@ -155,6 +155,15 @@ ADJACENCY_START, ADJACENCY_NEIGHBOURS, ADJACENCY_VERTEX_FLAGS = range(3)
 SMOOTH_PIN_BOUNDARY = 1
 SMOOTH_MAX_ITERATIONS = 10000
 ADJACENCY_MAX_FACES = ((1 << 31) - 1) // 3
+# gpnerf_mesh_components' stats, its table's columns, the keep modes, gpnerf_mesh_components_layout's offsets, the workspace's status
+# word and its values (include/gpnerf_hip.h GPNERF_COMPONENTS_* / GPNERF_COMPONENT_*)
+COMPONENT_STATS = ("components", "closed_components", "largest", "largest_faces", "largest_vertices", "largest_euler", "kept_components",
+                   "kept_vertices", "kept_faces")
+COMPONENT_COLS = ("label", "vertices", "edges", "faces", "euler", "boundary_vertices")
+COMPONENTS_KEEP_ALL, COMPONENTS_KEEP_LARGEST, COMPONENTS_KEEP_MIN_FACES = range(3)
+COMPONENTS_LABEL, COMPONENTS_VERTEX_COMPONENT, COMPONENTS_FACE_COMPONENT, COMPONENTS_TABLE = range(4)
+COMPONENTS_HDR_STATUS = 3
+COMPONENTS_COUNTING, COMPONENTS_COUNTED, COMPONENTS_EMITTED, COMPONENTS_MISMATCH, COMPONENTS_NO_ADJACENCY = 1, 2, 3, 4, 5
 # gpnerf_mesh_voxelize's rules and stats, gpnerf_voxel_stats' row (include/gpnerf_hip.h GPNERF_VOXEL_*)
 VOXEL_PARITY, VOXEL_NONZERO = range(2)
 VOXEL_RULES = {"parity": VOXEL_PARITY, "nonzero": VOXEL_NONZERO}
@@ -280,6 +289,12 @@ SYMBOLS = {
     "gpnerf_mesh_adjacency": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "gpnerf_mesh_smooth": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_size_t, C.c_int32, C.c_double, C.c_double, C.c_uint32, C.c_void_p,
                                      C.c_void_p]),
+    "gpnerf_mesh_components_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64]),
+    "gpnerf_mesh_components_layout": (C.c_int, [C.c_int64, C.c_int64, C.POINTER(C.c_int64)]),
+    "gpnerf_mesh_components": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_size_t, C.c_int32, C.c_int64, C.c_void_p, C.c_size_t,
+                                         C.c_void_p, C.c_void_p]),
+    "gpnerf_mesh_components_emit": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_size_t, C.c_int64, C.c_int64,
+                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gpnerf_mesh_voxelize_workspace_bytes": (C.c_size_t, [C.c_int64, C.POINTER(C.c_int32), C.c_int32]),
     "gpnerf_mesh_voxelize": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, DP, C.POINTER(C.c_int32), C.c_int32, C.c_void_p, C.c_size_t,
                                        C.c_void_p, C.c_void_p, C.c_void_p]),

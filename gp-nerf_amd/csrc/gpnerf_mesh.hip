@@ -385,33 +385,9 @@ __global__ void __launch_bounds__(CC_THREADS) cc_local_kernel(const float* __res
     }
 }
 
-// The global parent array inside cc_merge_kernel.  The eight XCDs' L2s are not coherent for plain loads within one kernel, so EVERY
-// access here is an agent-scope atomic: relaxed loads (they bypass the stale levels) and atomicMin.  A parent that is read late is
-// harmless all the same, and that is what the walk relies on between its load and its use: a word only ever decreases, from a
-// member of the set to a lower member of the same set, so an old value is still an ancestor-or-self on a path to the current root.
-__device__ __forceinline__ int g_load(int* p, long i) { return __hip_atomic_load(p + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ int g_find(int* p, int i) {
-    int q = g_load(p, i);
-    while (q != i) { i = q; q = g_load(p, i); }
-    return i;
-}
-// find, then point every word of the walked path at the root found (a lower member of the same set: the invariant above holds)
-__device__ __forceinline__ int g_find_compress(int* p, int i) {
-    const int r = g_find(p, i);
-    int q = g_load(p, i);
-    while (q > r) { atomicMin(&p[i], r); i = q; q = g_load(p, i); }
-    return r;
-}
-__device__ __forceinline__ void g_union(int* p, int a, int b) {
-    while (true) {
-        a = g_find_compress(p, a); b = g_find_compress(p, b);
-        if (a == b) return;
-        if (a < b) { const int t = a; a = b; b = t; }
-        const int old = atomicMin(&p[a], b);      // a was a root when read; if it still is, it now hangs below b
-        if (old == a) return;
-        a = old;                                   // somebody linked a first (to old < a): old and b still have to meet
-    }
-}
+// The global parent array inside cc_merge_kernel: g_load / g_find / g_find_compress / g_union, every access an agent-scope atomic
+// (shared with gpnerf_meshcomp.hip, which unites over a mesh's faces; the header says why no plain load will do and why no lane waits)
+#include "gpnerf_unionfind.h"
 
 template <int NLOWER>
 __global__ void __launch_bounds__(CC_THREADS) cc_merge_kernel(const Grid g, int* parent) {

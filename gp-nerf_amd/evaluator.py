@@ -257,6 +257,14 @@ class MeshEvaluator:
     `watertight_frames` (how many frames' meshes are closed and oriented), `topology_<name>` for the edge counts and `euler` (means
     over the frames) and their per-frame lists, and saves `<result_path>/topology_metrics.npy` (a structured array: frame_index, the
     ten counts, closed, oriented, watertight).
+    components (off by default; a knob of its own, so that topology=True's keys and file stay what they are): `evaluate` uploads the
+    frame's mesh and enqueues frame.mesh_components (every component kept), a slot per frame of the nine counts
+    (_lib.COMPONENT_STATS), the largest component's boundary vertices and the mesh's non-manifold and inconsistent edges; no host
+    read per frame.  `summarize()` reads the slots in one copy and adds `components_mean` (pieces per frame), `single_component_frames`
+    and the per-frame lists `components`, `components_largest_faces`, `components_largest_genus` and `components_frame_index`, and
+    saves `<result_path>/components_metrics.npy` (a structured array: frame_index, the nine counts, and largest_genus, the genus of
+    the largest component by frame.read_mesh_components' rule, -1 where it is not defined).  It is the first thing to look at when a
+    sequence's Chamfer distance or volume IoU jumps on one frame.
     volume (off by default; the third standard reconstruction number beside Chamfer and normal consistency, and the one that compares
     solids): a batch with `gt_mesh` and an output with `axes` make `evaluate` voxelise both meshes on the frame's padded cube lattice
     (frame.voxelize_mesh, rule `volume_rule`: "nonzero" unites a scan's separate parts, "parity" is indifferent to orientation) -- the
@@ -270,7 +278,7 @@ class MeshEvaluator:
 
     def __init__(self, result_path, mesh_th, export_mesh=False, metric_samples=100000, metric_thresholds=(0.005, 0.01, 0.02),
                  metric_max_dist=float("inf"), metric_device=None, metric_cell_cap=None, metric_entry_cap=None, silhouette=False,
-                 topology=False, volume=False, volume_rule="nonzero"):
+                 topology=False, volume=False, volume_rule="nonzero", components=False):
         self.mesh_th = mesh_th
         self.export_mesh = bool(export_mesh)
         self.result_path = result_path
@@ -284,6 +292,8 @@ class MeshEvaluator:
         self._sil_slots, self._sil_frames = [], []
         self.topology = bool(topology)
         self._topo_slots, self._topo_frames = [], []
+        self.components = bool(components)
+        self._comp_slots, self._comp_frames = [], []
         self.volume, self.volume_rule = bool(volume), str(volume_rule)
         if self.volume_rule not in L.VOXEL_RULES:
             raise L.GpnerfError(f"MeshEvaluator: volume_rule is 'parity' or 'nonzero', got {volume_rule!r}")
@@ -293,9 +303,9 @@ class MeshEvaluator:
 
     @property
     def has_mesh_metrics(self):
-        """True once a frame with `gt_mesh` (or, with silhouette on, with masks and cameras; or any frame with topology on) has been evaluated and not yet summarized
+        """True once a frame with `gt_mesh` (or, with silhouette on, with masks and cameras; or any frame with topology or components on) has been evaluated and not yet summarized
         (evaluate_loop asks)"""
-        return bool(self._slots) or bool(self._sil_slots) or bool(self._topo_slots) or bool(self._vol_slots)
+        return bool(self._slots) or bool(self._sil_slots) or bool(self._topo_slots) or bool(self._vol_slots) or bool(self._comp_slots)
 
     def _enqueue_volume(self, output, batch):
         from . import frame as F
@@ -406,6 +416,17 @@ class MeshEvaluator:
             v, f = F.mesh_to_device(output["mesh"], torch.device(self.metric_device if self.metric_device is not None else "cuda:0"))
             self._topo_slots.append(F.mesh_topology(f, int(v.shape[0])))
             self._topo_frames.append(self._scalar(batch["frame_index"]))
+        if self.components:
+            from . import frame as F
+            v, f = F.mesh_to_device(output["mesh"], torch.device(self.metric_device if self.metric_device is not None else "cuda:0"))
+            comp = F.mesh_components(f, int(v.shape[0]))
+            # the largest component's row, picked on the device (row 0 of a table that may have none, when there is no component)
+            at = comp.stats[L.COMPONENT_STATS.index("largest")].clamp(min=0).reshape(1)
+            boundary = (comp.table.index_select(0, at)[0, L.COMPONENT_COLS.index("boundary_vertices")].reshape(1) if comp.table.shape[0]
+                        else torch.zeros((1,), device=v.device, dtype=torch.int64))
+            edges = comp.adjacency.stats[[L.TOPOLOGY_STATS.index("nonmanifold_edges"), L.TOPOLOGY_STATS.index("inconsistent_edges")]]
+            self._comp_slots.append(torch.cat([comp.stats, boundary, edges]))
+            self._comp_frames.append(self._scalar(batch["frame_index"]))
 
     def _summarize_silhouettes(self):
         """the silhouette slots -> (means, per-frame lists), silhouette_metrics.npy written; resets them"""
@@ -458,10 +479,32 @@ class MeshEvaluator:
         self._topo_slots, self._topo_frames = [], []
         return metrics, per_frame
 
+    def _summarize_components(self):
+        """the component slots -> (means, per-frame lists), components_metrics.npy written; resets them"""
+        host = torch.stack(self._comp_slots).cpu().numpy()     # the one read
+        n = len(L.COMPONENT_STATS)
+        rows = [dict(zip(L.COMPONENT_STATS, (int(x) for x in h[:n]))) for h in host]
+        for r, h in zip(rows, host):                           # frame.read_mesh_components' rule, on the largest component's row
+            defined = r["largest"] >= 0 and h[n] == 0 and h[n + 1] == 0 and h[n + 2] == 0 and r["largest_euler"] % 2 == 0
+            r["largest_genus"] = (2 - r["largest_euler"]) // 2 if defined else -1
+        per_frame = {"components": [r["components"] for r in rows], "components_largest_faces": [r["largest_faces"] for r in rows],
+                     "components_largest_genus": [r["largest_genus"] for r in rows], "components_frame_index": list(self._comp_frames)}
+        metrics = {"components_mean": float(np.mean(per_frame["components"])),
+                   "single_component_frames": int(sum(c == 1 for c in per_frame["components"]))}
+        table = np.zeros(len(rows), dtype=[("frame_index", "i8")] + [(k, "i8") for k in L.COMPONENT_STATS] + [("largest_genus", "i8")])
+        table["frame_index"] = self._comp_frames
+        for k in table.dtype.names[1:]:
+            table[k] = [r[k] for r in rows]
+        os.makedirs(self.result_path, exist_ok=True)
+        np.save(os.path.join(self.result_path, "components_metrics.npy"), table)    # a structured array: one row per frame
+        print(f"single_component_frames: {metrics['single_component_frames']} of {len(rows)}")
+        self._comp_slots, self._comp_frames = [], []
+        return metrics, per_frame
+
     def summarize(self):
-        if self._sil_slots or self._topo_slots or self._vol_slots:
+        if self._sil_slots or self._topo_slots or self._vol_slots or self._comp_slots:
             parts = (([self._summarize_silhouettes()] if self._sil_slots else []) + ([self._summarize_topology()] if self._topo_slots else []) +
-                     ([self._summarize_volumes()] if self._vol_slots else []))
+                     ([self._summarize_volumes()] if self._vol_slots else []) + ([self._summarize_components()] if self._comp_slots else []))
             metrics = self._summarize_mesh_metrics() if self._slots else {"per_frame": {}}
             per_frame = metrics.pop("per_frame")
             for means, frames in parts:

@@ -1100,7 +1100,7 @@ def mesh_topology(faces, n_vertices):
 def read_mesh_topology(stats):
     """mesh_topology's stats on the host (a tensor or array of 10) -> dict of the _lib.TOPOLOGY_STATS names, plus `closed` (no boundary
     and no non-manifold edge), `oriented` (no inconsistent and no non-manifold edge) and `watertight` (both).  Connected components and
-    the genus are not counted."""
+    the genus: mesh_components / read_mesh_components."""
     row = np.asarray(stats.detach().cpu() if isinstance(stats, torch.Tensor) else stats).astype(np.int64).reshape(-1)
     if row.shape != (len(L.TOPOLOGY_STATS),):
         raise L.GpnerfError(f"read_mesh_topology: expected {len(L.TOPOLOGY_STATS)} counts, got {row.shape}")
@@ -1147,8 +1147,177 @@ def smooth_mesh(vertices, faces=None, adjacency=None, iterations=10, lam=0.5, mu
     return out
 
 
+def parse_components(value, what="components"):
+    """extract_mesh(components=...) / Renderer(mesh_components=...) / GPNERF_MESH_COMPONENTS -> None (off), "largest" (keep the component
+    with the most faces) or a whole number N >= 1 (keep the components of at least N faces): off is None, False, 0, "0" or "";
+    anything else is refused."""
+    if value is None or value is False:
+        return None
+    if isinstance(value, str):
+        text = value.strip()
+        if text in ("", "0"):
+            return None
+        if text == "largest":
+            return "largest"
+        try:
+            value = int(text)
+        except ValueError:
+            raise L.GpnerfError(f"{what}: expected 0, 'largest' or a number of faces >= 1, got {text!r}") from None
+    if isinstance(value, (float, np.floating)) and np.isfinite(value) and float(value) == int(value):
+        value = int(value)
+    if isinstance(value, bool) or not isinstance(value, (int, np.integer)):
+        raise L.GpnerfError(f"{what}: expected None, 'largest' or a number of faces >= 1, got {value!r}")
+    value = int(value)
+    if value == 0:
+        return None
+    if value < 1:
+        raise L.GpnerfError(f"{what}: expected None, 'largest' or a number of faces >= 1, got {value!r}")
+    return value
+
+
+class MeshComponents:
+    """gpnerf_mesh_components' result, all on the device: `stats` int64 [9] (_lib.COMPONENT_STATS names them), the MeshAdjacency it was
+    built on (`adjacency`), and four views into `workspace`: `label` int32 [n_vertices] (the smallest vertex index of the vertex's
+    component, -1 for a vertex no usable face references), `vertex_component` int32 [n_vertices] and `face_component` int32 [n_faces]
+    (the component's number, components numbered in ascending label; -1 for an unreferenced vertex / an unusable face) and `table`
+    int64 [n_vertices // 3, 6] (_lib.COMPONENT_COLS; only the first stats[0] rows are defined).  `keep` / `min_faces`: the selection
+    the counts KEPT_* were made for; filter_components emits it."""
+
+    def __init__(self, adjacency, workspace, stats, offsets, keep, min_faces):
+        self.adjacency, self.workspace, self.stats, self.keep, self.min_faces = adjacency, workspace, stats, keep, min_faces
+        self.n_vertices, self.n_faces = adjacency.n_vertices, adjacency.n_faces
+        view = lambda off, nbytes, dt: workspace[off:off + nbytes].view(dt)
+        self.label = view(offsets[L.COMPONENTS_LABEL], 4 * self.n_vertices, torch.int32)
+        self.vertex_component = view(offsets[L.COMPONENTS_VERTEX_COMPONENT], 4 * self.n_vertices, torch.int32)
+        self.face_component = view(offsets[L.COMPONENTS_FACE_COMPONENT], 4 * self.n_faces, torch.int32)
+        rows = self.n_vertices // 3
+        self.table = view(offsets[L.COMPONENTS_TABLE], 8 * len(L.COMPONENT_COLS) * rows, torch.int64).view(rows, len(L.COMPONENT_COLS))
+
+
+def _components_keep(keep, min_faces, what):
+    """(keep, min_faces) as the wrappers take them -> the C call's (mode, min_faces): keep is None or "all", "largest", or a whole
+    number N >= 1 (the components of at least N faces, which min_faces=N says too)"""
+    if isinstance(keep, str) and keep == "all":
+        keep = None
+    keep = parse_components(keep, f"{what}: keep")
+    if min_faces is not None:
+        if keep is not None:
+            raise L.GpnerfError(f"{what}: give keep or min_faces, not both")
+        if isinstance(min_faces, bool) or not isinstance(min_faces, (int, np.integer)) or min_faces < 1:
+            raise L.GpnerfError(f"{what}: min_faces must be an integer >= 1, got {min_faces!r}")
+        keep = int(min_faces)
+    if keep is None:
+        return L.COMPONENTS_KEEP_ALL, 0
+    if keep == "largest":
+        return L.COMPONENTS_KEEP_LARGEST, 0
+    return L.COMPONENTS_KEEP_MIN_FACES, keep
+
+
+def mesh_components(faces, n_vertices, adjacency=None, keep=None, min_faces=None):
+    """gpnerf_mesh_components on device faces (int32 [m,3]) of a mesh of n_vertices vertices -> MeshComponents: the connected components
+    of the graph of the usable faces' edges (VERTEX connectivity: two sheets that touch in one vertex are one component, where
+    trimesh.split's default, face adjacency, gives two), labelled, numbered in ascending label, with their table and the stats.
+    include/gpnerf_hip.h states the definition.  adjacency: a MeshAdjacency of this mesh to reuse; without one it is built here.
+    keep: None or "all" (every component), "largest", or N (the components of at least N faces; min_faces=N says the same) -- it
+    decides the stats' KEPT_* counts and what filter_components emits from this result.  Nothing is read back; the workspace's size is
+    a formula of the two counts."""
+    lib = L.lib()
+    nv, nf = _adjacency_faces(faces, n_vertices, "mesh_components")
+    mode, n_min = _components_keep(keep, min_faces, "mesh_components")
+    if adjacency is None:
+        adjacency = mesh_adjacency(faces, nv)
+    elif not isinstance(adjacency, MeshAdjacency) or adjacency.n_vertices != nv or adjacency.n_faces != nf or adjacency.workspace.device != faces.device:
+        raise L.GpnerfError(f"mesh_components: adjacency must be a MeshAdjacency of a mesh of {nv} vertices and {nf} faces on {faces.device}")
+    nbytes = int(lib.gpnerf_mesh_components_workspace_bytes(nv, nf))
+    offsets = (C.c_int64 * 4)()
+    if nbytes <= 0 or lib.gpnerf_mesh_components_layout(nv, nf, offsets) != 0:
+        raise L.GpnerfError(f"mesh_components: sizes refused ({nv} vertices, {nf} faces; at most {L.ADJACENCY_MAX_FACES} faces)")
+    dev = faces.device
+    ws = torch.empty((nbytes,), device=dev, dtype=torch.uint8)
+    stats = torch.empty((len(L.COMPONENT_STATS),), device=dev, dtype=torch.int64)
+    aws = adjacency.workspace
+    L.check(lib.gpnerf_mesh_components(faces.data_ptr() if nf else None, nf, nv, aws.data_ptr(), aws.numel(), mode, n_min, ws.data_ptr(),
+                                       ws.numel(), stats.data_ptr(), _stream_ptr(dev)), "gpnerf_mesh_components")
+    return MeshComponents(adjacency, ws, stats, [int(o) for o in offsets], mode, n_min)
+
+
+def read_mesh_components(stats, table=None, topology_stats=None):
+    """mesh_components' stats on the host (a tensor or array of 9) -> dict of the _lib.COMPONENT_STATS names.  With `table` (the
+    MeshComponents' table or its first rows) `rows` is added: one dict per component with the _lib.COMPONENT_COLS names, `closed`
+    (boundary_vertices == 0) and `genus`: (2 - euler) // 2 when the component is closed, the mesh's inconsistent_edges and
+    nonmanifold_edges are both 0 -- `topology_stats`, the adjacency's stats, says so; without it no genus is given -- and euler is
+    even; None otherwise.  `largest_genus` is that of the largest component (None when there is none or no table).  A PINCHED vertex --
+    all of its edges manifold, but its link more than one cycle (two cones tip to tip) -- is NOT detected: it leaves every count this
+    rule reads as a closed manifold's would be, and makes the genus wrong."""
+    host = lambda t: np.asarray(t.detach().cpu() if isinstance(t, torch.Tensor) else t).astype(np.int64)
+    row = host(stats).reshape(-1)
+    if row.shape != (len(L.COMPONENT_STATS),):
+        raise L.GpnerfError(f"read_mesh_components: expected {len(L.COMPONENT_STATS)} counts, got {row.shape}")
+    res = {k: int(v) for k, v in zip(L.COMPONENT_STATS, row)}
+    if table is None:
+        return res
+    tab = host(table)
+    if tab.ndim != 2 or tab.shape[1] != len(L.COMPONENT_COLS) or tab.shape[0] < res["components"]:
+        raise L.GpnerfError(f"read_mesh_components: expected a table of at least {res['components']} rows of {len(L.COMPONENT_COLS)}, got {tab.shape}")
+    manifold = False
+    if topology_stats is not None:
+        topo = read_mesh_topology(topology_stats)
+        manifold = topo["inconsistent_edges"] == 0 and topo["nonmanifold_edges"] == 0
+    rows = []
+    for r in tab[:res["components"]]:
+        d = {k: int(v) for k, v in zip(L.COMPONENT_COLS, r)}
+        d["closed"] = d["boundary_vertices"] == 0
+        d["genus"] = (2 - d["euler"]) // 2 if d["closed"] and manifold and d["euler"] % 2 == 0 else None
+        rows.append(d)
+    res["rows"] = rows
+    res["largest_genus"] = rows[res["largest"]]["genus"] if res["largest"] >= 0 else None
+    return res
+
+
+def filter_components(vertices, faces, keep="largest", components=None, want_map=False):
+    """gpnerf_mesh_components + gpnerf_mesh_components_emit: the device mesh (vertices float32 [n,3], faces int32 [m,3]) of the kept
+    components -> (vertices float32 [n',3], faces int32 [m',3], stats int64 [9] (_lib.COMPONENT_STATS), maps), all on the device.  keep:
+    "largest" (default), N (the components of at least N faces) or None / "all" (every component: only the unreferenced vertices and
+    the unusable faces go).  The kept vertices and faces stay in their original order, the coordinates are copied bit for bit.
+    components: a MeshComponents of this mesh to emit from (its own keep decides; `keep` is then not looked at).  want_map: maps =
+    (vertex_map int32 [n], old -> new or -1; kept_vertices int32 [n'], new -> old: attribute.index_select(0, kept_vertices.long())
+    carries a per-vertex attribute over), otherwise None.  One host read: the two kept sizes."""
+    lib = L.lib()
+    nv, nf = _mesh_arrays(vertices, faces, "filter_components")
+    if components is None:
+        components = mesh_components(faces, nv, keep=keep)
+    elif not isinstance(components, MeshComponents) or components.n_vertices != nv or components.n_faces != nf or components.workspace.device != vertices.device:
+        raise L.GpnerfError(f"filter_components: components must be a MeshComponents of a mesh of {nv} vertices and {nf} faces on {vertices.device}")
+    dev = vertices.device
+    n_out_v, n_out_f = (int(v) for v in components.stats[len(L.COMPONENT_STATS) - 2:].cpu().tolist())
+    out_v = torch.empty((n_out_v, 3), device=dev, dtype=torch.float32)
+    out_f = torch.empty((n_out_f, 3), device=dev, dtype=torch.int32)
+    vmap = torch.empty((nv,), device=dev, dtype=torch.int32) if want_map else None
+    kept = torch.empty((n_out_v,), device=dev, dtype=torch.int32) if want_map else None
+    ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None
+    ws = components.workspace
+    L.check(lib.gpnerf_mesh_components_emit(ptr(vertices), nv, ptr(faces), nf, ws.data_ptr(), ws.numel(), n_out_v, n_out_f, ptr(out_v), ptr(out_f),
+                                            ptr(vmap), ptr(kept), _stream_ptr(dev)), "gpnerf_mesh_components_emit")
+    return out_v, out_f, components.stats, ((vmap, kept) if want_map else None)
+
+
+def _mesh_arrays(vertices, faces, what):
+    """a device mesh that may be empty: (n_vertices, n_faces)"""
+    for t, name in ((vertices, "vertices"), (faces, "faces")):
+        if not isinstance(t, torch.Tensor):
+            raise L.GpnerfError(f"{what}: {name} must be a device tensor (mesh_to_device uploads a Mesh)")
+        _require_gpu(t, f"{what}: {name}")
+    if vertices.dtype != torch.float32 or vertices.dim() != 2 or vertices.shape[1] != 3 or not vertices.is_contiguous():
+        raise L.GpnerfError(f"{what}: expected contiguous float32 vertices [n,3], got {vertices.dtype} {tuple(vertices.shape)}")
+    if faces.dtype != torch.int32 or faces.dim() != 2 or faces.shape[1] != 3 or not faces.is_contiguous():
+        raise L.GpnerfError(f"{what}: expected contiguous int32 faces [m,3], got {faces.dtype} {tuple(faces.shape)}")
+    if faces.device != vertices.device:
+        raise L.GpnerfError(f"{what}: vertices and faces are on different devices")
+    return int(vertices.shape[0]), int(faces.shape[0])
+
+
 def extract_mesh(frame, voxel_size, bounds_min, Rh, Th, neg_ray=False, iso=1.0 / 50.0, host=None, clean=None, fill_cavities=None,
-                 normals=False, lattice=None, simplify=None, smooth=None, topology=False):
+                 normals=False, lattice=None, simplify=None, smooth=None, topology=False, components=None):
     """The geometry mode of demo_render.py's render_rays (:166-175, 249-311, 366-376) on the device: the box of the occupied voxels,
     the lattice, the alpha cube and its marching-cubes mesh.  Two host reads: the box (6 values) and the mesh counts (2).
     Returns {"cube" (device [X+20,Y+20,Z+20]), "vertices", "faces" (device), "axes", "can_bounds", "n_kept" (device int64),
@@ -1164,7 +1333,13 @@ def extract_mesh(frame, voxel_size, bounds_min, Rh, Th, neg_ray=False, iso=1.0 /
     iterations (smooth_mesh at its defaults: lam 0.5, mu -0.53, open borders pinned), which run behind marching cubes and simplify and
     in front of the normals, which are then taken at the smoothed vertices; topology: the mesh's topology counts.  With either,
     "topology_stats" (device int64 [10], _lib.TOPOLOGY_STATS: of the mesh as returned -- smoothing moves no face) is added, the
-    adjacency is built once, and no host read is added.  With all six off no further launch is enqueued.
+    adjacency is built once, and no host read is added.  components ("largest" or N, parse_components): filter_components runs behind
+    marching cubes and simplify and in front of smoothing, topology and normals -- the components that are not kept (all but the one
+    with the most faces, or those of fewer than N faces) leave the mesh, so that smoothing, "topology_stats", normals and colours are
+    of the mesh as returned --; "component_stats" (device int64 [9], _lib.COMPONENT_STATS: the counts of the mesh BEFORE the filter and
+    what was kept) is added, and the call has one more host read (the two kept sizes).  It builds an adjacency of the unfiltered mesh;
+    when smoothing or topology is also on, the adjacency is built a second time, on the filtered mesh.  With components off no launch
+    and no host read is added.  With all seven off no further launch is enqueued.
     lattice: a ready (cube, axes, n_kept) -- the dense renderer's hull-carved cube (density_lattice(inside=...)) -- in place of the
     box, the lattice and the occupancy-culled cube; cleaning, marching cubes, normals and "lattice" are then the same code.  The box
     read does not happen and "can_bounds" is left out."""
@@ -1187,6 +1362,9 @@ def extract_mesh(frame, voxel_size, bounds_min, Rh, Th, neg_ray=False, iso=1.0 /
         cells = [int(np.ceil(d / k)) + 1 for d in surface.shape]
         res["vertices"], res["faces"], res["simplify_stats"], _ = simplify_mesh(res["vertices"], res["faces"], k, lo=(-0.5, -0.5, -0.5),
                                                                                 cells=cells)
+    keep = parse_components(components, "extract_mesh: components")
+    if keep is not None:
+        res["vertices"], res["faces"], res["component_stats"], _ = filter_components(res["vertices"], res["faces"], keep=keep)
     n_smooth = parse_smooth(smooth, "extract_mesh: smooth")
     if n_smooth is not None or topology:
         adjacency = mesh_adjacency(res["faces"], int(res["vertices"].shape[0]))

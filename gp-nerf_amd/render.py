@@ -57,7 +57,8 @@ class Renderer(nn.Module):
     def __init__(self, encoder, nerfhead, is_train=False, neg_ray_train=False, neg_ray_val=False, n_rays=1024,
                  n_samples=64, voxel_size=(0.005, 0.005, 0.005), chunk=64, mesh_th=-1, early_term=None, term_eps=1e-5,
                  progressive=False, split_f16=None, sharded_outputs="all", shard_group=None, encoder_graph=None, fold_levels=None, reserve_cus=None,
-                 mesh_colors=None, mesh_clean=None, mesh_normals=None, mesh_simplify=None, mesh_smooth=None, mesh_topology=None):
+                 mesh_colors=None, mesh_clean=None, mesh_normals=None, mesh_simplify=None, mesh_smooth=None, mesh_topology=None,
+                 mesh_components=None):
         super().__init__()
         self.encoder = encoder
         self.nerfhead = nerfhead
@@ -130,6 +131,13 @@ class Renderer(nn.Module):
         self.mesh_smooth = F_.parse_smooth(os.environ.get("GPNERF_MESH_SMOOTH", "0") if mesh_smooth is None else mesh_smooth,
                                            "mesh_smooth / GPNERF_MESH_SMOOTH")
         self.mesh_topology = (os.environ.get("GPNERF_MESH_TOPOLOGY", "0") == "1") if mesh_topology is None else bool(mesh_topology)
+        # mesh_components (GPNERF_MESH_COMPONENTS = unset / 0 (off), largest, or N >= 1): the mesh's connected components are labelled
+        # on the device (gpnerf_mesh_components) behind marching cubes and the simplification, and only the one with the most faces
+        # -- or those of at least N faces -- stay, before smoothing, topology, normals and colours.  It is the mesh-side twin of
+        # mesh_clean, for what the cube cannot see (a sliver the simplification detached; the hull mesh).  `mesh_stats` gains the
+        # nine counts of _lib.COMPONENT_STATS as mesh_<name>.  Off by default.
+        self.mesh_components = F_.parse_components(os.environ.get("GPNERF_MESH_COMPONENTS", "0") if mesh_components is None else mesh_components,
+                                                   "mesh_components / GPNERF_MESH_COMPONENTS")
 
     # ---- helpers the reference exposes as methods (stage entry points) ----------------------------
     def _neg_ray(self, batch):
@@ -315,10 +323,12 @@ class Renderer(nn.Module):
     @staticmethod
     def _mesh_stats(m):
         """extract_mesh's device counts as one dict: gpnerf_cube_clean's six (_lib.CUBE_STATS) with mesh_clean, the simplification's
-        eight (_lib.SIMPLIFY_STATS) with mesh_simplify, the topology's ten (_lib.TOPOLOGY_STATS) with mesh_smooth or mesh_topology; None
+        eight (_lib.SIMPLIFY_STATS) with mesh_simplify, the components' nine (_lib.COMPONENT_STATS, as mesh_<name>: the cube's counts have a
+        `components` of their own) with mesh_components, the topology's ten (_lib.TOPOLOGY_STATS) with mesh_smooth or mesh_topology; None
         with all of them off."""
         stats = None
-        for key, names in (("clean_stats", L.CUBE_STATS), ("simplify_stats", L.SIMPLIFY_STATS), ("topology_stats", L.TOPOLOGY_STATS)):
+        for key, names in (("clean_stats", L.CUBE_STATS), ("simplify_stats", L.SIMPLIFY_STATS),
+                           ("component_stats", tuple(f"mesh_{n}" for n in L.COMPONENT_STATS)), ("topology_stats", L.TOPOLOGY_STATS)):
             if key in m:
                 stats = {**(stats or {}), **dict(zip(names, m[key].cpu().tolist()))}
         return stats
@@ -338,7 +348,10 @@ class Renderer(nn.Module):
         of that surface over cubic cells of k lattice steps (frame.simplify_mesh: one more host read, the two sizes); normals and
         colours are taken at the simplified vertices, and `mesh_stats` gains the eight counts of _lib.SIMPLIFY_STATS.  With mesh_smooth
         = n the vertices then go through n Taubin iterations (frame.smooth_mesh; no host read) before normals and colours are taken,
-        and with it or mesh_topology `mesh_stats` gains the ten counts of _lib.TOPOLOGY_STATS.  With all of them off, extract_mesh
+        and with it or mesh_topology `mesh_stats` gains the ten counts of _lib.TOPOLOGY_STATS.  With mesh_components ("largest" or N) only
+        the connected components kept stay in the mesh (frame.filter_components, behind the simplification and in front of smoothing,
+        topology, normals and colours: one more host read, the two sizes), and `mesh_stats` gains the nine counts of
+        _lib.COMPONENT_STATS as mesh_<name> (of the mesh before the filter, and what was kept).  With all of them off, extract_mesh
         enqueues exactly the launches it did before there were these options."""
         dev = batch["src_imgs"].device
         torch.cuda.synchronize(dev)
@@ -357,7 +370,8 @@ class Renderer(nn.Module):
         ev[2].record()
         m = F_.extract_mesh(frame, self.voxel_size, batch["bounds"][0, 0], batch["Rh"][0], batch["Th"][0], neg_ray=self._neg_ray(batch),
                             iso=M_.ISO_REFERENCE, host=box_host, clean=self.mesh_clean, normals=self.mesh_normals,
-                            simplify=self.mesh_simplify, smooth=self.mesh_smooth, topology=self.mesh_topology)
+                            simplify=self.mesh_simplify, smooth=self.mesh_smooth, topology=self.mesh_topology,
+                            components=self.mesh_components)
         colours = None
         if self.mesh_colors:
             colours = F_.query_points(frame, m["vertices"], neg_ray=self._neg_ray(batch), want=("rgb",), lattice=m["lattice"])["rgb"]
@@ -390,7 +404,7 @@ class Renderer(nn.Module):
               loader neither builds the 12 B/point `pts` array nor carves.
         Returns `cube` (the padded alpha cube, float32 numpy), `mesh` (mesh.Mesh, vertices in index units of the padded cube), `axes`
         (three host float32 arrays), `n_inside` (kept points), `time_slots`, `etime`, `rtime`, and `mesh_stats` with mesh_clean,
-        mesh_simplify, mesh_smooth or mesh_topology.  mesh_clean / mesh_normals / mesh_colors / mesh_simplify / mesh_smooth / mesh_topology act as in render_mesh.  Host reads: the constants (with the axes or the cameras) before
+        mesh_simplify, mesh_smooth, mesh_topology or mesh_components.  mesh_clean / mesh_normals / mesh_colors / mesh_simplify / mesh_smooth / mesh_topology / mesh_components act as in render_mesh.  Host reads: the constants (with the axes or the cameras) before
         the encoder, the mesh counts, and the results."""
         dev = batch["src_imgs"].device
         have_a = "pts" in batch and "inside" in batch
@@ -436,7 +450,7 @@ class Renderer(nn.Module):
         cube, n_kept = F_.density_lattice(frame, axes, neg_ray=neg, pad=F_.MESH_PAD, inside=inside)
         m = F_.extract_mesh(frame, self.voxel_size, None, None, None, neg_ray=neg, iso=self.mesh_th, host=[vs_host], clean=self.mesh_clean,
                             normals=self.mesh_normals, lattice=(cube, axes, n_kept), simplify=self.mesh_simplify, smooth=self.mesh_smooth,
-                            topology=self.mesh_topology)
+                            topology=self.mesh_topology, components=self.mesh_components)
         colours = None
         if self.mesh_colors:
             colours = F_.query_points(frame, m["vertices"], neg_ray=neg, want=("rgb",), lattice=m["lattice"])["rgb"]

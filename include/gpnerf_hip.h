@@ -845,8 +845,7 @@ int gpnerf_mesh_simplify_emit(const float* vertices, int64_t n_vertices, const i
  *      usable face), EDGES, BOUNDARY_EDGES, NONMANIFOLD_EDGES, INCONSISTENT_EDGES, EULER = VERTICES_REFERENCED - EDGES + FACES_USED,
  *      BOUNDARY_VERTICES (the vertices on a boundary or non-manifold edge), MAX_VALENCE (the largest number of neighbours).  The mesh
  *      is CLOSED iff it has no boundary and no non-manifold edge, ORIENTED iff no inconsistent and no non-manifold edge, WATERTIGHT iff
- *      both.  Connected components and the genus are not counted: a label propagation over a mesh needs a data-dependent number of
- *      launches or a device-wide loop, and the floaters are dealt with on the cube (gpnerf_cube_clean).
+ *      both.  Connected components, and with them the genus, are counted by gpnerf_mesh_components (below) on a finished adjacency.
  *   4. the ADJACENCY, a CSR inside the workspace at gpnerf_mesh_adjacency_layout's byte offsets: start int64 [n_vertices + 1] (start[0]
  *      = 0), neighbours int32 with a capacity of 6 n_faces of which start[n_vertices] = 2 EDGES entries are in use -- vertex v's
  *      neighbours, the other ends of its edges, each once, in ASCENDING index at start[v] .. start[v + 1] --, and vertex_flags uint8
@@ -906,6 +905,114 @@ int gpnerf_mesh_adjacency(const int32_t* faces, int64_t n_faces, int64_t n_verti
                           void* stream);
 int gpnerf_mesh_smooth(const float* vertices, int64_t n_vertices, void* workspace, size_t workspace_bytes, int32_t iterations, double lam,
                        double mu, uint32_t flags, float* out_vertices, void* stream);
+
+/* ---- the connected components of a mesh (gpnerf_meshcomp.hip): a label per vertex and face, a table with every component's counts
+ * and Euler characteristic, and the mesh of the components the caller keeps (all, the largest, those of at least min_faces faces).
+ * It is what tells how many pieces a mesh has and drops the floaters of a mesh that has no alpha cube to clean (a loaded scan, a
+ * simplified mesh, the hull mesh).  Both calls: kernel launches only, on the caller's stream; nothing allocated, nothing waited for;
+ * every launch sized from the arguments alone; every data-dependent length stays in the workspace; both capture into a HIP graph
+ * and replay with the same bits.  The labels come from a lock-free min-label union-find over the faces (gpnerf_unionfind.h, the
+ * scheme of the cube's components): a FIXED number of launches, no device-wide barrier, no cooperative launch, and no lane ever
+ * waits for a value another lane has yet to write.
+ * faces: device int32 [n_faces][3]; n_vertices 0 to 2^31 - 1; n_faces 0 to 715 827 882 (the adjacency's limits); faces may be NULL
+ * where n_faces is 0.  adjacency_workspace: the workspace gpnerf_mesh_adjacency filled for THIS mesh (same faces, n_vertices and
+ * n_faces), of adjacency_bytes >= gpnerf_mesh_adjacency_workspace_bytes(n_vertices, n_faces) bytes; it is read, never written.
+ *
+ * THE DEFINITION
+ *   1. USABLE faces are the adjacency's: indices in [0, n_vertices), pairwise distinct.  G is the graph whose nodes are the vertices a
+ *      usable face references and whose edges are the unique undirected edges of the usable faces: exactly what the adjacency's CSR
+ *      stores.
+ *   2. a COMPONENT is a connected component of G: VERTEX connectivity.  Two sheets that touch in a single vertex are one component.
+ *      (This differs from trimesh.split's default, which joins faces across shared EDGES only and would give two.)
+ *   3. label[v] = the smallest vertex index of v's component, -1 for a vertex no usable face references.  The components are numbered
+ *      0 .. C - 1 in ascending label.  vertex_component int32 [n_vertices]: the number of v's component, -1 for an unreferenced vertex.
+ *      face_component int32 [n_faces]: the number of the component of the face's vertices, -1 for a face that is not usable.
+ *   4. the TABLE, int64 [C][GPNERF_COMPONENT_COLS] inside the workspace with a capacity of floor(n_vertices / 3) rows (a component has
+ *      at least three vertices) of which only the first C are defined: LABEL, VERTICES, EDGES (half the sum of the CSR degrees of the
+ *      component's vertices), FACES (usable faces), EULER = VERTICES - EDGES + FACES, BOUNDARY_VERTICES (the component's vertices flagged
+ *      GPNERF_VERTEX_BOUNDARY: on a boundary or non-manifold edge).
+ *   5. the stats, int64 [GPNERF_COMPONENT_STATS], every one written by the call: COMPONENTS = C; CLOSED_COMPONENTS (rows with
+ *      BOUNDARY_VERTICES == 0); LARGEST, the number of the component with the most FACES, a tie going to the lower number (the maximum
+ *      of the packed word FACES << 32 | ~number: the total order of the cube's largest component), -1 when C == 0; LARGEST_FACES,
+ *      LARGEST_VERTICES, LARGEST_EULER (that row's, 0 when C == 0); KEPT_COMPONENTS, KEPT_VERTICES, KEPT_FACES (the selection's).
+ *   6. SELECTION.  keep = GPNERF_COMPONENTS_KEEP_ALL: every component is kept; _KEEP_LARGEST: the component LARGEST; _KEEP_MIN_FACES:
+ *      those with FACES >= min_faces (min_faces >= 1; it is ignored by the other two).  The kept vertices are the REFERENCED vertices of
+ *      the kept components in ascending original index, the kept faces the USABLE faces of the kept components in ascending original
+ *      index, their indices renumbered.  An unreferenced vertex and an unusable face are always dropped: KEEP_ALL is "remove the
+ *      unreferenced vertices and the unusable faces".  The kept coordinates are copied bit for bit.
+ *   7. every output is a function of n_vertices and the SET of faces: labels, table and stats do not depend on the order of the faces,
+ *      on the launch geometry or on the arrival order; face_component and the emitted faces follow the given face order.  Only integer
+ *      atomics are used: the union-find's atomicMin (the final roots are the sets' minima whatever the order of the links), integer
+ *      sums, one packed 64-bit maximum; no float is computed.
+ * The genus of a component is (2 - EULER) / 2 when the component is closed, the mesh has no inconsistent and no non-manifold edge
+ * (gpnerf_mesh_adjacency's stats) and EULER is even; a pinched vertex (all of its edges manifold, but its link more than one cycle)
+ * is NOT detected and makes that figure wrong.
+ *
+ * gpnerf_mesh_components fills the workspace and sets stats (device).  Launches: an initialisation (parent[v] = the smaller of v and
+ * its smallest neighbour, the first entry of its CSR run; the table zeroed, the header); a lane per face (usable: unite (a, b) and
+ * (b, c) -- two read-only walks first, the linking union with its path compression only when they end at different roots); a lane per vertex behind that kernel boundary (flatten: plain
+ * loads, label = the root or -1, roots marked); a three-launch integer scan of the root marks (numbers, C); a lane per vertex
+ * (vertex_component; VERTICES, the degree and the boundary flag added to the component's row) and a lane per face (face_component;
+ * FACES) -- a wavefront whose active lanes share a component adds once per wavefront, the wavefronts of a workgroup that agree once
+ * per workgroup, so that a mesh of ONE component issues one add per counter and workgroup instead of one per lane on one address;
+ * a mixed wavefront adds once per distinct component among its lanes --; a lane per table row (EDGES halved, EULER, the closed count, the packed
+ * maximum, the rows of at least min_faces); a lane per vertex and face (keep marks); two scans (the new numbers); one lane (stats).
+ * Every launch first compares the adjacency's header words with n_vertices and n_faces: on a workspace that holds no finished
+ * adjacency of this mesh nothing is written to stats, labels, numbers or table, and the workspace's 64-bit word
+ * GPNERF_COMPONENTS_HDR_STATUS says GPNERF_COMPONENTS_NO_ADJACENCY (only that header and scan scratch inside the workspace are touched).
+ * gpnerf_mesh_components_emit writes the kept mesh: out_vertices float [n_out_vertices][3], out_faces int32 [n_out_faces][3],
+ * vertex_map int32 [n_vertices] (old -> new, -1 for a dropped vertex) or NULL, kept_vertices int32 [n_out_vertices] (new -> old: one
+ * index_select carries any per-vertex attribute over) or NULL.  The caller reads KEPT_VERTICES and KEPT_FACES (the one host read) and
+ * sizes the outputs; emit reads nothing back: its first launch compares n_vertices, n_faces and the two output sizes with those
+ * counted ON THE DEVICE; when they differ, or the workspace holds no finished count, nothing is written and the status word is
+ * GPNERF_COMPONENTS_MISMATCH (after a good emit: GPNERF_COMPONENTS_EMITTED).  Then a lane per vertex and a lane per face.
+ * workspace: gpnerf_mesh_components_workspace_bytes(n_vertices, n_faces) bytes (host arithmetic only, from the worst-case capacities,
+ * so that no host read is needed; 0 for what the calls refuse) = 256 + 4 a(4 nv) + 2 a(4 nf) + a(48 floor(nv / 3)) +
+ * a(8 ceil(max(nv, nf, 1) / 2048)), with a() rounding up to a multiple of 256: the header; label, vertex_component, the root numbers and
+ * the new vertex numbers; face_component and the new face numbers; the table; the scans' block sums.  gpnerf_mesh_components_layout
+ * (host only): offsets[GPNERF_COMPONENTS_LABEL / _VERTEX_COMPONENT / _FACE_COMPONENT / _TABLE] = the byte offsets of the four arrays
+ * inside the workspace, each a multiple of 256, so that a caller hands out views and copies nothing.
+ * GPNERF_E_ARG, before anything is launched: a null workspace, adjacency_workspace, stats or offsets; null faces with n_faces > 0;
+ * emit: null vertices with n_vertices > 0, a null out_vertices / out_faces whose size is > 0; a count that is negative or beyond the
+ * limits above; an unknown keep; min_faces < 1 with KEEP_MIN_FACES; a workspace or an adjacency workspace under its formula; emit:
+ * output sizes that are negative or exceed the input's. */
+#define GPNERF_COMPONENT_LABEL 0
+#define GPNERF_COMPONENT_VERTICES 1
+#define GPNERF_COMPONENT_EDGES 2
+#define GPNERF_COMPONENT_FACES 3
+#define GPNERF_COMPONENT_EULER 4
+#define GPNERF_COMPONENT_BOUNDARY_VERTICES 5
+#define GPNERF_COMPONENT_COLS 6
+#define GPNERF_COMPONENTS_COMPONENTS 0
+#define GPNERF_COMPONENTS_CLOSED_COMPONENTS 1
+#define GPNERF_COMPONENTS_LARGEST 2
+#define GPNERF_COMPONENTS_LARGEST_FACES 3
+#define GPNERF_COMPONENTS_LARGEST_VERTICES 4
+#define GPNERF_COMPONENTS_LARGEST_EULER 5
+#define GPNERF_COMPONENTS_KEPT_COMPONENTS 6
+#define GPNERF_COMPONENTS_KEPT_VERTICES 7
+#define GPNERF_COMPONENTS_KEPT_FACES 8
+#define GPNERF_COMPONENT_STATS 9
+#define GPNERF_COMPONENTS_KEEP_ALL 0
+#define GPNERF_COMPONENTS_KEEP_LARGEST 1
+#define GPNERF_COMPONENTS_KEEP_MIN_FACES 2
+#define GPNERF_COMPONENTS_LABEL 0
+#define GPNERF_COMPONENTS_VERTEX_COMPONENT 1
+#define GPNERF_COMPONENTS_FACE_COMPONENT 2
+#define GPNERF_COMPONENTS_TABLE 3
+#define GPNERF_COMPONENTS_HDR_STATUS 3
+#define GPNERF_COMPONENTS_COUNTING 1
+#define GPNERF_COMPONENTS_COUNTED 2
+#define GPNERF_COMPONENTS_EMITTED 3
+#define GPNERF_COMPONENTS_MISMATCH 4
+#define GPNERF_COMPONENTS_NO_ADJACENCY 5
+size_t gpnerf_mesh_components_workspace_bytes(int64_t n_vertices, int64_t n_faces);
+int gpnerf_mesh_components_layout(int64_t n_vertices, int64_t n_faces, int64_t* offsets);
+int gpnerf_mesh_components(const int32_t* faces, int64_t n_faces, int64_t n_vertices, const void* adjacency_workspace, size_t adjacency_bytes,
+                           int32_t keep, int64_t min_faces, void* workspace, size_t workspace_bytes, int64_t* stats, void* stream);
+int gpnerf_mesh_components_emit(const float* vertices, int64_t n_vertices, const int32_t* faces, int64_t n_faces, void* workspace,
+                                size_t workspace_bytes, int64_t n_out_vertices, int64_t n_out_faces, float* out_vertices, int32_t* out_faces,
+                                int32_t* vertex_map, int32_t* kept_vertices, void* stream);
 
 /* ---- voxelising a mesh (gpnerf_voxelize.hip): the SOLID occupancy of a triangle mesh on a lattice, packed one bit per lattice point,
  * the counts that give its volume, and the small operations on packed cubes that go with it (from a density cube, back to a float
