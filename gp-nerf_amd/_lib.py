@@ -170,6 +170,20 @@ VOXEL_RULES = {"parity": VOXEL_PARITY, "nonzero": VOXEL_NONZERO}
 VOXEL_STATS = ("used", "skipped_vertex", "skipped_area", "crossings", "open_columns", "occupied")
 VOXEL_A, VOXEL_B, VOXEL_BOTH, VOXEL_EITHER, VOXEL_COUNTS = range(5)
 VOXEL_MAX_POINTS = 1 << 28
+# gpnerf_conv_variant's row and its kernel families (include/gpnerf_hip.h GPNERF_CONV_*)
+CONV_VARIANT = ("family", "cot", "rw", "ksplit", "cat", "tiles", "tile_h", "tile_w")
+CONV_FAMILIES = ("REFUSED", "DIRECT_1X1", "DIRECT_NARROW3", "TILED_S1", "TILED_S2", "STEM")
+
+
+def conv_variant(n, h, w, cin_a, cin_b, cout, ks, stride):
+    """gpnerf_conv_variant as a dict (host arithmetic only): which kernel the convolution calls launch for this shape; the family
+    by name, "REFUSED" for a shape they do not take."""
+    row = (C.c_int32 * len(CONV_VARIANT))()
+    lib().gpnerf_conv_variant(n, h, w, cin_a, cin_b, cout, ks, stride, row)
+    v = dict(zip(CONV_VARIANT, row))
+    v["family"] = CONV_FAMILIES[v["family"]]
+    return v
+
 
 # every symbol include/gpnerf_hip.h declares: (restype, argtypes)
 SYMBOLS = {
@@ -201,6 +215,7 @@ SYMBOLS = {
     "gpnerf_conv_packed_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
     "gpnerf_conv_pack_weight": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "gpnerf_conv_out_tiles": (C.c_int32, [C.c_int32] * 5),
+    "gpnerf_conv_variant": (C.c_int, [C.c_int32] * 8 + [C.POINTER(C.c_int32)]),
     "gpnerf_conv2d_nhwc": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
                                      C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
     "gpnerf_conv2d_nhwc_exact": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,

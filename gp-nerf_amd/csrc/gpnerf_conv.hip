@@ -193,7 +193,7 @@ struct ConvArgs {
     // Range flag of the split-f16 form, or nullptr: ONE word that is set to 1 when an operand left the f16 range.  An activation
     // with |16 x| >= 65520 (or a weight with |4096 w| >= 65520) becomes an f16 infinity when it is split, its lo half the opposite
     // infinity, and every accumulator it meets ends up NaN -- nothing is silently wrong, the result is loudly non-finite.  That is
-    // looked for where it costs nothing: the InstanceNorm table's sums (finalize_if_last: a non-finite sum or sum of squares of any
+    // looked for where it costs nothing: the InstanceNorm table's sums (finalize_if_last: a non-finite sum or M2 of any
     // channel), and the accumulators themselves in a convolution with no norm behind it.  The host then runs the layer chain
     // again in the exact fp32 form (exact = 1).  A non-finite INPUT sets the flag too (the exact form then returns
     // what fp32 arithmetic makes of it).  The word is only ever written with 1; the caller zeroes it.
@@ -221,10 +221,13 @@ DEV Moments merge(const Moments& x, const Moments& y) {
 // Last-arriving workgroup of (image n, channel group ct0 .. ct0 + COT): every workgroup has written its tile's (sum, sum of squares,
 // M2); the one whose atomic ticket is the last adds the tiles of its COT * 32 channels in double, in tile order (so the result does
 // not depend on which workgroup that is), and writes mean / gamma * rstd / beta.  256 threads: 256 / (COT * 32) tile lanes per channel.
-// The variance is E[y^2] - mean^2 from the float32 tile sums where that is well conditioned (var >= 1e-3 mean^2: at most three of
-// float32's seven digits cancel), and otherwise assembled from the tiles' sums of squares ABOUT THEIR MEANS (tile_stats) by Chan's
-// pairwise merge: on a channel that is nearly constant over the image (a one-hot source image behind a large InstanceNorm scale)
-// the difference cancels to a few roundings of E[y^2] -- measured 3e-4 of the output range on such a frame, 1e-6 with the merge.
+// The variance is assembled from the tiles' sums of squares ABOUT THEIR MEANS (tile_stats' M2) and the spread of the tile means,
+// sum_k s_k^2 / n_k - (sum s)^2 / hw, in one pass: a rounding of a float32 tile sum costs |mean| / sigma of its size there, where
+// E[y^2] - mean^2 from float32 sums of squares costs (mean / sigma)^2 (an output of a few pixels, where many channels have a mean of
+// several sigma, was 3e-5 off the stand-alone operator: tests/test_gpu_conv_variants.py).  Where even that is ill conditioned
+// (var < 1e-3 mean^2) the tiles are merged pairwise as Chan et al.: on a channel that is nearly constant over the image (a one-hot
+// source image behind a large InstanceNorm scale) the difference cancels to a few roundings -- measured 3e-4 of the output range
+// on such a frame with E[y^2] - mean^2, 1e-6 with the merge.
 template <int COT>
 DEV void finalize_if_last(const ConvArgs& a, const int n, const int ct0, const int ntiles, double* red /* [3][256] doubles of LDS */) {
     // No agent-scope fence here: a release fence would write back this XCD's whole L2 (the convolution's output has just
@@ -248,33 +251,39 @@ DEV void finalize_if_last(const ConvArgs& a, const int n, const int ct0, const i
     if (!s_last) return;
     constexpr int NCH = COT * 32, LANES = 256 / NCH;
     const int ch = threadIdx.x % NCH, kl = threadIdx.x / NCH, co = 32 * ct0 + ch;
-    double ts = 0, tq = 0;
+    double ts = 0, tm = 0, tb = 0;                              // of this lane's tiles: the sums, their M2, (sum)^2 / (pixels)
     if (co < a.Cout)
         for (int k0 = kl; k0 < ntiles; k0 += 8 * LANES) {     // eight tiles' loads in flight, added in tile order
-            float vs[8], vq[8];
+            float vs[8], vm[8];
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
                 const int k = k0 + j * LANES;
                 const float* o = a.stats + (((size_t)n * ntiles + (k < ntiles ? k : kl)) * a.Cout + co) * 3;
                 vs[j] = __hip_atomic_load(o, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                vq[j] = __hip_atomic_load(o + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                vm[j] = __hip_atomic_load(o + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
 #pragma unroll
             for (int j = 0; j < 8; ++j)
-                if (k0 + j * LANES < ntiles) { ts += (double)vs[j]; tq += (double)vq[j]; }
+                if (k0 + j * LANES < ntiles) {
+                    const double sk = (double)vs[j], cnt = (double)tile_pixels(a, k0 + j * LANES);
+                    ts += sk; tm += (double)vm[j]; tb += cnt > 0 ? sk * sk / cnt : 0.0;
+                }
         }
     red[threadIdx.x] = ts;
-    red[256 + threadIdx.x] = tq;
+    red[256 + threadIdx.x] = tm;
+    red[512 + threadIdx.x] = tb;
     __syncthreads();
     __shared__ unsigned s_ill;
     if (threadIdx.x == 0) s_ill = 0u;
     const double hw = (double)a.Ho * (double)a.Wo;
-    double mean = 0, var = 0, sum_s = 0, sum_q = 0;
+    double mean = 0, var = 0, sum_s = 0, sum_m = 0, sum_b = 0;
     if (kl == 0 && co < a.Cout) {
 #pragma unroll
-        for (int k = 0; k < LANES; ++k) { sum_s += red[k * NCH + ch]; sum_q += red[256 + k * NCH + ch]; }
+        for (int k = 0; k < LANES; ++k) { sum_s += red[k * NCH + ch]; sum_m += red[256 + k * NCH + ch]; sum_b += red[512 + k * NCH + ch]; }
         mean = sum_s / hw;
-        var = sum_q / hw - mean * mean;                         // biased variance, as InstanceNorm2d normalises with
+        // biased variance, as InstanceNorm2d normalises with: the squares within the tiles (about their own means) + those of the tile
+        // means about the image's, sum_k n_k (mean_k - mean)^2 = sum_k s_k^2 / n_k - (sum s)^2 / hw in double
+        var = (sum_m + (sum_b - sum_s * mean)) / hw;
     }
     __syncthreads();
     const bool ill = kl == 0 && co < a.Cout && !(var >= 1e-3 * mean * mean);
@@ -308,8 +317,11 @@ DEV void finalize_if_last(const ConvArgs& a, const int n, const int ct0, const i
         a.out_tab[((size_t)n * 3 + 0) * a.Cout + co] = (float)mean;
         a.out_tab[((size_t)n * 3 + 1) * a.Cout + co] = g;
         a.out_tab[((size_t)n * 3 + 2) * a.Cout + co] = a.beta[co];
-        // an operand beyond the f16 range (ConvArgs::flag): the channel's sums are non-finite
-        if (a.flag && !(fabs(sum_s) < __builtin_inf() && fabs(sum_q) < __builtin_inf())) __hip_atomic_store(a.flag, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        // an operand beyond the f16 range (ConvArgs::flag): the channel's sums are non-finite.  (The M2 where the sum of squares was
+        // looked at before the variance was taken from it: an infinite or NaN output makes both NaN.  Intended difference: a FINITE
+        // output beyond 1.8e19, whose square overflows float32, raised the flag through the sum of squares and need not through the
+        // M2 -- such a value is no sign of an operand out of the f16 range, which is all the flag stands for.)
+        if (a.flag && !(fabs(sum_s) < __builtin_inf() && fabs(sum_m) < __builtin_inf())) __hip_atomic_store(a.flag, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     }
     if (threadIdx.x == 0) __hip_atomic_store(&a.counters[(size_t)n * gridDim.z + blockIdx.z], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // ready for the next launch
 }
@@ -1212,15 +1224,67 @@ __global__ void __launch_bounds__(WAVES * 64) conv2d_exact_kernel(const ExactArg
     }
 }
 
+// ---- the launch choice, in one place ----------------------------------------------------------------------------------------
+// Which kernel family, which instantiation (COT output tiles per workgroup, RW rows per wave, KSPLIT halves of the channel blocks)
+// and which workgroup tile a convolution takes: the launchers below, gpnerf_conv_out_tiles() and the host-only query
+// gpnerf_conv_variant() all read it from here.
+struct ConvVariant { int family, cot, rw, ksplit, tiles, tile_h, tile_w; };
+
+// rows per wave of the 3x3 kernel for an (Ho x Wo) output: images of at most sixteen 8-row tiles (64 x 64 and smaller) take 4-row tiles (threshold swept: 8: 1.165, 16: 1.147, 64: 1.203 ms per frame).
+// A function of the output size ALONE, so that gpnerf_conv_out_tiles() can tell the caller how many tile rows the statistics have.
+int conv3x3_rows(int ho, int wo) {
+    return ((ho + 7) / 8) * ((wo + TW - 1) / TW) <= 16 && ho > 4 ? 1 : 2;
+}
+
+// family and workgroup tile: a function of the output size, the kernel and whether the input is narrow (cin < 8), nothing else
+ConvVariant conv_tiling(int ho, int wo, int cin, int ks, int stride) {
+    ConvVariant v{GPNERF_CONV_DIRECT_1X1, 1, 0, 1, 0, 0, WAVES * PT * 32};
+    if (ks == 3 && stride == 1 && cin >= 8) { v.family = GPNERF_CONV_TILED_S1; v.rw = conv3x3_rows(ho, wo); }
+    else if (ks == 3 && stride == 2 && cin >= 8) { v.family = GPNERF_CONV_TILED_S2; v.rw = 1; }
+    else if (ks == 7 && stride == 2 && cin <= 4) { v.family = GPNERF_CONV_STEM; v.rw = STEM_TH / WAVES; }
+    else if (ks == 3) v.family = GPNERF_CONV_DIRECT_NARROW3;
+    if (v.rw) {
+        v.tile_h = tile_rows(v.rw); v.tile_w = TW;
+        v.tiles = ((ho + v.tile_h - 1) / v.tile_h) * ((wo + TW - 1) / TW);
+    } else v.tiles = (ho * wo + v.tile_w - 1) / v.tile_w;            // tile_h = 0: tile_w consecutive pixels
+    return v;
+}
+
+// ... and the instantiation, which also looks at the batch and the channel counts (CB 16-channel input blocks, CT 32-channel output tiles)
+ConvVariant conv_variant(int N, int ho, int wo, int cin, int CB, int CT, int ks, int stride, bool cat) {
+    ConvVariant v = conv_tiling(ho, wo, cin, ks, stride);
+    switch (v.family) {
+    case GPNERF_CONV_DIRECT_1X1:
+    case GPNERF_CONV_DIRECT_NARROW3:
+        // output tiles per workgroup: as many as still leave the chip a full round of workgroups (weights read once per COT tiles)
+        v.cot = 4;
+        while (v.cot > 1 && (CT % v.cot != 0 || (long)v.tiles * N * (CT / v.cot) < 256)) v.cot >>= 1;
+        break;
+    case GPNERF_CONV_TILED_S1:
+        // one 32-channel output tile per workgroup everywhere: with the weights in registers and 54 KB of LDS two workgroups share a CU,
+        // and one's staging runs under the other's MFMAs (two tiles per workgroup: 1.19 -> 1.38 ms per frame).
+        // A grid of at most one workgroup per CU (the 32 x 32 stage: 192): the channel blocks are split over the two halves of an
+        // eight-wave workgroup (encoder 1.097 -> 1.030 ms; at <= 400 workgroups, which takes in the 64 x 64 stage: 1.087)
+        if (!cat && v.rw == 1 && CB % 2 == 0 && CB >= 4 && (long)v.tiles * N * CT <= 256) v.ksplit = 2;
+        break;
+    case GPNERF_CONV_STEM:
+        v.cot = CT % 2 == 0 ? 2 : 1;
+        break;
+    default: break;
+    }
+    return v;
+}
+ConvVariant conv_variant(const ConvArgs& a, int N, int ks, int stride) {
+    return conv_variant(N, a.Ho, a.Wo, a.Cin, a.CB, a.CT, ks, stride, a.x2 != nullptr);
+}
+
 template <int KS, int STRIDE, bool NARROW>
 int launch_conv(const ConvArgs& a, int N, void* stream) {
-    const int tiles = (a.Ho * a.Wo + WAVES * PT * 32 - 1) / (WAVES * PT * 32);
-    // output tiles per workgroup: as many as still leave the chip a full round of workgroups (weights read once per COT tiles)
-    int cot = 4;
-    while (cot > 1 && (a.CT % cot != 0 || (long)tiles * N * (a.CT / cot) < 256)) cot >>= 1;
-    const dim3 grid((unsigned)tiles, (unsigned)N, (unsigned)(a.CT / cot));
+    const ConvVariant v = conv_variant(a, N, KS, STRIDE);
+    const int cot = v.cot;
+    const dim3 grid((unsigned)v.tiles, (unsigned)N, (unsigned)(a.CT / cot));
     ConvArgs g = a;
-    g.tile_h = 0; g.tile_w = WAVES * PT * 32;
+    g.tile_h = v.tile_h; g.tile_w = v.tile_w;
     const ConvArgs& a2 = g;
     if (a.exact) {
         if (cot == 4) hipLaunchKernelGGL((conv2d_nhwc_kernel<KS, STRIDE, 4, NARROW, true>), grid, dim3(WAVES * 64), 0, S_(stream), a2);
@@ -1234,16 +1298,10 @@ int launch_conv(const ConvArgs& a, int N, void* stream) {
     return launch_status();
 }
 
-// rows per wave of the 3x3 kernel for an (Ho x Wo) output: images of at most sixteen 8-row tiles (64 x 64 and smaller) take 4-row tiles (threshold swept: 8: 1.165, 16: 1.147, 64: 1.203 ms per frame).
-// A function of the output size ALONE, so that gpnerf_conv_out_tiles() can tell the caller how many tile rows the statistics have.
-int conv3x3_rows(int ho, int wo) {
-    return ((ho + 7) / 8) * ((wo + TW - 1) / TW) <= 16 && ho > 4 ? 1 : 2;
-}
-
 template <int COT, int RW, int STRIDE = 1, int KSPLIT = 1, bool CAT = false, bool EXACT = false>
-int launch_conv3x3_as(const ConvArgs& a, int N, int tiles, void* stream) {
+int launch_conv3x3_as(const ConvArgs& a, int N, const ConvVariant& v, void* stream) {
     if constexpr (!EXACT) {
-        if (a.exact) return launch_conv3x3_as<COT, RW, STRIDE, KSPLIT, CAT, true>(a, N, tiles, stream);
+        if (a.exact) return launch_conv3x3_as<COT, RW, STRIDE, KSPLIT, CAT, true>(a, N, v, stream);
     }
     // two patch buffers per K half (+ the input norm's table); never less than what the epilogue's reductions use (tile sums,
     // finalize: 16 KB; the halves' exchange: RW * COT * 16 KB behind them)
@@ -1253,48 +1311,56 @@ int launch_conv3x3_as(const ConvArgs& a, int N, int tiles, void* stream) {
     const void* fn = reinterpret_cast<const void*>(&conv3x3_s1_nhwc_kernel<COT, RW, STRIDE, KSPLIT, CAT, EXACT>);
     // > 64 KB of dynamic LDS is an opt-in per device; setting it is cheap, so it is simply set before every launch
     if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return GPNERF_E_DEVICE;
-    const dim3 grid((unsigned)tiles, (unsigned)N, (unsigned)(a.CT / COT));
+    const dim3 grid((unsigned)v.tiles, (unsigned)N, (unsigned)(a.CT / COT));
     ConvArgs g = a;
-    g.tile_h = tile_rows(RW); g.tile_w = TW;
+    g.tile_h = v.tile_h; g.tile_w = v.tile_w;
     hipLaunchKernelGGL((conv3x3_s1_nhwc_kernel<COT, RW, STRIDE, KSPLIT, CAT, EXACT>), grid, dim3(WAVES * KSPLIT * 64), lds, S_(stream), g);
     return launch_status();
 }
 
 int launch_conv3x3(const ConvArgs& a, int N, void* stream) {
-    const int rw = conv3x3_rows(a.Ho, a.Wo), th = tile_rows(rw);
-    const int tiles = ((a.Ho + th - 1) / th) * ((a.Wo + TW - 1) / TW);
-    // one 32-channel output tile per workgroup everywhere: with the weights in registers and 54 KB of LDS two workgroups share a CU,
-    // and one's staging runs under the other's MFMAs (two tiles per workgroup: 1.19 -> 1.38 ms per frame)
-    if (a.x2) return rw == 1 ? launch_conv3x3_as<1, 1, 1, 1, true>(a, N, tiles, stream) : launch_conv3x3_as<1, 2, 1, 1, true>(a, N, tiles, stream);
-    // a grid of at most one workgroup per CU (the 32 x 32 stage: 192): the channel blocks are split over the two halves of an
-    // eight-wave workgroup (encoder 1.097 -> 1.030 ms; at <= 400 workgroups, which takes in the 64 x 64 stage: 1.087)
-    if (rw == 1 && a.CB % 2 == 0 && a.CB >= 4 && (long)tiles * N * a.CT <= 256)
-        return launch_conv3x3_as<1, 1, 1, 2>(a, N, tiles, stream);
-    return rw == 1 ? launch_conv3x3_as<1, 1>(a, N, tiles, stream) : launch_conv3x3_as<1, 2>(a, N, tiles, stream);
+    const ConvVariant v = conv_variant(a, N, 3, 1);
+    if (a.x2) return v.rw == 1 ? launch_conv3x3_as<1, 1, 1, 1, true>(a, N, v, stream) : launch_conv3x3_as<1, 2, 1, 1, true>(a, N, v, stream);
+    if (v.ksplit == 2) return launch_conv3x3_as<1, 1, 1, 2>(a, N, v, stream);
+    return v.rw == 1 ? launch_conv3x3_as<1, 1>(a, N, v, stream) : launch_conv3x3_as<1, 2>(a, N, v, stream);
 }
 
 // 3x3 stride 2 (the entry of every residual stage): the same kernel on 4-row output tiles, whose input patch is 9 x 65 pixels
 int launch_conv3x3_s2(const ConvArgs& a, int N, void* stream) {
-    const int tiles = ((a.Ho + 3) / 4) * ((a.Wo + TW - 1) / TW);
-    return launch_conv3x3_as<1, 1, 2>(a, N, tiles, stream);
+    return launch_conv3x3_as<1, 1, 2>(a, N, conv_variant(a, N, 3, 2), stream);
 }
 
 template <int COT, bool EXACT = false>
-int launch_stem_as(const ConvArgs& a, int N, void* stream) {
+int launch_stem_as(const ConvArgs& a, int N, const ConvVariant& v, void* stream) {
     if constexpr (!EXACT) {
-        if (a.exact) return launch_stem_as<COT, true>(a, N, stream);
+        if (a.exact) return launch_stem_as<COT, true>(a, N, v, stream);
     }
-    const int tiles = ((a.Ho + STEM_TH - 1) / STEM_TH) * ((a.Wo + TW - 1) / TW);
     const size_t lds = 2 * (size_t)STEM_PLANE + (size_t)STEM_CHUNKS * COT * STEP_BYTES;
     const void* fn = reinterpret_cast<const void*>(&conv7x7_s2_stem_kernel<COT, EXACT>);
     if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return GPNERF_E_DEVICE;
-    const dim3 grid((unsigned)tiles, (unsigned)N, (unsigned)(a.CT / COT));
+    const dim3 grid((unsigned)v.tiles, (unsigned)N, (unsigned)(a.CT / COT));
     ConvArgs g = a;
-    g.tile_h = STEM_TH; g.tile_w = TW;
+    g.tile_h = v.tile_h; g.tile_w = v.tile_w;
     hipLaunchKernelGGL((conv7x7_s2_stem_kernel<COT, EXACT>), grid, dim3(WAVES * 64), lds, S_(stream), g);
     return launch_status();
 }
-int launch_stem(const ConvArgs& a, int N, void* stream) { return a.CT % 2 == 0 ? launch_stem_as<2>(a, N, stream) : launch_stem_as<1>(a, N, stream); }
+int launch_stem(const ConvArgs& a, int N, void* stream) {
+    const ConvVariant v = conv_variant(a, N, 7, 2);
+    return v.cot == 2 ? launch_stem_as<2>(a, N, v, stream) : launch_stem_as<1>(a, N, v, stream);
+}
+
+// What gpnerf_conv2d_norm_nhwc accepts of a convolution's shape (cat = false; cin_b is not looked at) and gpnerf_conv2d_norm_cat_nhwc
+// of a concatenating one (cat = true: both parts whole 16-channel blocks, neither empty)
+bool conv_shape_ok(bool cat, int n, int h, int w, int cin_a, int cin_b, int cout, int ks, int stride) {
+    if (n < 0 || cout < 4 || (cout & 3)) return false;
+    if (cat) return ks == 3 && stride == 1 && h >= 2 && w >= 2 && cin_a >= 16 && !(cin_a & 15) && cin_b >= 16 && !(cin_b & 15);
+    if (h < 1 || w < 1 || cin_a < 1) return false;
+    if ((ks != 1 && ks != 3 && ks != 7) || (stride != 1 && stride != 2)) return false;
+    if (h <= ks / 2 || w <= ks / 2) return false;                        // reflection needs pad < size
+    if (cin_a < 8) return (ks == 7 && stride == 2 && cin_a <= 4) || (ks == 3 && stride == 1);   // (7x7 on 5 .. 7 channels: not built)
+    if (cin_a & 15) return false;                                        // full 16-channel chunks, 32-byte aligned loads
+    return ks != 7;
+}
 
 }  // namespace
 
@@ -1328,10 +1394,28 @@ int gpnerf_conv_pack_weight(const float* weight, int32_t cout, int32_t cin, int3
 int32_t gpnerf_conv_out_tiles(int32_t h, int32_t w, int32_t cin, int32_t ks, int32_t stride) {
     if (h < 1 || w < 1 || (ks != 1 && ks != 3 && ks != 7) || (stride != 1 && stride != 2)) return 0;
     const int pad = ks / 2, ho = (h + 2 * pad - ks) / stride + 1, wo = (w + 2 * pad - ks) / stride + 1;
-    if (ks == 3 && stride == 1 && cin >= 8) { const int th = tile_rows(conv3x3_rows(ho, wo)); return ((ho + th - 1) / th) * ((wo + TW - 1) / TW); }
-    if (ks == 3 && stride == 2 && cin >= 8) return ((ho + 3) / 4) * ((wo + TW - 1) / TW);
-    if (ks == 7 && stride == 2 && cin <= 4) return ((ho + STEM_TH - 1) / STEM_TH) * ((wo + TW - 1) / TW);
-    return (ho * wo + WAVES * PT * 32 - 1) / (WAVES * PT * 32);
+    return conv_tiling(ho, wo, cin, ks, stride).tiles;
+}
+
+int gpnerf_conv_variant(int32_t n, int32_t h, int32_t w, int32_t cin_a, int32_t cin_b, int32_t cout, int32_t ks, int32_t stride,
+                        int32_t* variant) {
+    if (!variant) return GPNERF_E_ARG;
+    for (int i = 0; i < GPNERF_CONV_VARIANT_INTS; ++i) variant[i] = 0;
+    variant[GPNERF_CONV_FAMILY] = GPNERF_CONV_REFUSED;
+    if (cin_b < 0 || !conv_shape_ok(cin_b != 0, n, h, w, cin_a, cin_b, cout, ks, stride)) return GPNERF_E_ARG;
+    const int pad = ks / 2, ho = (h + 2 * pad - ks) / stride + 1, wo = (w + 2 * pad - ks) / stride + 1;
+    const int cin = cin_a + cin_b;
+    const int CB = cin < 8 ? (ks * ks * cin + 15) / 16 : (cin + 15) / 16, CT = (cout + 31) / 32;
+    const ConvVariant v = conv_variant(n, ho, wo, cin, CB, CT, ks, stride, cin_b != 0);
+    variant[GPNERF_CONV_FAMILY] = v.family;
+    variant[GPNERF_CONV_COT] = v.cot;
+    variant[GPNERF_CONV_RW] = v.rw;
+    variant[GPNERF_CONV_KSPLIT] = v.ksplit;
+    variant[GPNERF_CONV_CAT] = cin_b != 0;
+    variant[GPNERF_CONV_TILES] = v.tiles;
+    variant[GPNERF_CONV_TILE_H] = v.tile_h;
+    variant[GPNERF_CONV_TILE_W] = v.tile_w;
+    return GPNERF_OK;
 }
 
 int gpnerf_conv2d_norm_cat_nhwc(const float* x, int32_t cin_a, const float* x_b, int32_t cin_b, int32_t n, int32_t h, int32_t w,
@@ -1340,8 +1424,7 @@ int gpnerf_conv2d_norm_cat_nhwc(const float* x, int32_t cin_a, const float* x_b,
                                 void* stream) {
     if (n == 0) return GPNERF_OK;
     if (exact < 0 || exact > 1) return GPNERF_E_ARG;
-    if (!x || !x_b || !packed || !y || n < 0 || h < 2 || w < 2 || cin_a < 16 || (cin_a & 15) || cin_b < 16 || (cin_b & 15) || cout < 4 || (cout & 3))
-        return GPNERF_E_ARG;
+    if (!x || !x_b || !packed || !y || !conv_shape_ok(true, n, h, w, cin_a, cin_b, cout, 3, 1)) return GPNERF_E_ARG;
     if (out_table && (!tile_stats || !gamma || !beta || !counters)) return GPNERF_E_ARG;
     ConvArgs a;
     a.x = x; a.x2 = x_b; a.CinA = cin_a; a.packed = reinterpret_cast<const uint16_t*>(packed); a.bias = bias; a.y = y; a.stats = tile_stats;
@@ -1358,12 +1441,9 @@ int gpnerf_conv2d_norm_nhwc(const float* x, int32_t n, int32_t h, int32_t w, int
                             int32_t exact, void* stream) {
     if (n == 0) return GPNERF_OK;
     if (exact < 0 || exact > 1) return GPNERF_E_ARG;
-    if (!x || !packed || !y || n < 0 || h < 1 || w < 1 || cin < 1 || cout < 4 || (cout & 3)) return GPNERF_E_ARG;
-    if ((ks != 1 && ks != 3 && ks != 7) || (stride != 1 && stride != 2)) return GPNERF_E_ARG;
+    if (!x || !packed || !y || !conv_shape_ok(false, n, h, w, cin, 0, cout, ks, stride)) return GPNERF_E_ARG;
     const int pad = ks / 2;
-    if (h <= pad || w <= pad) return GPNERF_E_ARG;                       // reflection needs pad < size
     const bool narrow = cin < 8;
-    if (!narrow && (cin & 15)) return GPNERF_E_ARG;                       // full 16-channel chunks, 32-byte aligned loads
     if (in_table && (narrow || ks == 7)) return GPNERF_E_ARG;                       // wide 3x3 (while staging) and 1x1 (while splitting) only
     if (in_table && (in_act < 0 || in_act > 1 || cin > 1024)) return GPNERF_E_ARG;
     if (out_table && (!tile_stats || !gamma || !beta || !counters)) return GPNERF_E_ARG;
@@ -1374,17 +1454,13 @@ int gpnerf_conv2d_norm_nhwc(const float* x, int32_t n, int32_t h, int32_t w, int
     a.CB = narrow ? (ks * ks * cin + 15) / 16 : (cin + 15) / 16; a.CT = (cout + 31) / 32;
     a.in_tab = in_table; a.in_act = in_act; a.out_tab = out_table; a.gamma = gamma; a.beta = beta; a.eps = eps; a.counters = counters;
     a.flag = exact ? nullptr : range_flag; a.exact = exact;
-    if (narrow) {
-        if (ks == 7 && stride == 2 && cin <= 4) return launch_stem(a, n, stream);
-        if (ks == 7) return GPNERF_E_ARG;                                  // (7x7 on 5 .. 7 channels: not built)
-        if (ks == 3 && stride == 1) return launch_conv<3, 1, true>(a, n, stream);
-        return GPNERF_E_ARG;
+    switch (conv_tiling(a.Ho, a.Wo, cin, ks, stride).family) {
+    case GPNERF_CONV_STEM: return launch_stem(a, n, stream);
+    case GPNERF_CONV_DIRECT_NARROW3: return launch_conv<3, 1, true>(a, n, stream);
+    case GPNERF_CONV_TILED_S1: return launch_conv3x3(a, n, stream);
+    case GPNERF_CONV_TILED_S2: return launch_conv3x3_s2(a, n, stream);
+    default: return stride == 1 ? launch_conv<1, 1, false>(a, n, stream) : launch_conv<1, 2, false>(a, n, stream);
     }
-    if (ks == 3 && stride == 1) return launch_conv3x3(a, n, stream);
-    if (ks == 3 && stride == 2) return launch_conv3x3_s2(a, n, stream);
-    if (ks == 1 && stride == 1) return launch_conv<1, 1, false>(a, n, stream);
-    if (ks == 1 && stride == 2) return launch_conv<1, 2, false>(a, n, stream);
-    return GPNERF_E_ARG;
 }
 
 int gpnerf_conv2d_nhwc(const float* x, int32_t n, int32_t h, int32_t w, int32_t cin, const void* packed, const float* bias,

@@ -1219,8 +1219,9 @@ int gpnerf_vertex_attention(const float* q, const float* kv, const float* w_qs, 
  *   bytes; re-pack when the parameter changes); bias: [cout] or NULL.  y: [N][Ho][Wo][cout], Ho = (H + 2 (ks/2) - ks) / stride + 1.
  *   tile_stats: NULL, or [N][gpnerf_conv_out_tiles()][cout][3] floats that receive every workgroup tile's per-channel sum, sum of
  *   squares, and M2 (sum of squares about the tile's own mean) of the outputs -- the statistics the InstanceNorm behind the
- *   convolution needs, without re-reading y.  out_table below takes the variance as E[y^2] - mean^2 from the sums where that is
- *   well conditioned and from the M2's (merged as Chan et al.) on a channel whose values are nearly constant over the image.
+ *   convolution needs, without re-reading y.  out_table below takes the variance from the M2's and the spread of the tiles' means
+ *   (sum s^2 / n - (sum s)^2 / hw, in double), and merges the tiles pairwise as Chan et al. on a channel whose values are nearly
+ *   constant over the image.
  * instance_norm_act_nhwc = act(InstanceNorm2d(x; gamma, beta, eps, biased variance, no running statistics) [+ residual]),
  *   act 0 none / 1 ReLU / 2 ELU (UNet.py:38-53,117-120,180-183); statistics from a double-precision pass over x, added up in a
  *   fixed order (deterministic): the stand-alone operator, what the fused tables of conv2d_norm_nhwc are tested against;
@@ -1250,7 +1251,34 @@ int gpnerf_vertex_attention(const float* q, const float* kv, const float* w_qs, 
  * conv2d_nhwc_exact = the same nn.Conv2d on fp32 operands (v_mfma_f32_32x32x2_f32, an fp32 FMA chain per output, any odd ks,
  *   any stride, any channel counts), from the PyTorch weight [cout][cin][ks][ks] as it is, one scalar load per operand: the
  *   independent restatement the tests hold the fused exact = 1 form against (and a way to run shapes the fused kernels do not
- *   cover); ~20x slower, not on the encoder's path. */
+ *   cover); ~20x slower, not on the encoder's path.
+ * conv_variant = which kernel a convolution call launches, for tools and tests.  Host arithmetic only, nothing is launched; the
+ *   launchers and gpnerf_conv_out_tiles() read their choice from the same function.  n, h, w, cout, ks, stride as for
+ *   conv2d_norm_nhwc with cin = cin_a and cin_b = 0, or as for conv2d_norm_cat_nhwc (cin_b > 0; ks = 3, stride = 1).
+ *   variant: host, GPNERF_CONV_VARIANT_INTS int32 -- [GPNERF_CONV_FAMILY] the kernel family (GPNERF_CONV_DIRECT_1X1 ...),
+ *   [GPNERF_CONV_COT] 32-channel output tiles per workgroup, [GPNERF_CONV_RW] output rows per wave of the tiled kernels (0: the
+ *   direct kernel, which tiles consecutive pixels), [GPNERF_CONV_KSPLIT] halves the channel blocks are split over,
+ *   [GPNERF_CONV_CAT] 1 for the concatenating form, [GPNERF_CONV_TILES] workgroup tiles per image (= gpnerf_conv_out_tiles()),
+ *   [GPNERF_CONV_TILE_H], [GPNERF_CONV_TILE_W] the workgroup's tile of output pixels (tile_h = 0: tile_w consecutive pixels).
+ *   Returns GPNERF_E_ARG, with the family GPNERF_CONV_REFUSED, for every shape the convolution calls refuse. */
+#define GPNERF_CONV_FAMILY 0
+#define GPNERF_CONV_COT 1
+#define GPNERF_CONV_RW 2
+#define GPNERF_CONV_KSPLIT 3
+#define GPNERF_CONV_CAT 4
+#define GPNERF_CONV_TILES 5
+#define GPNERF_CONV_TILE_H 6
+#define GPNERF_CONV_TILE_W 7
+#define GPNERF_CONV_VARIANT_INTS 8
+/* [GPNERF_CONV_FAMILY] */
+#define GPNERF_CONV_REFUSED 0              /* the convolution calls return GPNERF_E_ARG for this shape */
+#define GPNERF_CONV_DIRECT_1X1 1           /* 1x1, stride 1 or 2: the direct kernel, 256 consecutive pixels per workgroup */
+#define GPNERF_CONV_DIRECT_NARROW3 2       /* 3x3 stride 1 on fewer than 8 channels: the direct kernel on the flattened (tap, channel) K */
+#define GPNERF_CONV_TILED_S1 3             /* 3x3 stride 1: 4 RW rows x 32 columns per workgroup, patch staged in LDS */
+#define GPNERF_CONV_TILED_S2 4             /* 3x3 stride 2: the same kernel on 4 x 32 output tiles */
+#define GPNERF_CONV_STEM 5                 /* 7x7 stride 2 on at most 4 channels: 8 x 32 output tiles */
+int gpnerf_conv_variant(int32_t n, int32_t h, int32_t w, int32_t cin_a, int32_t cin_b, int32_t cout, int32_t ks, int32_t stride,
+                        int32_t* variant);
 int64_t gpnerf_conv_packed_bytes(int32_t cout, int32_t cin, int32_t ks);
 int gpnerf_conv_pack_weight(const float* weight, int32_t cout, int32_t cin, int32_t ks, int32_t exact, void* packed, void* stream);
 int32_t gpnerf_conv_out_tiles(int32_t h, int32_t w, int32_t cin, int32_t ks, int32_t stride);

@@ -116,6 +116,15 @@ def test_host_only_entry_points_run_without_a_gpu(pkg):
     assert lib.gpnerf_render_plan(512 * 512, 64, 0, 256, 0, lib.gpnerf_render_workspace_bytes(512 * 512, 64), C.byref(plan)) == 0
     assert plan.triple() == ("QUEUE", "UNIFIED", "REF") and plan.grid == 256 and plan.tiles == 8192
     assert lib.gpnerf_render_plan(512 * 512, 0, 0, 256, 0, 0, C.byref(plan)) == -1
+    v = (C.c_int32 * len(pkg._lib.CONV_VARIANT))()
+    assert lib.gpnerf_conv_variant(3, 128, 128, 64, 0, 64, 3, 1, v) == 0 and list(v) == [3, 1, 2, 1, 0, 64, 8, 32]      # the encoder's bulk: 8-row tiles
+    assert lib.gpnerf_conv_variant(3, 128, 128, 24, 0, 64, 3, 1, v) == -1 and v[0] == 0
+    hdr = open(HEADER).read()
+    for i, name in enumerate(pkg._lib.CONV_VARIANT):
+        assert re.search(rf"#define GPNERF_CONV_{name.upper()} {i}\b", hdr), name
+    for i, name in enumerate(pkg._lib.CONV_FAMILIES):
+        assert re.search(rf"#define GPNERF_CONV_{name} {i}\b", hdr), name
+    assert f"#define GPNERF_CONV_VARIANT_INTS {len(pkg._lib.CONV_VARIANT)}" in hdr
 
 
 def test_the_workspace_covers_the_colour_list_at_its_worst(pkg):
