@@ -136,6 +136,15 @@ GRID_HDR_INTS = 64
 SAMPLE_OK, SAMPLE_NO_AREA = range(2)
 DIST_FINITE, DIST_INF, DIST_NAN, DIST_MEAN, DIST_MEAN_SQ, DIST_MAX, DIST_WITHIN = range(7)
 DIST_MAX_THRESHOLDS, DIST_DOUBLES = 4, 10
+# gpnerf_rigid_fit / gpnerf_align_step: the sums' geometry, the statuses, the slot's indices and the workspace's (doubles) (include/gpnerf_hip.h
+# GPNERF_ALIGN_* / GPNERF_XFORM_*)
+ALIGN_THREADS, ALIGN_BLOCKS = 256, 64
+ALIGN_OK, ALIGN_FEW, ALIGN_SINGULAR = range(3)
+ALIGN_STATUS_NAMES = ("ok", "few", "singular")
+XFORM_M, XFORM_SCALE, XFORM_STATUS, XFORM_USED, XFORM_SKIPPED, XFORM_TRIMMED, XFORM_WSUM, XFORM_RMS, XFORM_PIVOT = 0, 12, 13, 14, 15, 16, 17, 18, 19
+XFORM_DOUBLES = 24
+ALIGN_WS = {"sums1": 0, "centroids": 8, "sums2": 16, "step": 32, "counts": 64, "rows": 128, "count_rows": 1984}
+ALIGN_WS_DOUBLES = 2240
 # gpnerf_mesh_rasterize's stats row and gpnerf_silhouette_stats' row (include/gpnerf_hip.h GPNERF_RASTER_* / GPNERF_SILHOUETTE_*)
 RASTER_DRAWN, RASTER_SKIPPED_VERTEX, RASTER_SKIPPED_AREA, RASTER_PIXELS = range(4)
 SILHOUETTE_COVERED, SILHOUETTE_GT, SILHOUETTE_BOTH, SILHOUETTE_EITHER, SILHOUETTE_IGNORED, SILHOUETTE_COUNTS = range(6)
@@ -288,6 +297,12 @@ SYMBOLS = {
     "gpnerf_mesh_sample_surface": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_uint32, C.c_void_p, C.c_size_t,
                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gpnerf_distance_stats": (C.c_int, [C.c_void_p, C.c_int64, FP, C.c_int32, C.c_void_p, C.c_void_p]),
+    "gpnerf_align_workspace_bytes": (C.c_size_t, []),
+    "gpnerf_rigid_fit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "gpnerf_align_init": (C.c_int, [C.c_void_p, C.c_int64, DP, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "gpnerf_transform_points": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    "gpnerf_align_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+                                    C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "gpnerf_mesh_raster_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32, C.c_int32]),
     "gpnerf_mesh_rasterize": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, DP, C.c_int32, C.c_int32, C.c_int32, C.c_double,
                                         C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

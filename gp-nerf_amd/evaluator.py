@@ -244,6 +244,13 @@ class MeshEvaluator:
     for the project's scenes: 5 mm, 1 cm, 2 cm); metric_max_dist: gpnerf_mesh_distance's max_dist (inf: exact everywhere);
     metric_cell_cap, metric_entry_cap: the grids' capacities (None: frame.mesh_grid_caps).  `evaluate` does not read the grids'
     status, so a grid that overflows its entry capacity shows at `summarize()`, whose error says how to find the capacity to pass here.
+    align (None by default; "rigid"): the frame's mesh is first registered onto `gt_mesh` on the device (frame.align_mesh through
+    frame.mesh_metrics(align="rigid"): `align_iterations` trimmed point-to-plane steps, pairs beyond `align_max_dist` trimmed; still
+    no host read per frame), so the geometry metrics are those AFTER registration -- a scan sits millimetres to centimetres off the
+    lattice frame, which at 5 mm decides the F-score.  `summarize()` then adds per frame `align_rms`, `align_rotation_deg`,
+    `align_translation` (the length of the translation) and `align_status` (0 ok, 1 few, 2 singular), their means but for the
+    status, and saves the 4 x 4 matrices as `<result_path>/align_transforms.npy` [frames, 4, 4].  With None the keys and files are
+    what they are without the keyword.
     silhouette (off by default; data with cameras and masks but no scan): a batch with `hull_masks` [1,n,h,w] uint8 (0, 1, border
     100), `hull_Ks` [1,n,3,3] and `hull_RTs` [1,n,3,4] -- the keys of the dense renderer's geometry mode -- makes `evaluate` put the
     frame's mesh through `to_lattice_frame(output["axes"], PAD)`, draw it into those cameras at the masks' size
@@ -278,7 +285,8 @@ class MeshEvaluator:
 
     def __init__(self, result_path, mesh_th, export_mesh=False, metric_samples=100000, metric_thresholds=(0.005, 0.01, 0.02),
                  metric_max_dist=float("inf"), metric_device=None, metric_cell_cap=None, metric_entry_cap=None, silhouette=False,
-                 topology=False, volume=False, volume_rule="nonzero", components=False):
+                 topology=False, volume=False, volume_rule="nonzero", components=False, align=None, align_iterations=10,
+                 align_max_dist=float("inf")):
         self.mesh_th = mesh_th
         self.export_mesh = bool(export_mesh)
         self.result_path = result_path
@@ -288,6 +296,10 @@ class MeshEvaluator:
         self.metric_max_dist, self.metric_device = float(metric_max_dist), metric_device
         self.metric_cell_cap, self.metric_entry_cap = metric_cell_cap, metric_entry_cap
         self._slots, self._frames = [], []
+        if align not in (None, "rigid"):
+            raise L.GpnerfError(f"MeshEvaluator: align is None or 'rigid', got {align!r}")
+        self.align, self.align_iterations, self.align_max_dist = align, int(align_iterations), float(align_max_dist)
+        self._transforms = []
         self.silhouette = bool(silhouette)
         self._sil_slots, self._sil_frames = [], []
         self.topology = bool(topology)
@@ -403,9 +415,15 @@ class MeshEvaluator:
             pred = output["mesh"]
             if "axes" in output:
                 pred = pred.to_lattice_frame(output["axes"], self.PAD)
-            self._slots.append(F.mesh_metrics(pred, batch["gt_mesh"], n_samples=self.metric_samples, thresholds=self.metric_thresholds,
-                                              max_dist=self.metric_max_dist, device=self.metric_device, cell_cap=self.metric_cell_cap,
-                                              entry_cap=self.metric_entry_cap))
+            kw = dict(n_samples=self.metric_samples, thresholds=self.metric_thresholds, max_dist=self.metric_max_dist,
+                      device=self.metric_device, cell_cap=self.metric_cell_cap, entry_cap=self.metric_entry_cap)
+            if self.align is None:
+                self._slots.append(F.mesh_metrics(pred, batch["gt_mesh"], **kw))
+            else:
+                slots, transform = F.mesh_metrics(pred, batch["gt_mesh"], align=self.align, align_iterations=self.align_iterations,
+                                                  align_max_dist=self.align_max_dist, want_transform=True, **kw)
+                self._slots.append(slots)
+                self._transforms.append(transform)
             self._frames.append(self._scalar(batch["frame_index"]))
             if self.volume:
                 self._enqueue_volume(output, batch)
@@ -519,15 +537,25 @@ class MeshEvaluator:
             return {}
         from . import frame as F
         host = torch.stack(self._slots).cpu().numpy()         # the one read: it waits for the frames' kernels
+        moves = [F.read_transform(t) for t in torch.stack(self._transforms).cpu().numpy()] if self._transforms else []
         rows = [F.read_mesh_metrics(s, self.metric_thresholds) for s in host]
         per_frame = {k: [r[k] for r in rows] for k in rows[0]}
         per_frame["frame_index"] = list(self._frames)
         metrics = {k: float(np.mean(v)) for k, v in per_frame.items() if k != "frame_index"}
+        if moves:
+            aligned = {"align_rms": [m["rms"] for m in moves], "align_rotation_deg": [m["rotation_deg"] for m in moves],
+                       "align_translation": [float(np.linalg.norm(m["translation"])) for m in moves]}
+            metrics.update({k: float(np.mean(v)) for k, v in aligned.items()})
+            aligned["align_status"] = [L.ALIGN_STATUS_NAMES.index(m["status"]) for m in moves]
         table = np.zeros(len(rows), dtype=[(k, "i8" if k == "frame_index" else "f8") for k in ["frame_index"] + list(rows[0])])
         for k in table.dtype.names:
             table[k] = per_frame[k]
         os.makedirs(self.result_path, exist_ok=True)
         np.save(os.path.join(self.result_path, "mesh_metrics.npy"), table)      # a structured array: one row per frame, a field per key
+        if moves:
+            per_frame.update(aligned)
+            np.save(os.path.join(self.result_path, "align_transforms.npy"), np.stack([m["matrix"] for m in moves]))
+            self._transforms = []
         for k in ("accuracy", "completeness", "chamfer", "normal_consistency"):
             print(f"{k}: {metrics[k]}")
         metrics["per_frame"] = per_frame

@@ -1533,17 +1533,181 @@ def distance_stats(values, thresholds=(), out=None):
     return out
 
 
+# ---- registering a mesh onto a scan (csrc/gpnerf_align.hip)
+
+def align_workspace(device):
+    """a workspace for rigid_fit / align_mesh's calls (uint8, gpnerf_align_workspace_bytes()); _lib.ALIGN_WS names its doubles"""
+    return torch.empty((int(L.lib().gpnerf_align_workspace_bytes()),), device=device, dtype=torch.uint8)
+
+
+def _slot(out, device, what):
+    if out is None:
+        return torch.empty((L.XFORM_DOUBLES,), device=device, dtype=torch.float64)
+    _require_gpu(out, f"{what}: the slot")
+    if out.dtype != torch.float64 or out.numel() != L.XFORM_DOUBLES or not out.is_contiguous() or out.device != device:
+        raise L.GpnerfError(f"{what}: the slot is a contiguous float64 [{L.XFORM_DOUBLES}] tensor on {device}, got {out.dtype} "
+                            f"{tuple(out.shape)} on {out.device}")
+    return out
+
+
+def rigid_fit(src, dst, weights=None, scale=False, out=None, workspace=None):
+    """gpnerf_rigid_fit: the weighted least-squares x -> s R x + t (s = 1 unless scale) that takes the device float32 points src
+    [n,3] onto dst [n,3]; weights: device float32 [n] or None.  Returns the transform slot (float64 [_lib.XFORM_DOUBLES] on the
+    device; out: a slot to write into); read_transform turns it into a dict.  workspace: an align_workspace to use (its sums stay
+    readable behind the call).  Nothing is read back."""
+    lib = L.lib()
+    src = _points(src, "rigid_fit: src")
+    dst = _points(dst, "rigid_fit: dst", like=src)
+    n, dev = int(src.shape[0]), src.device
+    if dst.device != dev:
+        raise L.GpnerfError("rigid_fit: src and dst are on different devices")
+    if weights is not None:
+        _require_gpu(weights, "rigid_fit: weights")
+        if weights.dtype != torch.float32 or weights.shape != (n,) or not weights.is_contiguous() or weights.device != dev:
+            raise L.GpnerfError(f"rigid_fit: weights is a contiguous float32 [{n}] tensor on {dev}, got {weights.dtype} {tuple(weights.shape)}")
+    slot = _slot(out, dev, "rigid_fit")
+    ws = align_workspace(dev) if workspace is None else workspace
+    L.check(lib.gpnerf_rigid_fit(src.data_ptr() or ws.data_ptr(), dst.data_ptr() or ws.data_ptr(),
+                                 (weights.data_ptr() or ws.data_ptr()) if weights is not None else None, n, int(bool(scale)), slot.data_ptr(),
+                                 ws.data_ptr(), ws.numel(), _stream_ptr(dev)), "gpnerf_rigid_fit")
+    return slot
+
+
+def transform_points(points, slot, vectors=False, out=None):
+    """gpnerf_transform_points: float32(M p) for device float32 points [n,3] and a transform slot; vectors: the rotation alone
+    (normals).  out: where to write (may be `points` itself).  Nothing is read back."""
+    lib = L.lib()
+    points = _points(points, "transform_points: points")
+    slot = _slot(slot, points.device, "transform_points")
+    out = torch.empty_like(points) if out is None else _points(out, "transform_points: out", like=points)
+    if out.device != points.device:
+        raise L.GpnerfError("transform_points: points and out are on different devices")
+    n = int(points.shape[0])
+    L.check(lib.gpnerf_transform_points(points.data_ptr() or slot.data_ptr(), n, slot.data_ptr(), int(bool(vectors)),
+                                        out.data_ptr() or slot.data_ptr(), _stream_ptr(points.device)), "gpnerf_transform_points")
+    return out
+
+
+def read_transform(slot):
+    """A transform slot (tensor or array; the tensor's copy is the one host read, and the caller's) -> dict: matrix (4 x 4 float64),
+    scale, rotation_deg (the angle of R), translation [3], rms, used, skipped, trimmed, status ("ok", "few", "singular"), pivot [3].
+    Raises when nothing was used and every pair was skipped: align_mesh's target grid overflowed its entry capacity, or the
+    sampled mesh has no valid face with area (read_mesh_metrics' advice)."""
+    s = np.asarray(slot.detach().cpu() if isinstance(slot, torch.Tensor) else slot, dtype=np.float64).reshape(L.XFORM_DOUBLES)
+    used, skipped, trimmed = (int(s[k]) for k in (L.XFORM_USED, L.XFORM_SKIPPED, L.XFORM_TRIMMED))
+    if used == 0 and trimmed == 0 and skipped > 0:
+        raise L.GpnerfError("read_transform: every pair was skipped: either the grid of the mesh registered onto overflowed its "
+                            "entry capacity (build_mesh_grid(vertices, faces).entry_cap is a capacity that fits: pass it as entry_cap), "
+                            "or the sampled mesh has no valid face with a positive area")
+    M = np.vstack([s[L.XFORM_M:L.XFORM_M + 12].reshape(3, 4), [0.0, 0.0, 0.0, 1.0]])
+    scale = float(s[L.XFORM_SCALE])
+    cos = (np.trace(M[:3, :3]) / scale - 1.0) / 2.0
+    return {"matrix": M, "scale": scale, "rotation_deg": float(np.degrees(np.arccos(min(1.0, max(-1.0, cos))))),
+            "translation": M[:3, 3].copy(), "rms": float(s[L.XFORM_RMS]), "used": used, "skipped": skipped, "trimmed": trimmed,
+            "status": L.ALIGN_STATUS_NAMES[int(s[L.XFORM_STATUS])], "pivot": s[L.XFORM_PIVOT:L.XFORM_PIVOT + 3].copy()}
+
+
+def align_init(points, init=None, out=None, workspace=None):
+    """gpnerf_align_init: a slot with M = init (a host 3 x 4 or 4 x 4 matrix; None: the identity) and PIVOT = the centroid of the
+    finite device float32 points [n,3]"""
+    lib = L.lib()
+    points = _points(points, "align_init: points")
+    dev = points.device
+    slot = _slot(out, dev, "align_init")
+    ws = align_workspace(dev) if workspace is None else workspace
+    m = None
+    if init is not None:
+        a = np.asarray(init.detach().cpu() if isinstance(init, torch.Tensor) else init, dtype=np.float64)
+        if a.shape not in ((3, 4), (4, 4)):
+            raise L.GpnerfError(f"align_init: init is a 3 x 4 or 4 x 4 matrix, got {a.shape}")
+        m = (C.c_double * 12)(*a[:3].reshape(-1))
+    L.check(lib.gpnerf_align_init(points.data_ptr() or ws.data_ptr(), int(points.shape[0]), m, slot.data_ptr(), ws.data_ptr(), ws.numel(),
+                                  _stream_ptr(dev)), "gpnerf_align_init")
+    return slot
+
+
+def align_step(cur, nearest, vertices, faces, slot, max_dist=float("inf"), history_row=None, workspace=None):
+    """gpnerf_align_step: one trimmed point-to-plane step composed onto the slot's matrix.  cur: the source points as transformed by
+    the slot; nearest: point_mesh_distance(cur, ..., want_closest=True)'s result against the device mesh (vertices, faces);
+    history_row: a device float64 [4] for (rms, used, trimmed, status)."""
+    lib = L.lib()
+    nv, nf = _mesh_tensors(vertices, faces, "align_step")
+    cur = _points(cur, "align_step: cur")
+    dev = cur.device
+    closest = _points(nearest["closest"], "align_step: closest", like=cur)
+    face, dist = nearest["face"], nearest["dist"]
+    n = int(cur.shape[0])
+    if face.dtype != torch.int32 or dist.dtype != torch.float32 or face.shape != (n,) or dist.shape != (n,) or not face.is_contiguous() \
+            or not dist.is_contiguous() or any(t.device != dev for t in (closest, face, dist, vertices)):
+        raise L.GpnerfError("align_step: face int32 [n] and dist float32 [n] as point_mesh_distance wrote them, on the points' device")
+    slot = _slot(slot, dev, "align_step")
+    if history_row is not None and (history_row.dtype != torch.float64 or history_row.numel() != 4 or not history_row.is_contiguous()
+                                    or history_row.device != dev):
+        raise L.GpnerfError("align_step: history_row is a contiguous float64 [4] tensor on the points' device")
+    ws = align_workspace(dev) if workspace is None else workspace
+    p = lambda t: t.data_ptr() or ws.data_ptr()
+    L.check(lib.gpnerf_align_step(p(cur), p(closest), p(face), p(dist), n, p(vertices), nv, faces.data_ptr(), nf, float(max_dist),
+                                  slot.data_ptr(), history_row.data_ptr() if history_row is not None else None, ws.data_ptr(), ws.numel(),
+                                  _stream_ptr(dev)), "gpnerf_align_step")
+    return slot
+
+
+def align_mesh(src, dst, iterations=10, n_samples=20000, max_dist=float("inf"), seed=0, init=None, grid=None, cell_cap=None,
+               entry_cap=None, points=None, device=None):
+    """Register the mesh src onto the mesh dst by trimmed point-to-plane ICP, enqueued on the device without a host read:
+    n_samples stratified surface samples of src (sample_surface, `seed`), a grid of dst (build_mesh_grid(check=False), unless a
+    MeshGrid `grid` of it is given -- dst may then be None), align_init (init: a host 3 x 4 or 4 x 4 starting matrix), then
+    `iterations` times, a fixed count: transform_points of the ORIGINAL samples by the cumulative matrix (float32 roundings never
+    pile up), point_mesh_distance(want_closest=True) at max_dist inf, align_step (pairs farther than max_dist trimmed).
+    points: device float32 [n,3] source points to use instead of sampling (src may then be None).
+    src, dst: mesh.Mesh, or (vertices, faces) arrays / tensors.  Returns {"transform": the slot of the transform src -> dst,
+    "history": float64 [iterations, 4] on the device, a row (rms before the step, used, trimmed, status) per iteration}.
+    A grid that overflowed makes every distance NaN: every pair is skipped, the status is "few", and read_transform raises."""
+    if device is None:
+        first = points if points is not None else (grid.vertices if grid is not None else (src[0] if isinstance(src, (tuple, list)) else None))
+        device = first.device if isinstance(first, torch.Tensor) and first.is_cuda else torch.device("cuda:0")
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise L.GpnerfError(f"align_mesh computes on the GPU (got {device}); the HIP path has no CPU fallback")
+    iterations = int(iterations)
+    if iterations < 0:
+        raise L.GpnerfError(f"align_mesh: iterations >= 0, got {iterations}")
+    if points is None:
+        sv, sf = mesh_to_device(src, device)
+        points = sample_surface(sv, sf, n_samples, seed=seed, want_face=False, want_normal=False)["points"]
+    points = _points(points, "align_mesh: points")
+    if grid is None:
+        dv, df = mesh_to_device(dst, device)
+        grid = build_mesh_grid(dv, df, cell_cap, entry_cap, check=False)
+    ws = align_workspace(device)
+    slot = align_init(points, init, workspace=ws)
+    history = torch.empty((iterations, 4), device=device, dtype=torch.float64)
+    cur = torch.empty_like(points)
+    for it in range(iterations):
+        transform_points(points, slot, out=cur)
+        near = point_mesh_distance(cur, grid=grid, want_closest=True)
+        align_step(cur, near, grid.vertices, grid.faces, slot, max_dist=max_dist, history_row=history[it], workspace=ws)
+    return {"transform": slot, "history": history}
+
+
 MESH_METRIC_ROWS = ("pred_to_gt", "gt_to_pred", "cos_pred_to_gt", "cos_gt_to_pred")
+ALIGN_SAMPLES = 20000                    # align_mesh's default number of source samples
 
 
 def mesh_metrics(pred, gt, n_samples=100000, thresholds=(0.005, 0.01, 0.02), seed=0, max_dist=float("inf"), device=None, cell_cap=None,
-                 entry_cap=None):
+                 entry_cap=None, align=None, align_iterations=10, align_max_dist=float("inf"), want_transform=False):
     """The geometry metrics of a predicted mesh against a ground-truth one, enqueued on the device without a host read:
     n_samples stratified surface samples of each (sample_surface; seeds `seed` and `seed + 1`), the exact distance of each sample
     to the OTHER mesh with the cosine between the sample's face normal and the nearest face's (point_mesh_distance through a grid
     built with check=False), and the four reductions (distance_stats).  pred, gt: mesh.Mesh, or (vertices, faces) arrays / tensors,
     in the same frame and unit; device: where to compute (default: the tensors' device, else cuda:0).
+    align: None (the default: the meshes are compared where they are, with exactly the launches of a call without the keyword), or
+    "rigid": the predicted mesh is first registered onto gt by align_mesh (align_iterations steps on min(n_samples, ALIGN_SAMPLES)
+    samples, pairs beyond align_max_dist trimmed) and its vertices go through transform_points before the sampling: still no host
+    read.  want_transform: return (slots, transform slot); the slot is None without align.
     Returns float64 [4, _lib.DIST_DOUBLES] on the device, rows MESH_METRIC_ROWS; read_mesh_metrics turns it into a dict."""
+    if align not in (None, "rigid"):
+        raise L.GpnerfError(f"mesh_metrics: align is None or 'rigid', got {align!r}")
     if device is None:
         v = pred[0] if isinstance(pred, (tuple, list)) else None
         device = v.device if isinstance(v, torch.Tensor) and v.is_cuda else torch.device("cuda:0")
@@ -1554,9 +1718,16 @@ def mesh_metrics(pred, gt, n_samples=100000, thresholds=(0.005, 0.01, 0.02), see
     pv, pf = mesh_to_device(pred, device)
     gv, gf = mesh_to_device(gt, device)
     slots = torch.empty((4, L.DIST_DOUBLES), device=device, dtype=torch.float64)
+    transform = g_gt = None
+    if align is not None:
+        g_gt = build_mesh_grid(gv, gf, cell_cap, entry_cap, check=False)
+        transform = align_mesh((pv, pf), None, iterations=align_iterations, n_samples=min(int(n_samples), ALIGN_SAMPLES),
+                               max_dist=align_max_dist, seed=seed, grid=g_gt)["transform"]
+        pv = transform_points(pv, transform)
     sp = sample_surface(pv, pf, n_samples, seed=seed, want_face=False)
     sg = sample_surface(gv, gf, n_samples, seed=seed + 1, want_face=False)
-    g_gt = build_mesh_grid(gv, gf, cell_cap, entry_cap, check=False)
+    if g_gt is None:
+        g_gt = build_mesh_grid(gv, gf, cell_cap, entry_cap, check=False)
     g_pred = build_mesh_grid(pv, pf, cell_cap, entry_cap, check=False)
     a = point_mesh_distance(sp["points"], grid=g_gt, max_dist=max_dist, query_normals=sp["normal"])
     b = point_mesh_distance(sg["points"], grid=g_pred, max_dist=max_dist, query_normals=sg["normal"])
@@ -1564,7 +1735,7 @@ def mesh_metrics(pred, gt, n_samples=100000, thresholds=(0.005, 0.01, 0.02), see
     distance_stats(b["dist"], th, out=slots[1])
     distance_stats(a["cosine"], (), out=slots[2])
     distance_stats(b["cosine"], (), out=slots[3])
-    return slots
+    return (slots, transform) if want_transform else slots
 
 
 def read_mesh_metrics(slots, thresholds=(0.005, 0.01, 0.02)):

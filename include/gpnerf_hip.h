@@ -667,6 +667,120 @@ int gpnerf_mesh_sample_surface(const float* vertices, int64_t n_vertices, const 
                                float* sample_normal, void* stream);
 int gpnerf_distance_stats(const float* values, int64_t n, const float* thresholds, int32_t n_thresholds, double* out, void* stream);
 
+/* ---- registering a mesh onto a scan (gpnerf_align.hip): the least-squares rigid / similarity fit of given pairs, the transform of
+ * a point list, and one trimmed point-to-plane step of ICP (iterative closest point) on the correspondences gpnerf_mesh_distance
+ * wrote.  A scan sits millimetres to centimetres off the frame a predicted mesh is extracted in, and at F-score thresholds of 5 mm
+ * that offset decides the number; the loop -- transform, nearest point, step, a fixed number of times -- runs without a host read.
+ * All entry points: kernel launches only, on the caller's stream; nothing allocated, nothing waited for; a fixed number of launches
+ * of a fixed size; every data-dependent decision is taken on the device and leaves a status; no atomics; every call captures into
+ * a HIP graph and replays with the same bits.
+ *
+ * THE SLOT: device double [GPNERF_XFORM_DOUBLES].  M[12]: the row-major 3 x 4 matrix of x -> s R x + t;  SCALE: s;  STATUS:
+ * GPNERF_ALIGN_OK, GPNERF_ALIGN_FEW (too few pairs) or GPNERF_ALIGN_SINGULAR;  USED: the pairs that entered the last fit;  SKIPPED:
+ * the pairs with a non-finite coordinate, a weight that is not finite and > 0, a face outside [0, n_faces) or INVALID, or a nearest
+ * face of zero area;  TRIMMED: the pairs whose distance exceeds max_dist;  WSUM: the sum of the weights used;  RMS: the weighted
+ * root-mean-square residual of the used pairs BEFORE the fit (NaN when none was used);  PIVOT[3]: the point c the plane step rotates
+ * about.  The counts are whole numbers stored as doubles.  No call ever writes a non-finite number into M or SCALE.
+ *
+ * THE SUMS.  Everything is double, unfused, from the float32 inputs converted exactly, and every sum has one association: pair i
+ * belongs to thread t = i % GPNERF_ALIGN_THREADS of workgroup b = (i / GPNERF_ALIGN_THREADS) % GPNERF_ALIGN_BLOCKS, i.e. thread t of
+ * workgroup b adds the terms of the pairs i = (k BLOCKS + b) THREADS + t, k = 0, 1, ..., in ascending k, onto zero; a workgroup's 256
+ * partials fold by the halving tree x[t] += x[t + s], s = 128, 64, ..., 1 (gpnerf_distance_stats' tree); the 64 workgroups' rows go
+ * to the workspace and the next launch folds them by the same tree from s = 32.  A pair that is skipped or trimmed adds exact zeros
+ * and is counted in integers.  dot(u, v) = (ux vx + uy vy) + uz vz;  u x v = (uy vz - uz vy, uz vx - ux vz, ux vy - uy vx).
+ * The workspace (gpnerf_align_workspace_bytes(), host arithmetic only: 8 GPNERF_ALIGN_WS_DOUBLES) is read as doubles at these
+ * indices once a call's launches are through: WS_SUMS1: W, sum w src [3], sum w dst [3];  WS_CENTROIDS: c_src [3], c_dst [3];
+ * WS_SUMS2: S[9], sum w |a|^2, sum w |dst - src|^2;  WS_STEP: the plane step's 29 sums;  WS_COUNTS: int64 used, skipped, trimmed;
+ * WS_ROWS: the workgroups' rows, [BLOCKS][29];  WS_COUNT_ROWS: int64 [BLOCKS][4].  A call carries nothing over from the workspace.
+ *
+ * (w, x, y, z) -> R, for a unit quaternion: R = [1 - 2 (yy + zz), 2 (xy - wz), 2 (xz + wy);  2 (xy + wz), 1 - 2 (xx + zz),
+ * 2 (yz - wx);  2 (xz - wy), 2 (yz + wx), 1 - 2 (xx + yy)], every product formed once (xx = x x, wz = w z, ...).
+ *
+ * gpnerf_rigid_fit(src, dst, weights, n, with_scale, slot, workspace, workspace_bytes, stream): the weighted least-squares
+ * x -> s R x + t over the n pairs (src[i], dst[i]) (device float [n][3]; weights: device float [n] or NULL for 1), four launches:
+ *   - pass 1: W = sum w, sum w src, sum w dst (term w * coordinate); c_src = sum w src / W, c_dst likewise (0 when no pair is used);
+ *   - pass 2, with a = src - c_src, b = dst - c_dst: S[3 r + k] = sum (w a_r) b_k, sum w dot(a, a), and sum w dot(e, e), e = dst - src;
+ *   - one thread solves Horn's symmetric 4 x 4 (Closed-form solution of absolute orientation using unit quaternions, 1987):
+ *     N00 = (Sxx + Syy) + Szz, N11 = (Sxx - Syy) - Szz, N22 = (Syy - Sxx) - Szz, N33 = (Szz - Sxx) - Syy, N01 = Syz - Szy,
+ *     N02 = Szx - Sxz, N03 = Sxy - Syx, N12 = Sxy + Syx, N13 = Szx + Sxz, N23 = Syz + Szy, by cyclic Jacobi: V = I, a fixed 8
+ *     sweeps, the pairs (p, q), p < q, in row-major order; a rotation is skipped when A[p][q] == 0; theta = (A[q][q] - A[p][p]) /
+ *     (2 A[p][q]), t = sign(theta) / (|theta| + sqrt(theta theta + 1)) (sign(0) = 1), c = 1 / sqrt(t t + 1), s = t c; for k = 0..3
+ *     the columns (A[k][p], A[k][q]) <- (c A[k][p] - s A[k][q], s A[k][p] + c A[k][q]), then the rows p, q likewise, then
+ *     A[p][q] = A[q][p] = 0, then V's columns like A's;
+ *   - the quaternion is V's column at the largest diagonal entry (the lowest index among equal ones), divided by its length
+ *     sqrt(((q0 q0 + q1 q1) + q2 q2) + q3 q3), negated when q0 < 0;  s = 1, or with with_scale (Umeyama's scale for this R)
+ *     s = (sum over i, j in row-major order, onto zero, of R[i][j] S[3 j + i]) / sum w |a|^2;
+ *     t_i = c_dst_i - s ((R_i0 c_src_0 + R_i1 c_src_1) + R_i2 c_src_2);  M = [s R | t];
+ *   - STATUS: fewer than 3 used pairs: _FEW;  sum w |a|^2 not > 0, the four diagonal entries all equal, s not > 0, or anything not
+ *     finite: _SINGULAR.  The call writes the slot ABSOLUTELY: M is the identity and SCALE 1 when the status is not _OK.
+ *     TRIMMED = 0, PIVOT = c_src, RMS = sqrt(sum w |dst - src|^2 / W): the residual of the pairs as given;
+ *   - n == 0 is legal: the sums are empty and the status is _FEW.
+ *
+ * gpnerf_align_init(points, n, init_matrix12, slot, workspace, workspace_bytes, stream): M = init_matrix12 (HOST double [12],
+ * row-major 3 x 4, passed by value; NULL: the identity), SCALE = the length of its first row, STATUS _OK, USED / WSUM = the number of
+ * finite points, SKIPPED the others, RMS 0, PIVOT = the unweighted centroid of the finite points (pass 1 above with w = 1; 0 when
+ * there is none).  Two launches.
+ *
+ * gpnerf_transform_points(points, n, slot, vectors, out, stream): out[i] = float32(M p), each coordinate ((m0 x + m1 y) + m2 z) + m3
+ * in double, rounded once.  vectors != 0 applies R only: (((m0 / s) x + (m1 / s) y) + (m2 / s) z), s = SCALE, no translation (normals).
+ * A point with a non-finite coordinate gives three NaN.  out == points is allowed.  n == 0 is a no-op.
+ *
+ * gpnerf_align_step(cur, closest, face, dist, n, vertices, n_vertices, faces, n_faces, max_dist, slot, history_row, workspace,
+ * workspace_bytes, stream): one point-to-plane Gauss-Newton step.  cur (device float [n][3]) are the source points as the caller
+ * transformed them by the slot's M; closest, face, dist are what gpnerf_mesh_distance wrote for cur against the mesh.  Two launches.
+ *   - a pair in this order: dist NaN or cur not finite: SKIPPED;  dist > max_dist: TRIMMED;  dist infinite, face outside
+ *     [0, n_faces), closest not finite, the face INVALID, or its normal's length not > 0: SKIPPED;  otherwise used;
+ *   - per used pair, a, b, c the face's vertices: n_f = (b - a) x (c - a), each component divided by sqrt(dot(n, n));
+ *     c' = M PIVOT, each coordinate ((m0 c0 + m1 c1) + m2 c2) + m3;  J = [(p - c') x n_f, n_f];  r = dot(closest - p, n_f);
+ *   - the 29 sums: J_u J_v for u <= v in row-major order (21), J_u r (6), r r, and 1 (W);
+ *   - one thread solves (sum J J^T) x = sum J r, x = (omega, u), by Cholesky, column by column, every sum a chain of subtractions in
+ *     ascending k: d_j = A_jj - L_j0 L_j0 - ...; L_jj = sqrt(d_j); L_ij = (A_ij - L_i0 L_j0 - ...) / L_jj;  y_i = (g_i - L_i0 y_0 -
+ *     ...) / L_ii;  x_i = (y_i - L_(i+1)i x_(i+1) - ... - L_5i x_5) / L_ii for i = 5 .. 0.  A pivot d_j that is not > 2^-30 A_jj:
+ *     _SINGULAR.  Fewer than 6 used pairs: _FEW (tested first);
+ *   - the rotation of the update uses no trigonometry (Cayley), so only + - x / sqrt occur: h = omega / 2, q = (1, h) / sqrt(1 +
+ *     ((hx hx + hy hy) + hz hz)) -- 1 / sqrt(..) formed once, then multiplied -- and R from q as above;
+ *   - the step p -> R (p - c') + c' + u = R p + ts, ts_i = (c'_i + u_i) - ((R_i0 c'_0 + R_i1 c'_1) + R_i2 c'_2), is composed onto M
+ *     on the left: M'_ij = (R_i0 M_0j + R_i1 M_1j) + R_i2 M_2j, j = 0 .. 3, and M'_i3 + ts_i.  SCALE and PIVOT stay;
+ *   - a status other than _OK (or a non-finite M', reported as _SINGULAR) leaves M as it was: the step is the identity;
+ *   - USED, SKIPPED, TRIMMED, WSUM (= USED), STATUS are written; RMS = sqrt(sum r r / W), the plane residual BEFORE the step;
+ *     history_row (device double [4] or NULL) receives RMS, USED, TRIMMED, STATUS.
+ *
+ * GPNERF_E_ARG, before any device call: a null pointer (weights, init_matrix12 and history_row may be null), n < 0 or >= 2^39, a
+ * workspace under gpnerf_align_workspace_bytes(), a max_dist that is not > 0, n_vertices < 0, n_faces < 1 or >= 2^31, a non-finite
+ * init_matrix12 or one whose first row is zero. */
+#define GPNERF_ALIGN_THREADS 256
+#define GPNERF_ALIGN_BLOCKS 64
+#define GPNERF_ALIGN_OK 0
+#define GPNERF_ALIGN_FEW 1
+#define GPNERF_ALIGN_SINGULAR 2
+#define GPNERF_XFORM_M 0
+#define GPNERF_XFORM_SCALE 12
+#define GPNERF_XFORM_STATUS 13
+#define GPNERF_XFORM_USED 14
+#define GPNERF_XFORM_SKIPPED 15
+#define GPNERF_XFORM_TRIMMED 16
+#define GPNERF_XFORM_WSUM 17
+#define GPNERF_XFORM_RMS 18
+#define GPNERF_XFORM_PIVOT 19
+#define GPNERF_XFORM_DOUBLES 24
+#define GPNERF_ALIGN_WS_SUMS1 0
+#define GPNERF_ALIGN_WS_CENTROIDS 8
+#define GPNERF_ALIGN_WS_SUMS2 16
+#define GPNERF_ALIGN_WS_STEP 32
+#define GPNERF_ALIGN_WS_COUNTS 64
+#define GPNERF_ALIGN_WS_ROWS 128
+#define GPNERF_ALIGN_WS_COUNT_ROWS 1984
+#define GPNERF_ALIGN_WS_DOUBLES 2240
+size_t gpnerf_align_workspace_bytes(void);
+int gpnerf_rigid_fit(const float* src, const float* dst, const float* weights, int64_t n, int32_t with_scale, double* slot, void* workspace,
+                     size_t workspace_bytes, void* stream);
+int gpnerf_align_init(const float* points, int64_t n, const double* init_matrix12, double* slot, void* workspace, size_t workspace_bytes,
+                      void* stream);
+int gpnerf_transform_points(const float* points, int64_t n, const double* slot, int32_t vectors, float* out, void* stream);
+int gpnerf_align_step(const float* cur, const float* closest, const int32_t* face, const float* dist, int64_t n, const float* vertices,
+                      int64_t n_vertices, const int32_t* faces, int64_t n_faces, float max_dist, double* slot, double* history_row,
+                      void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- drawing a mesh into calibrated cameras (gpnerf_raster.hip): depth and face-id maps, vertex attributes interpolated over them,
  * and the counts that compare the mesh's silhouette with a foreground mask (mask IoU, precision, recall: how a body mesh is judged on
  * data that has cameras and masks but no scan).  All entry points: kernel launches only, on the caller's stream; nothing allocated,
