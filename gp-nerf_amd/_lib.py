@@ -179,6 +179,10 @@ VOXEL_RULES = {"parity": VOXEL_PARITY, "nonzero": VOXEL_NONZERO}
 VOXEL_STATS = ("used", "skipped_vertex", "skipped_area", "crossings", "open_columns", "occupied")
 VOXEL_A, VOXEL_B, VOXEL_BOTH, VOXEL_EITHER, VOXEL_COUNTS = range(5)
 VOXEL_MAX_POINTS = 1 << 28
+# gpnerf_mesh_sdf's stats, its tier threshold and its limit on the band in steps (include/gpnerf_hip.h GPNERF_SDF_*)
+SDF_STATS = ("used", "skipped_vertex", "skipped_box", "large", "in_band", "inside", "visited", "pairs")
+SDF_LARGE_POINTS = 64
+SDF_MAX_BAND_STEPS = 1024
 # gpnerf_conv_variant's row and its kernel families (include/gpnerf_hip.h GPNERF_CONV_*)
 CONV_VARIANT = ("family", "cot", "rw", "ksplit", "cat", "tiles", "tile_h", "tile_w")
 CONV_FAMILIES = ("REFUSED", "DIRECT_1X1", "DIRECT_NARROW3", "TILED_S1", "TILED_S2", "STEM")
@@ -332,6 +336,10 @@ SYMBOLS = {
     "gpnerf_voxel_unpack": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_void_p, C.c_void_p]),
     "gpnerf_voxel_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_void_p, C.c_void_p]),
     "gpnerf_voxel_contains": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), DP, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "gpnerf_mesh_sdf_workspace_bytes": (C.c_size_t, [C.c_int64, C.POINTER(C.c_int32)]),
+    "gpnerf_mesh_sdf": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, DP, C.POINTER(C.c_int32), C.c_float, C.c_void_p, C.c_void_p,
+                                  C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gpnerf_sdf_sample": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), DP, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "gpnerf_head_layout": (C.c_int, [C.POINTER(C.c_int32)]),
     "gpnerf_strerror": (C.c_char_p, [C.c_int]),
     "gpnerf_rays_per_tile": (C.c_int32, []),

@@ -280,13 +280,24 @@ class MeshEvaluator:
     `volume_iou`, `volume_pred`, `volume_gt` (the volumes in the axes' unit cubed; means over the frames) and
     `volume_open_columns_pred` / `_gt` (lattice columns through which a mesh leaks: more than 0 says it is not closed, and its volume
     is not to be trusted there), their per-frame lists, and saves `<result_path>/volume_metrics.npy`.  A `gt_mesh` with an output
-    that has no `axes` raises a GpnerfError naming the key.  Off, nothing changes."""
+    that has no `axes` raises a GpnerfError naming the key.  Off, nothing changes.
+    signed (off by default; P2S and Chamfer say how far the reconstruction is from the scan, never on which side: "bloated" and
+    "shrunk" score the same): like `volume` it needs `gt_mesh` in the batch and `axes` in the output.  `evaluate` builds the scan's
+    truncated signed distance field on the frame's padded cube lattice (frame.mesh_sdf, rule `volume_rule`, a band of `signed_band`
+    lattice steps -- times the smallest step), draws `metric_samples` surface samples of the predicted mesh in that frame
+    (to_lattice_frame, frame.sample_surface), samples the field there (SdfGrid.sample) and reduces the values with
+    frame.distance_stats at threshold 0 into a slot: no host read.  `summarize()` reads the slots in one copy and adds
+    `signed_mean` (positive: the prediction lies outside the scan), `inside_fraction` (the share of the samples with a value <= 0)
+    and `signed_outside_lattice` (samples outside the padded lattice, which take no part), their per-frame lists, and saves
+    `<result_path>/signed_metrics.npy`.  Values beyond the band saturate at +-band, so `signed_mean` is a truncated mean: it is the
+    true signed mean while the surfaces are within the band of each other, and an under-estimate in size (never in sign) beyond.
+    Off, nothing changes."""
     PAD = 10                              # if_nerf_mesh.py:20, the np.pad(cube, 10) of BaseRender.py:269
 
     def __init__(self, result_path, mesh_th, export_mesh=False, metric_samples=100000, metric_thresholds=(0.005, 0.01, 0.02),
                  metric_max_dist=float("inf"), metric_device=None, metric_cell_cap=None, metric_entry_cap=None, silhouette=False,
                  topology=False, volume=False, volume_rule="nonzero", components=False, align=None, align_iterations=10,
-                 align_max_dist=float("inf")):
+                 align_max_dist=float("inf"), signed=False, signed_band=8):
         self.mesh_th = mesh_th
         self.export_mesh = bool(export_mesh)
         self.result_path = result_path
@@ -310,6 +321,10 @@ class MeshEvaluator:
         if self.volume_rule not in L.VOXEL_RULES:
             raise L.GpnerfError(f"MeshEvaluator: volume_rule is 'parity' or 'nonzero', got {volume_rule!r}")
         self._vol_slots, self._vol_frames, self._vol_cells = [], [], []
+        self.signed, self.signed_band = bool(signed), float(signed_band)
+        if not 0.0 < self.signed_band <= L.SDF_MAX_BAND_STEPS:
+            raise L.GpnerfError(f"MeshEvaluator: signed_band is in lattice steps, > 0 and at most {L.SDF_MAX_BAND_STEPS}, got {signed_band!r}")
+        self._signed_slots, self._signed_frames = [], []
 
     SILHOUETTE_KEYS = ("hull_masks", "hull_Ks", "hull_RTs")
 
@@ -317,7 +332,48 @@ class MeshEvaluator:
     def has_mesh_metrics(self):
         """True once a frame with `gt_mesh` (or, with silhouette on, with masks and cameras; or any frame with topology or components on) has been evaluated and not yet summarized
         (evaluate_loop asks)"""
-        return bool(self._slots) or bool(self._sil_slots) or bool(self._topo_slots) or bool(self._vol_slots) or bool(self._comp_slots)
+        return (bool(self._slots) or bool(self._sil_slots) or bool(self._topo_slots) or bool(self._vol_slots) or bool(self._comp_slots) or
+                bool(self._signed_slots))
+
+    def _padded_lattice(self, axes):
+        """(lo, step, dims) of the frame's padded cube lattice in the axes' frame: to_lattice_frame's steps, PAD points around"""
+        ax = [np.asarray(a.detach().cpu() if hasattr(a, "detach") else a, dtype=np.float64).reshape(-1) for a in axes]
+        step = np.array([(a[-1] - a[0]) / (len(a) - 1) if len(a) > 1 else 1.0 for a in ax])      # to_lattice_frame's
+        lo = np.array([a[0] for a in ax]) - self.PAD * step
+        return lo, step, tuple(len(a) + 2 * self.PAD for a in ax)
+
+    def _enqueue_signed(self, output, batch):
+        from . import frame as F
+        if "axes" not in output:
+            raise L.GpnerfError("MeshEvaluator(signed=True): the output has no 'axes', so the scan cannot be put on the frame's lattice "
+                                "(the inference renderer's render_mesh; the dense renderer's geometry mode returns axes)")
+        dev = torch.device(self.metric_device if self.metric_device is not None else "cuda:0")
+        lo, step, dims = self._padded_lattice(output["axes"])
+        gv, gf = F.mesh_to_device(batch["gt_mesh"], dev)
+        scan = F.mesh_sdf(gv, gf, lo, step, dims, self.signed_band * float(step.min()), rule=self.volume_rule)
+        pv, pf = F.mesh_to_device(output["mesh"].to_lattice_frame(output["axes"], self.PAD), dev)
+        samples = F.sample_surface(pv, pf, self.metric_samples, want_face=False, want_normal=False)["points"]
+        # threshold 0: the share of the samples with a value <= 0, i.e. inside the scan; the samples outside the lattice are the NaNs
+        self._signed_slots.append(F.distance_stats(scan.sample(samples), thresholds=(0.0,)))
+        self._signed_frames.append(self._scalar(batch["frame_index"]))
+
+    def _summarize_signed(self):
+        """the signed slots -> (means, per-frame lists), signed_metrics.npy written; resets them"""
+        host = torch.stack(self._signed_slots).cpu().numpy()   # the one read
+        per_frame = {"signed_mean": [float(h[L.DIST_MEAN]) for h in host], "inside_fraction": [float(h[L.DIST_WITHIN]) for h in host],
+                     "signed_outside_lattice": [int(h[L.DIST_NAN]) for h in host]}
+        metrics = {k: float(np.mean(v)) for k, v in per_frame.items()}
+        per_frame["signed_frame_index"] = list(self._signed_frames)
+        table = np.zeros(len(host), dtype=[("frame_index", "i8"), ("samples", "i8"), ("outside_lattice", "i8"), ("signed_mean", "f8"),
+                                           ("signed_max", "f8"), ("inside_fraction", "f8")])
+        table["frame_index"] = self._signed_frames
+        table["samples"], table["outside_lattice"] = host[:, L.DIST_FINITE], host[:, L.DIST_NAN]
+        table["signed_mean"], table["signed_max"], table["inside_fraction"] = host[:, L.DIST_MEAN], host[:, L.DIST_MAX], host[:, L.DIST_WITHIN]
+        os.makedirs(self.result_path, exist_ok=True)
+        np.save(os.path.join(self.result_path, "signed_metrics.npy"), table)        # a structured array: one row per frame
+        print(f"signed_mean: {metrics['signed_mean']} (inside_fraction {metrics['inside_fraction']})")
+        self._signed_slots, self._signed_frames = [], []
+        return metrics, per_frame
 
     def _enqueue_volume(self, output, batch):
         from . import frame as F
@@ -325,10 +381,7 @@ class MeshEvaluator:
             raise L.GpnerfError("MeshEvaluator(volume=True): the output has no 'axes', so the scan cannot be put on the frame's lattice "
                                 "(the inference renderer's render_mesh; the dense renderer's geometry mode returns axes)")
         dev = torch.device(self.metric_device if self.metric_device is not None else "cuda:0")
-        ax = [np.asarray(a.detach().cpu() if hasattr(a, "detach") else a, dtype=np.float64).reshape(-1) for a in output["axes"]]
-        step = np.array([(a[-1] - a[0]) / (len(a) - 1) if len(a) > 1 else 1.0 for a in ax])      # to_lattice_frame's
-        lo = np.array([a[0] for a in ax]) - self.PAD * step
-        dims = tuple(len(a) + 2 * self.PAD for a in ax)
+        lo, step, dims = self._padded_lattice(output["axes"])
         pv, pf = F.mesh_to_device(output["mesh"], dev)
         gv, gf = F.mesh_to_device(batch["gt_mesh"], dev)
         pred = F.voxelize_mesh(pv, pf, (0.0, 0.0, 0.0), (1.0, 1.0, 1.0), dims, rule=self.volume_rule)
@@ -427,6 +480,8 @@ class MeshEvaluator:
             self._frames.append(self._scalar(batch["frame_index"]))
             if self.volume:
                 self._enqueue_volume(output, batch)
+            if self.signed:
+                self._enqueue_signed(output, batch)
         if self.silhouette and all(k in batch for k in self.SILHOUETTE_KEYS):
             self._enqueue_silhouette(output, batch)
         if self.topology:
@@ -520,9 +575,10 @@ class MeshEvaluator:
         return metrics, per_frame
 
     def summarize(self):
-        if self._sil_slots or self._topo_slots or self._vol_slots or self._comp_slots:
+        if self._sil_slots or self._topo_slots or self._vol_slots or self._comp_slots or self._signed_slots:
             parts = (([self._summarize_silhouettes()] if self._sil_slots else []) + ([self._summarize_topology()] if self._topo_slots else []) +
-                     ([self._summarize_volumes()] if self._vol_slots else []) + ([self._summarize_components()] if self._comp_slots else []))
+                     ([self._summarize_volumes()] if self._vol_slots else []) + ([self._summarize_components()] if self._comp_slots else []) +
+                     ([self._summarize_signed()] if self._signed_slots else []))
             metrics = self._summarize_mesh_metrics() if self._slots else {"per_frame": {}}
             per_frame = metrics.pop("per_frame")
             for means, frames in parts:

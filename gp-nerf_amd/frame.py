@@ -2015,3 +2015,89 @@ def read_volume_metrics(host_counts, step):
     ratio = lambda num, den: float(c[num]) / float(c[den]) if c[den] else 1.0
     return {"volume_a": float(c[L.VOXEL_A]) * cell, "volume_b": float(c[L.VOXEL_B]) * cell, "iou": ratio(L.VOXEL_BOTH, L.VOXEL_EITHER),
             "precision": ratio(L.VOXEL_BOTH, L.VOXEL_A), "recall": ratio(L.VOXEL_BOTH, L.VOXEL_B)}
+
+
+# ---- the truncated signed distance field of a mesh on a lattice (csrc/gpnerf_sdf.hip)
+
+class SdfGrid:
+    """gpnerf_mesh_sdf's field with its lattice.  values: device float32 [nx,ny,nz], the distance to the mesh where it is within
+    `band`, the band elsewhere, negative where the voxels' bit is set; face: device int32 of the same shape (the nearest face, -1
+    beyond the band) or None; voxels: the VoxelGrid the signs came from, or None for the unsigned field; lo, step: float64 [3];
+    dims; band: the float32 value the kernels compared against; stats: device int64 [8] (_lib.SDF_STATS)."""
+
+    def __init__(self, values, face, voxels, lo, step, dims, band, stats):
+        self.values, self.face, self.voxels, self.stats = values, face, voxels, stats
+        self.dims, self.band = _voxel_dims(dims, "SdfGrid"), float(band)
+        lat = _voxel_lattice(lo, step, "SdfGrid")
+        self.lo, self.step = lat[:3].copy(), lat[3:].copy()
+
+    def sample(self, points):
+        """gpnerf_sdf_sample: the trilinear value of the field at device float32 points [n,3] -> device float32 [n]; NaN for a point
+        that is not finite or lies outside the lattice.  Beyond the band the field is +-band, so the interpolant saturates there."""
+        if not isinstance(points, torch.Tensor):
+            raise L.GpnerfError("SdfGrid.sample: points must be a device tensor")
+        pts = _points(points, "SdfGrid.sample: points")
+        _require_gpu(self.values, "SdfGrid.sample: values")
+        if pts.device != self.values.device:
+            raise L.GpnerfError(f"SdfGrid.sample: points on {pts.device}, the field on {self.values.device}")
+        if min(self.dims) < 2:
+            raise L.GpnerfError(f"SdfGrid.sample: dims {self.dims} refused (each >= 2)")
+        n, dev = int(pts.shape[0]), self.values.device
+        out = torch.empty((n,), device=dev, dtype=torch.float32)
+        lat = np.concatenate([self.lo, self.step])
+        L.check(L.lib().gpnerf_sdf_sample(self.values.data_ptr(), (C.c_int32 * 3)(*self.dims), lat.ctypes.data_as(L.DP),
+                                          pts.data_ptr() if n else None, n, out.data_ptr() if n else None, _stream_ptr(dev)), "gpnerf_sdf_sample")
+        return out
+
+    def offset_mesh(self, offset=0.0):
+        """The surface sdf = offset -- the mesh grown (offset > 0) or shrunk (< 0) by that metric distance -- as (vertices float32
+        [nv,3] in the lattice's frame, faces int32 [nf,3]), device: marching_cubes(-values, iso=-offset), which takes !(v < iso) as
+        inside, with the vertices mapped by lo + v * step.  |offset| must be under the band: the field is flat beyond it."""
+        offset = float(offset)
+        if not abs(offset) < self.band:
+            raise L.GpnerfError(f"SdfGrid.offset_mesh: |offset| = {abs(offset)} is not under the band {self.band}: the field is flat there")
+        v, f = marching_cubes(-self.values, iso=-offset)
+        lo, step = (torch.from_numpy(a).to(v.device) for a in (self.lo, self.step))
+        return (lo + v.to(torch.float64) * step).to(torch.float32), f
+
+
+def mesh_sdf(vertices, faces, lo, step, dims, band, rule="nonzero", voxels=None, want_face=False):
+    """gpnerf_mesh_sdf: the truncated signed distance field of a mesh on the lattice of dims = (nx, ny, nz) POINTS at
+    lo + (i, j, k) * step, as an SdfGrid (everything on the device, nothing read back).  vertices, faces: as voxelize_mesh takes them.
+    band: metric, > 0, at most 1024 x the smallest step.  The sign is the lattice point's own occupancy: `voxels`, a VoxelGrid of the
+    same lattice, or -- voxels None -- voxelize_mesh under `rule` ("nonzero" / "parity"); rule=None gives the unsigned field.
+    include/gpnerf_hip.h states the definition: |value| and face equal point_mesh_distance(lattice points, max_dist=band) bit for
+    bit, with inf read as the band."""
+    lib = L.lib()
+    d = _voxel_dims(dims, "mesh_sdf")
+    lat = _voxel_lattice(lo, step, "mesh_sdf")
+    band32 = float(np.float32(band))
+    if not (np.isfinite(band32) and 0.0 < band32 <= L.SDF_MAX_BAND_STEPS * float(lat[3:].min())):
+        raise L.GpnerfError(f"mesh_sdf: band {band} refused (finite, > 0, at most {L.SDF_MAX_BAND_STEPS} x the smallest step {float(lat[3:].min())})")
+    vertices, faces = _raster_mesh(vertices, faces, "mesh_sdf")
+    dev = vertices.device
+    if voxels is not None:
+        if not isinstance(voxels, VoxelGrid):
+            raise L.GpnerfError("mesh_sdf: voxels must be a VoxelGrid")
+        _require_gpu(voxels.bits, "mesh_sdf: voxels")
+        if voxels.dims != d or voxels.bits.device != dev or not (np.array_equal(voxels.lo, lat[:3]) and np.array_equal(voxels.step, lat[3:])):
+            raise L.GpnerfError(f"mesh_sdf: the voxels live on another lattice (dims {voxels.dims}, lo {voxels.lo.tolist()}, step "
+                                f"{voxels.step.tolist()} on {voxels.bits.device})")
+    elif rule is not None:
+        if rule not in L.VOXEL_RULES:
+            raise L.GpnerfError(f"mesh_sdf: rule is 'nonzero', 'parity' or None, got {rule!r}")
+        voxels = voxelize_mesh(vertices, faces, lat[:3], lat[3:], d, rule=rule)
+    cd = (C.c_int32 * 3)(*d)
+    nv, nf = int(vertices.shape[0]), int(faces.shape[0])
+    nbytes = int(lib.gpnerf_mesh_sdf_workspace_bytes(nf, cd))
+    if nbytes <= 0:
+        raise L.GpnerfError(f"mesh_sdf: refused ({nf} faces, dims {d})")
+    ws = _workspace(dev, nbytes)                              # (the voxeliser's launches, if any, are in front of these on the stream)
+    values = torch.empty(d, device=dev, dtype=torch.float32)
+    face = torch.empty(d, device=dev, dtype=torch.int32) if want_face else None
+    stats = torch.empty((len(L.SDF_STATS),), device=dev, dtype=torch.int64)
+    ptr = lambda t: t.data_ptr() if t.numel() else None
+    L.check(lib.gpnerf_mesh_sdf(ptr(vertices), nv, ptr(faces), nf, lat.ctypes.data_as(L.DP), cd, band32,
+                                voxels.bits.data_ptr() if voxels is not None else None, ws.data_ptr(), ws.numel(), values.data_ptr(),
+                                face.data_ptr() if face is not None else None, stats.data_ptr(), _stream_ptr(dev)), "gpnerf_mesh_sdf")
+    return SdfGrid(values, face, voxels, lat[:3], lat[3:], d, band32, stats)

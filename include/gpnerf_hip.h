@@ -1215,6 +1215,97 @@ int gpnerf_voxel_stats(const uint32_t* a, const uint32_t* b, const int32_t* dims
 int gpnerf_voxel_contains(const uint32_t* bits, const int32_t* dims, const double* lattice, const float* points, int64_t n, uint8_t* out,
                           void* stream);
 
+/* ---- the truncated signed distance field of a mesh on a lattice (gpnerf_sdf.hip): at every lattice point the distance to the mesh
+ * where it is within a band, the band elsewhere, negative where the voxeliser's bit is set; and the trilinear value of such a field at
+ * points.  Marching cubes at an iso value of it is the surface at that metric offset from the mesh.  Mesh, lattice and dims as the
+ * voxeliser takes them (above).  Both entry points: kernel launches only, on the caller's stream; nothing allocated, nothing waited
+ * for; every launch sized from the arguments alone; the one data-dependent length (the large-face list's) stays on the device; every
+ * call captures into a HIP graph and replays with the same bytes; the result is a function of the inputs alone and of no launch
+ * geometry, of no arrival order and -- the face ids aside -- of no order of the faces (integer atomics only: a 64-bit minimum, integer sums).
+ *
+ * THE DEFINITION (gpnerf_mesh_sdf)
+ *   - lattice point (i, j, k) is the float32 point P with P_a = float32(lo_a + double(i_a) * step_a): product and sum in float64, one
+ *     rounding;
+ *   - a face is SKIPPED FOR A VERTEX under the voxeliser's rule extended to all three axes: an index outside [0, n_vertices), or a
+ *     vertex with a u_a = (p_a - lo_a) / step_a (float64, subtract then divide) that is not finite or has |u_a| > 2^16, on ANY axis;
+ *   - the BOX of every other face, per axis, float64: mn, mx = the least and largest of its three float32 coordinates,
+ *     i0 = ceil(((mn - band) - lo_a) / step_a) - 1, i1 = floor(((mx + band) - lo_a) / step_a) + 1, clipped to [0, n_a - 1]: the face's
+ *     extent widened by the band and ONE lattice step.  The face is SKIPPED FOR ITS BOX when the clipped range is empty on an axis
+ *     (it lies farther than the band from the lattice), otherwise it is USED;
+ *   - m(P) = the minimum over the USED faces of THE DISTANCE of gpnerf_mesh_distance (float32, unfused: the closest point of the
+ *     triangle relative to P, then sqrt of its dot product with itself); the face of P = the LOWEST index among the faces whose
+ *     distance has the same bits;
+ *   - if m(P) <= band: |sdf| = m(P) and face_id = that face; otherwise |sdf| = band and face_id = -1 (`<=`: the rule
+ *     gpnerf_mesh_distance has for max_dist);
+ *   - the sign: sdf = -|sdf| where the point's bit in `bits` is set -- negative inside, the usual convention; a point on the surface is
+ *     +0 or -0 by its bit.  The sign is the lattice point's own occupancy: it is known everywhere, beyond the band too, and it is
+ *     not an exact sign at distances under a step.  bits NULL: no value is negative (the unsigned field).
+ * For a mesh whose faces are all USED or SKIPPED FOR THEIR BOX, |sdf| and face_id at every lattice point EQUAL, bit for bit, what
+ * gpnerf_mesh_distance(P, max_dist = band) writes for the query P, in either of its forms, with +inf read as band (and its face -1):
+ * both translation units compile the same distance function (csrc/gpnerf_tridist.h).
+ * WHY NO POINT OUTSIDE A FACE'S BOX CAN HAVE A COMPUTED DISTANCE <= band.  Let P be a lattice point whose index on some axis a lies
+ * outside [i0, i1], say below: i <= ceil(x) - 2 < x - 1 with x = ((mn - band) - lo_a) / step_a, so lo_a + i step_a < mn - band - step_a
+ * (the float64 roundings of x move it by 2^-52 of its size).  The exact point therefore lies more than band + step_a from the face
+ * along axis a alone, and so does its true distance D.  Against that margin of one step stand (1) the rounding of P to float32, at
+ * most 2^-24 |P_a|: under 1/16 step wherever float32 resolves the lattice at all, |P_a| <= 2^20 step_a -- a lattice beyond that has
+ * neighbouring points that round to one float32 and no use for a distance to them --, and (2) the distance function's error, at most
+ * 2^-20 (D + diameter of the face) (gpnerf_mesh_distance, above): a usable face spans at most 2^17 steps per axis, a diameter under
+ * 2^18 steps of an isotropic lattice, so under 1/4 step + 2^-20 D.  A computed distance <= band would need D (1 - 2^-20) <= band +
+ * step_a (1/4 + 1/16 sqrt(3)) < band + 0.36 step_a, and D > band + step_a: it cannot, with more than half a step of room (band <=
+ * 1024 steps: 2^-20 D is under 0.001 step).  On a lattice whose steps differ the same holds while the face's diameter is under
+ * 2^19 of the SMALLEST steps, which every face of a mesh the lattice resolves is.  So the minimum over a point's boxes is the minimum
+ * over all USED faces wherever that is <= band, and elsewhere both are above it.
+ * Outputs.  sdf: device float [nx][ny][nz].  face_id: device int32 of the same shape, or NULL.  stats: device int64
+ * [GPNERF_SDF_STATS], set by the call: faces USED, SKIPPED_VERTEX, SKIPPED_BOX (their sum is n_faces); LARGE: the used faces that went
+ * through the list; IN_BAND: the lattice points with m <= band; INSIDE: the points whose bit is set; VISITED: the (face, point)
+ * pairs evaluated, i.e. the sum of the used faces' box sizes; PAIRS: those of them with a distance <= band, which bounds the atomics
+ * issued from above (the number issued depends on arrival order and is not counted).
+ * band: float, finite, > 0, at most 1024 x the smallest step.  bits: gpnerf_mesh_voxelize's packed occupancy for the same lattice and
+ * dims (device uint32 [nx][ny][ceil(nz / 32)]), or NULL.
+ * Launches: a clear (a kernel of the library's own: every key to all ones); one lane per face, which tests the face, computes its box
+ * and walks the box's points -- unless the box holds more than 64 points (one step of a wavefront): such a face is appended to a list
+ * in the workspace (one counter add per wavefront); a launch of fixed grid that reads the list's length on the device and gives each
+ * listed face a wavefront, 64 points of the box per step, z fastest; a resolve, one lane per lattice point, which turns key and bit
+ * into sdf and face_id and counts IN_BAND and INSIDE with one add per wavefront and counter.  At a point a lane evaluates the
+ * distance d, and where d <= band the point's uint64 key takes the unsigned MINIMUM with (bits(d) << 32) | face -- one atomic, no
+ * return value; d >= +0, so its bits order as the floats do, and the low word makes the lower face win a tie.  A relaxed read of
+ * the key first skips the atomic where the key is already as low: keys only fall, so a stale read can only let a needless atomic
+ * through.  With a band of a few steps every face of a body-sized mesh (faces of about a step) is in the wavefront tier.
+ * workspace: gpnerf_mesh_sdf_workspace_bytes(n_faces, dims) bytes (host arithmetic only; 0 for what the call refuses) =
+ * 256 + align256(8 nx ny nz) + align256(4 n_faces): the header, a key per lattice point, the list at its worst.  It carries nothing
+ * from call to call.
+ * GPNERF_E_ARG, before anything is launched: everything gpnerf_mesh_voxelize refuses of the arguments they share (null lattice, dims,
+ * workspace or stats; null vertices with n_vertices > 0 or faces with n_faces > 0; a count that is negative or >= 2^31; a dims entry
+ * < 1 or a product > 2^28; a lattice entry that is not finite or a step that is not > 0; a workspace under the formula); a null sdf;
+ * a band that is NaN, infinite, <= 0 or above 1024 x the smallest step.
+ *
+ * gpnerf_sdf_sample(sdf, dims, lattice, points, n, out, stream): the trilinear value of a field (device float [nx][ny][nz], dims each
+ * >= 2) at device float [n][3] points, into device float [n]; one lane per point.  Per axis, float64: u_a = (p_a - lo_a) / step_a
+ * (subtract, then divide); the result is NaN when a coordinate is not finite or a u_a lies outside [0, n_a - 1]; the cell is
+ * c_a = floor(u_a), lowered to n_a - 2 where u_a == n_a - 1, and t_a = u_a - c_a.  The eight corners, widened to float64, are
+ * interpolated along z, then y, then x, each time as a + t (b - a), unfused; the result is rounded once to float32.  At a lattice
+ * point every t is 0 (or 1 in the last cell, where a + (b - a) gives b back for any two floats with |a| < 2^29 |b| or b = 0) and the
+ * stored value comes back (a stored -0 as +0).  Values beyond the band are the band's: the interpolant saturates there.
+ * 0 <= n < 2^31; points and out may be NULL where n is 0 (nothing is launched).  GPNERF_E_ARG: a null sdf, dims or lattice, a dims
+ * entry < 2 or a product > 2^28, a lattice entry that is not finite or a step that is not > 0, an n outside its range. */
+#define GPNERF_SDF_USED 0
+#define GPNERF_SDF_SKIPPED_VERTEX 1
+#define GPNERF_SDF_SKIPPED_BOX 2
+#define GPNERF_SDF_LARGE 3
+#define GPNERF_SDF_IN_BAND 4
+#define GPNERF_SDF_INSIDE 5
+#define GPNERF_SDF_VISITED 6
+#define GPNERF_SDF_PAIRS 7
+#define GPNERF_SDF_STATS 8
+#define GPNERF_SDF_LARGE_POINTS 64
+#define GPNERF_SDF_MAX_BAND_STEPS 1024
+size_t gpnerf_mesh_sdf_workspace_bytes(int64_t n_faces, const int32_t* dims);
+int gpnerf_mesh_sdf(const float* vertices, int64_t n_vertices, const int32_t* faces, int64_t n_faces, const double* lattice,
+                    const int32_t* dims, float band, const uint32_t* bits, void* workspace, size_t workspace_bytes, float* sdf,
+                    int32_t* face_id, int64_t* stats, void* stream);
+int gpnerf_sdf_sample(const float* sdf, const int32_t* dims, const double* lattice, const float* points, int64_t n, float* out,
+                      void* stream);
+
 /* ---- per-frame sparse convolution pyramid (gpnerf_volume.hip), replacing the external spconv v1.2.1 calls of
  * libs/nerfheads/networks/SparseConvNet.py:22-111 (SubMConv3d / SparseConv3d + BatchNorm1d + ReLU, .dense()).
  * A sparse tensor is: features [M][C] fp32, coords [M][3] int32 (d,h,w), and a dense int32 index grid [D][H][W]
