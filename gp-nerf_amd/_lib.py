@@ -183,6 +183,10 @@ VOXEL_MAX_POINTS = 1 << 28
 SDF_STATS = ("used", "skipped_vertex", "skipped_box", "large", "in_band", "inside", "visited", "pairs")
 SDF_LARGE_POINTS = 64
 SDF_MAX_BAND_STEPS = 1024
+# gpnerf_mesh_raycast's modes and gpnerf_pixel_rays' limit on the cameras (include/gpnerf_hip.h GPNERF_RAYCAST_*)
+RAYCAST_NEAREST, RAYCAST_ANY = range(2)
+RAYCAST_MODES = {"nearest": RAYCAST_NEAREST, "any": RAYCAST_ANY}
+RAYCAST_MAX_VIEWS = 8
 # gpnerf_conv_variant's row and its kernel families (include/gpnerf_hip.h GPNERF_CONV_*)
 CONV_VARIANT = ("family", "cot", "rw", "ksplit", "cat", "tiles", "tile_h", "tile_w")
 CONV_FAMILIES = ("REFUSED", "DIRECT_1X1", "DIRECT_NARROW3", "TILED_S1", "TILED_S2", "STEM")
@@ -340,6 +344,9 @@ SYMBOLS = {
     "gpnerf_mesh_sdf": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, DP, C.POINTER(C.c_int32), C.c_float, C.c_void_p, C.c_void_p,
                                   C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gpnerf_sdf_sample": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), DP, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "gpnerf_mesh_raycast": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p,
+                                      C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gpnerf_pixel_rays": (C.c_int, [DP, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_void_p, C.c_void_p]),
     "gpnerf_head_layout": (C.c_int, [C.POINTER(C.c_int32)]),
     "gpnerf_strerror": (C.c_char_p, [C.c_int]),
     "gpnerf_rays_per_tile": (C.c_int32, []),

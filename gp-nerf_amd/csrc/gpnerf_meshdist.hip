@@ -25,49 +25,14 @@ namespace {
 #include "gpnerf_util.h"       // align256, S_, launch_status, blocks_for
 #include "gpnerf_tridist.h"    // V3, Best, closest_on_triangle, test_face, face_valid: THE distance and its tie rule
 
+#include "gpnerf_meshgrid.h"   // GridLayout, grid_layout, Grid, grid_of, cell_of: the grid's layout, shared with gpnerf_raycast.hip
+
 constexpr int THREADS = 256;
-constexpr int BOX_BLOCKS_MAX = 1024;                     // partial boxes of the reduction
 constexpr int SCAN_THREADS = 1024;
 constexpr int STAT_THREADS = 256;
-constexpr int MAX_AXIS_CELLS = 1024;                     // per axis: the shell bound's rounding argument relies on it
 constexpr int64_t MAX_CELL_CAP = (int64_t)1 << 24, MAX_ENTRY_CAP = (int64_t)1 << 30, MAX_FACES = INT32_MAX;
-constexpr int32_t GRID_MAGIC = 0x47524431;               // "GRD1"
 constexpr int SAMPLE_CHUNK = 1024;                       // faces per block of the area scan (4 per thread)
 constexpr int TILE = 256;                                // faces per LDS tile of the brute-force form
-
-struct GridLayout { size_t hdr, part, start, cursor, entries, tmp_face, tmp_cell, total; };
-
-__host__ __device__ inline GridLayout grid_layout(int64_t cell_cap, int64_t entry_cap) {
-    GridLayout l;
-    size_t o = 0;
-    l.hdr = o;      o += 256;
-    l.part = o;     o += align256(sizeof(float) * 8 * BOX_BLOCKS_MAX);
-    l.start = o;    o += align256(sizeof(int32_t) * (size_t)(cell_cap + 1));
-    l.cursor = o;   o += align256(sizeof(int32_t) * (size_t)cell_cap);
-    l.entries = o;  o += align256(sizeof(int32_t) * (size_t)entry_cap);
-    l.tmp_face = o; o += align256(sizeof(int32_t) * (size_t)entry_cap);
-    l.tmp_cell = o; o += align256(sizeof(int32_t) * (size_t)entry_cap);
-    l.total = o;
-    return l;
-}
-
-struct Grid {                                            // the workspace's regions, as the kernels see them
-    int32_t* hdr; float* part; int32_t* start; int32_t* cursor; int32_t* entries; int32_t* tmp_face; int32_t* tmp_cell;
-};
-
-__host__ __device__ inline Grid grid_of(void* workspace, int64_t cell_cap, int64_t entry_cap) {
-    const GridLayout l = grid_layout(cell_cap, entry_cap);
-    char* base = static_cast<char*>(workspace);
-    Grid g;
-    g.hdr = reinterpret_cast<int32_t*>(base + l.hdr);
-    g.part = reinterpret_cast<float*>(base + l.part);
-    g.start = reinterpret_cast<int32_t*>(base + l.start);
-    g.cursor = reinterpret_cast<int32_t*>(base + l.cursor);
-    g.entries = reinterpret_cast<int32_t*>(base + l.entries);
-    g.tmp_face = reinterpret_cast<int32_t*>(base + l.tmp_face);
-    g.tmp_cell = reinterpret_cast<int32_t*>(base + l.tmp_cell);
-    return g;
-}
 
 bool grid_sizes_ok(int64_t n_faces, int64_t cell_cap, int64_t entry_cap) {
     return n_faces >= 1 && n_faces <= MAX_FACES && cell_cap >= 1 && cell_cap <= MAX_CELL_CAP && entry_cap >= 1 && entry_cap <= MAX_ENTRY_CAP;
@@ -106,12 +71,6 @@ DEV void write_nan(long i, float* dist, int32_t* face, float* closest, float* co
 }
 
 // ---------------------------------------------------------------- the grid
-
-// the cell of a coordinate on one axis: monotone in x, clamped, never out of range (the clamp is taken in float: no int overflow)
-DEV int cell_of(float x, float lo, float inv, int n) {
-    const float t = floorf((x - lo) * inv);
-    return (int)fminf(fmaxf(t, 0.f), (float)(n - 1));
-}
 
 __global__ __launch_bounds__(THREADS) void grid_box_kernel(const float* __restrict__ vertices, int64_t n_vertices,
                                                            const int32_t* __restrict__ faces, long n_faces, int64_t cell_cap, Grid g) {

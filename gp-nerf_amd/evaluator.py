@@ -291,13 +291,23 @@ class MeshEvaluator:
     and `signed_outside_lattice` (samples outside the padded lattice, which take no part), their per-frame lists, and saves
     `<result_path>/signed_metrics.npy`.  Values beyond the band saturate at +-band, so `signed_mean` is a truncated mean: it is the
     true signed mean while the surfaces are within the band of each other, and an under-estimate in size (never in sign) beyond.
-    Off, nothing changes."""
+    Off, nothing changes.
+    visible (off by default; the visible-surface error depth evaluations report -- P2S and Chamfer average over hidden surface too):
+    it needs `gt_mesh` in the batch, `axes` in the output and the `hull_masks` / `hull_Ks` / `hull_RTs` keys `silhouette` uses (only
+    the masks' size is read).  `evaluate` casts the hull cameras' pixel rays (frame.pixel_rays at the masks' size) against the
+    predicted mesh (`to_lattice_frame`) and against the scan, each through its own grid (frame.raycast_mesh), forms |t_pred - t_gt|
+    on the device -- NaN where neither is hit, +inf where exactly one is -- and reduces it with frame.distance_stats into a slot: no
+    host read.  `summarize()` reads the slots in one copy and adds `visible_depth_mean`, `visible_depth_rms`, `visible_depth_max`
+    (camera depth, the meshes' unit, over the pixels where both are hit; means over the frames, the max over them),
+    `visible_hit_disagreement` (the share of the pixels hit by exactly one mesh among those hit by either), their per-frame lists,
+    and saves `<result_path>/visible_metrics.npy`.  A `gt_mesh` with an output that has no `axes`, or a batch without one of the
+    three keys, raises a GpnerfError naming the key.  Off, nothing changes."""
     PAD = 10                              # if_nerf_mesh.py:20, the np.pad(cube, 10) of BaseRender.py:269
 
     def __init__(self, result_path, mesh_th, export_mesh=False, metric_samples=100000, metric_thresholds=(0.005, 0.01, 0.02),
                  metric_max_dist=float("inf"), metric_device=None, metric_cell_cap=None, metric_entry_cap=None, silhouette=False,
                  topology=False, volume=False, volume_rule="nonzero", components=False, align=None, align_iterations=10,
-                 align_max_dist=float("inf"), signed=False, signed_band=8):
+                 align_max_dist=float("inf"), signed=False, signed_band=8, visible=False):
         self.mesh_th = mesh_th
         self.export_mesh = bool(export_mesh)
         self.result_path = result_path
@@ -325,6 +335,8 @@ class MeshEvaluator:
         if not 0.0 < self.signed_band <= L.SDF_MAX_BAND_STEPS:
             raise L.GpnerfError(f"MeshEvaluator: signed_band is in lattice steps, > 0 and at most {L.SDF_MAX_BAND_STEPS}, got {signed_band!r}")
         self._signed_slots, self._signed_frames = [], []
+        self.visible = bool(visible)
+        self._visible_slots, self._visible_frames = [], []
 
     SILHOUETTE_KEYS = ("hull_masks", "hull_Ks", "hull_RTs")
 
@@ -333,7 +345,7 @@ class MeshEvaluator:
         """True once a frame with `gt_mesh` (or, with silhouette on, with masks and cameras; or any frame with topology or components on) has been evaluated and not yet summarized
         (evaluate_loop asks)"""
         return (bool(self._slots) or bool(self._sil_slots) or bool(self._topo_slots) or bool(self._vol_slots) or bool(self._comp_slots) or
-                bool(self._signed_slots))
+                bool(self._signed_slots) or bool(self._visible_slots))
 
     def _padded_lattice(self, axes):
         """(lo, step, dims) of the frame's padded cube lattice in the axes' frame: to_lattice_frame's steps, PAD points around"""
@@ -373,6 +385,54 @@ class MeshEvaluator:
         np.save(os.path.join(self.result_path, "signed_metrics.npy"), table)        # a structured array: one row per frame
         print(f"signed_mean: {metrics['signed_mean']} (inside_fraction {metrics['inside_fraction']})")
         self._signed_slots, self._signed_frames = [], []
+        return metrics, per_frame
+
+    def _enqueue_visible(self, output, batch):
+        from . import frame as F
+        if "axes" not in output:
+            raise L.GpnerfError("MeshEvaluator(visible=True): the output has no 'axes', so its mesh cannot be put into the cameras' frame "
+                                "(the inference renderer's render_mesh; the dense renderer's geometry mode returns axes)")
+        missing = [k for k in self.SILHOUETTE_KEYS if k not in batch]
+        if missing:
+            raise L.GpnerfError(f"MeshEvaluator(visible=True): the batch has no {', '.join(repr(k) for k in missing)} (the cameras and masks "
+                                "of the dense renderer's geometry mode: hull_masks [1,n,h,w], hull_Ks [1,n,3,3], hull_RTs [1,n,3,4])")
+        shape = tuple(batch["hull_masks"].shape)
+        if len(shape) != 4:
+            raise L.GpnerfError(f"MeshEvaluator(visible=True): hull_masks must be [1,n,h,w], got {shape}")
+        dev = torch.device(self.metric_device if self.metric_device is not None else "cuda:0")
+        Ks, RTs = F.fetch_host(batch["hull_Ks"][0], batch["hull_RTs"][0])
+        rays = F.pixel_rays(Ks, RTs, int(shape[2]), int(shape[3]), device=dev)
+        depth = []
+        for mesh in (output["mesh"].to_lattice_frame(output["axes"], self.PAD), batch["gt_mesh"]):
+            v, f = F.mesh_to_device(mesh, dev)
+            grid = F.build_mesh_grid(v, f, cell_cap=self.metric_cell_cap, entry_cap=self.metric_entry_cap, check=False)
+            depth.append(F.raycast_mesh(rays, grid=grid)["t"])
+        # inf - inf is NaN (neither hit), inf - finite is inf (exactly one): distance_stats counts the three kinds apart
+        self._visible_slots.append(F.distance_stats((depth[0] - depth[1]).abs().reshape(-1)))
+        self._visible_frames.append(self._scalar(batch["frame_index"]))
+
+    def _summarize_visible(self):
+        """the visible-surface slots -> (means, per-frame lists), visible_metrics.npy written; resets them"""
+        host = torch.stack(self._visible_slots).cpu().numpy()   # the one read
+        both, one, neither = host[:, L.DIST_FINITE], host[:, L.DIST_INF], host[:, L.DIST_NAN]
+        with np.errstate(divide="ignore", invalid="ignore"):
+            disagreement = one / (both + one)
+        per_frame = {"visible_depth_mean": [float(x) for x in host[:, L.DIST_MEAN]],
+                     "visible_depth_rms": [float(x) for x in np.sqrt(host[:, L.DIST_MEAN_SQ])],
+                     "visible_depth_max": [float(x) for x in host[:, L.DIST_MAX]],
+                     "visible_hit_disagreement": [float(x) for x in disagreement]}
+        metrics = {k: float(np.max(v) if k == "visible_depth_max" else np.mean(v)) for k, v in per_frame.items()}
+        per_frame["visible_frame_index"] = list(self._visible_frames)
+        table = np.zeros(len(host), dtype=[("frame_index", "i8"), ("pixels_both", "i8"), ("pixels_one", "i8"), ("pixels_neither", "i8"),
+                                           ("depth_mean", "f8"), ("depth_rms", "f8"), ("depth_max", "f8"), ("hit_disagreement", "f8")])
+        table["frame_index"] = self._visible_frames
+        table["pixels_both"], table["pixels_one"], table["pixels_neither"] = both, one, neither
+        table["depth_mean"], table["depth_rms"], table["depth_max"] = host[:, L.DIST_MEAN], np.sqrt(host[:, L.DIST_MEAN_SQ]), host[:, L.DIST_MAX]
+        table["hit_disagreement"] = disagreement
+        os.makedirs(self.result_path, exist_ok=True)
+        np.save(os.path.join(self.result_path, "visible_metrics.npy"), table)       # a structured array: one row per frame
+        print(f"visible_depth_mean: {metrics['visible_depth_mean']} (hit disagreement {metrics['visible_hit_disagreement']})")
+        self._visible_slots, self._visible_frames = [], []
         return metrics, per_frame
 
     def _enqueue_volume(self, output, batch):
@@ -482,6 +542,8 @@ class MeshEvaluator:
                 self._enqueue_volume(output, batch)
             if self.signed:
                 self._enqueue_signed(output, batch)
+            if self.visible:
+                self._enqueue_visible(output, batch)
         if self.silhouette and all(k in batch for k in self.SILHOUETTE_KEYS):
             self._enqueue_silhouette(output, batch)
         if self.topology:
@@ -575,10 +637,10 @@ class MeshEvaluator:
         return metrics, per_frame
 
     def summarize(self):
-        if self._sil_slots or self._topo_slots or self._vol_slots or self._comp_slots or self._signed_slots:
+        if self._sil_slots or self._topo_slots or self._vol_slots or self._comp_slots or self._signed_slots or self._visible_slots:
             parts = (([self._summarize_silhouettes()] if self._sil_slots else []) + ([self._summarize_topology()] if self._topo_slots else []) +
                      ([self._summarize_volumes()] if self._vol_slots else []) + ([self._summarize_components()] if self._comp_slots else []) +
-                     ([self._summarize_signed()] if self._signed_slots else []))
+                     ([self._summarize_signed()] if self._signed_slots else []) + ([self._summarize_visible()] if self._visible_slots else []))
             metrics = self._summarize_mesh_metrics() if self._slots else {"per_frame": {}}
             per_frame = metrics.pop("per_frame")
             for means, frames in parts:

@@ -2101,3 +2101,80 @@ def mesh_sdf(vertices, faces, lo, step, dims, band, rule="nonzero", voxels=None,
                                 voxels.bits.data_ptr() if voxels is not None else None, ws.data_ptr(), ws.numel(), values.data_ptr(),
                                 face.data_ptr() if face is not None else None, stats.data_ptr(), _stream_ptr(dev)), "gpnerf_mesh_sdf")
     return SdfGrid(values, face, voxels, lat[:3], lat[3:], d, band32, stats)
+
+
+# ---- casting rays against a mesh (csrc/gpnerf_raycast.hip)
+
+def _rays(t, what):
+    if not isinstance(t, torch.Tensor):
+        raise L.GpnerfError(f"{what} must be a device tensor")
+    _require_gpu(t, what)
+    if t.dtype != torch.float32 or t.dim() < 1 or t.shape[-1] != 8 or not t.is_contiguous():
+        raise L.GpnerfError(f"{what}: expected a contiguous float32 [...,8] tensor of (o, d, tmin, tmax) rows, got {t.dtype} {tuple(t.shape)}")
+    return t
+
+
+def raycast_mesh(rays, vertices=None, faces=None, grid=None, mode="nearest", want_bary=False):
+    """gpnerf_mesh_raycast: what each ray of a device float32 [...,8] list of (o, d, tmin, tmax) rows -- make_rays' and render_fused's
+    layout, d as given, so t is the renderer's depth -- hits of the mesh -> {"t" [...], "face" int32 [...], "bary" [...,2]}.
+    mode "nearest": the smallest t in [tmin, tmax] (+inf: none; NaN: a ray that is not one), its face (the lowest index among equal
+    t, -1: none) and, with want_bary, the hit's barycentric weights of the face's second and third vertex.  mode "any": t = 0 where
+    some face lies in [tmin, tmax] and +inf where none does -- a shadow ray; which face it names depends on the form.
+    grid: a MeshGrid (its mesh is used) selects the walk through the grid; without one, `vertices` and `faces` go through the
+    brute-force form; the two agree bit for bit.  Nothing is read back."""
+    lib = L.lib()
+    if mode not in L.RAYCAST_MODES:
+        raise L.GpnerfError(f"raycast_mesh: mode is 'nearest' or 'any', got {mode!r}")
+    if grid is not None:
+        if not isinstance(grid, MeshGrid):
+            raise L.GpnerfError("raycast_mesh: grid must be a MeshGrid (build_mesh_grid)")
+        vertices, faces = grid.vertices, grid.faces
+    nv, nf = _mesh_tensors(vertices, faces, "raycast_mesh")
+    rays = _rays(rays, "raycast_mesh: rays")
+    if rays.device != vertices.device:
+        raise L.GpnerfError("raycast_mesh: rays and mesh are on different devices")
+    shape, dev = tuple(rays.shape[:-1]), rays.device
+    n = int(np.prod(shape, dtype=np.int64))
+    res = {"t": torch.empty(shape, device=dev, dtype=torch.float32), "face": torch.empty(shape, device=dev, dtype=torch.int32)}
+    if want_bary:
+        res["bary"] = torch.empty(shape + (2,), device=dev, dtype=torch.float32)
+    ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None
+    L.check(lib.gpnerf_mesh_raycast(ptr(rays), n, vertices.data_ptr() or faces.data_ptr(), nv, faces.data_ptr(), nf,
+                                    grid.workspace.data_ptr() if grid is not None else None, L.RAYCAST_MODES[mode], ptr(res["t"]),
+                                    ptr(res["face"]), ptr(res.get("bary")), _stream_ptr(dev)), "gpnerf_mesh_raycast")
+    return res
+
+
+def pixel_rays(Ks, RTs, H, W, z_near=1e-6, device=None):
+    """gpnerf_pixel_rays: the rays through the pixel centres of the cameras Ks [n,3,3], RTs [n,3,4] (host arrays, used in float64;
+    rasterize_mesh's cameras and pixel convention) -> device float32 [n,H,W,8] rows (o, d, z_near, +inf) with d's camera-z component 1:
+    raycast_mesh's t along them is the camera depth rasterize_mesh draws.  device: where the rays go (default cuda:0)."""
+    lib = L.lib()
+    cams = _raster_cams(Ks, RTs, "pixel_rays")
+    dev = torch.device(device if device is not None else "cuda:0")
+    if dev.type != "cuda":
+        raise L.GpnerfError(f"pixel_rays: the rays must live on the GPU (got {dev}); the HIP path has no CPU fallback")
+    n, H, W = cams.shape[0], int(H), int(W)
+    if not (1 <= H <= 16384 and 1 <= W <= 16384):
+        raise L.GpnerfError(f"pixel_rays: refused ({n} views, {H} x {W})")
+    rays = torch.empty((n, H, W, 8), device=dev, dtype=torch.float32)
+    L.check(lib.gpnerf_pixel_rays(cams.ctypes.data_as(L.DP), n, H, W, float(z_near), rays.data_ptr(), _stream_ptr(dev)), "gpnerf_pixel_rays")
+    return rays
+
+
+def mesh_visibility(points, eyes, vertices=None, faces=None, grid=None, eps=1e-4):
+    """Which of the device float32 points [n,3] each of the eyes [m,3] (device float32, or host numbers) sees past the mesh ->
+    device uint8 [n,m], 1 where nothing lies between.  One "any" ray per pair: o = p, d = eye - p, tmin = eps, tmax = 1, so the
+    segment from just off the point to the eye; eps (a fraction of the segment) keeps a point ON the mesh from being hidden by its
+    own faces.  The rows are composed by torch; the cast is raycast_mesh's.  Nothing is read back."""
+    points = _points(points, "mesh_visibility: points")
+    dev = points.device
+    eyes = torch.as_tensor(eyes, dtype=torch.float32).to(dev).reshape(-1, 3)
+    n, m = int(points.shape[0]), int(eyes.shape[0])
+    rows = torch.empty((n, m, 8), device=dev, dtype=torch.float32)
+    rows[..., 0:3] = points[:, None, :]
+    rows[..., 3:6] = eyes[None, :, :] - points[:, None, :]
+    rows[..., 6] = float(eps)
+    rows[..., 7] = 1.0
+    t = raycast_mesh(rows, vertices, faces, grid=grid, mode="any")["t"]
+    return (t > 0).to(torch.uint8)

@@ -1306,6 +1306,115 @@ int gpnerf_mesh_sdf(const float* vertices, int64_t n_vertices, const int32_t* fa
 int gpnerf_sdf_sample(const float* sdf, const int32_t* dims, const double* lattice, const float* points, int64_t n, float* out,
                       void* stream);
 
+/* ---- casting rays against a mesh (gpnerf_raycast.hip): what does a ray hit?  The nearest face of a triangle mesh along each ray of a
+ * list in the renderer's row layout, so that a mesh's depth compares element for element with a rendered depth; whether anything lies
+ * between two points (visibility, shadow and occlusion rays); and the rays through the pixel centres of calibrated cameras.  Both entry
+ * points: kernel launches only, on the caller's stream; nothing allocated, nothing waited for; every launch sized from the arguments
+ * alone; NO atomics; every call captures into a HIP graph and replays with the same bytes; the result is a function of the inputs alone.
+ * A mesh is gpnerf_mesh_distance's: vertices device float [n_vertices][3], faces device int32 [n_faces][3], 1 <= n_faces < 2^31; a face
+ * with an index outside [0, n_vertices) or a non-finite vertex is INVALID: skipped, never dereferenced.  A ray is a row of eight floats
+ * (o[3], d[3], tmin, tmax): the points o + t d, tmin <= t <= tmax, d as given and NOT normalised, so t is the renderer's z_vals / depth.
+ *
+ * THE INTERSECTION of a ray with a triangle (a, b, c), the one __device__ function both forms use (gpnerf_raytri.h), in float32,
+ * unfused: the watertight test of Woop, Benthin and Wald (JCGT 2013).
+ *   - axes: kz = the axis of the largest |d|, the lowest index on a tie; kx = (kz + 1) % 3, ky = (kx + 1) % 3, the two swapped when
+ *     d[kz] < 0;  Sx = d[kx] / d[kz], Sy = d[ky] / d[kz], Sz = 1 / d[kz];
+ *   - the vertices relative to the origin, A = a - o (one rounding per component), sheared: Ax = A[kx] - Sx A[kz], Ay = A[ky] - Sy
+ *     A[kz], Az = Sz A[kz]; the same for B and C;
+ *   - edge functions f(P, Q) = Px Qy - Py Qx:  U = f(C, B), V = f(A, C), W = f(B, A).  If any of the three is exactly 0, all three are
+ *     recomputed in float64 from the float32 sheared coordinates (both products are exact there, so the signs are exact); the miss
+ *     test below reads the float64 values, which are then rounded to float32;
+ *   - MISS when one of U, V, W is < 0 and another is > 0 (no back-face culling);  det = (U + V) + W, MISS when det == 0;
+ *   - T = (U Az + V Bz) + W Cz, t = T / det;  HIT iff tmin <= t <= tmax (both ends inclusive; a NaN fails);  the barycentric weights
+ *     of b and c are V / det and W / det.
+ * It is watertight: f is exactly antisymmetric in float32 and a nonzero float32 sign is the exact sign, so a face is accepted iff the
+ * ray lies in the CLOSED exact triangle of its float32 sheared vertices, and two faces that share an edge or a vertex share those
+ * vertices bit for bit: no gap between them (gpnerf_raytri.h carries the argument).
+ *
+ * gpnerf_mesh_raycast(rays, n_rays, vertices, n_vertices, faces, n_faces, grid_workspace, mode, t, face, bary, stream): for each of the
+ * device float [n_rays][8] rays, with mode GPNERF_RAYCAST_NEAREST:
+ *   t (device float [n]): the minimum over the valid faces that THE INTERSECTION accepts of its t;  face (device int32 [n]): the face
+ *   that attains it, the LOWEST index among faces at bit-equal t;  bary (device float [n][2] or NULL): that face's weights of b and c.
+ *   - no face accepted: t = +inf, face = -1, bary NaN;
+ *   - a ray with a non-finite component of o or d, d = 0, a NaN bound, or tmin > tmax: t = NaN, face = -1, bary NaN (infinite bounds
+ *     are legal);
+ *   - GPNERF_RAYCAST_ANY stops at the first accepted face: t = 0 for such a ray (occluded) and +inf for a free one, face = the face
+ *     it stopped at (-1 when free), bary NaN.  WHETHER a ray is occluded is the same in both forms and equals "NEAREST hits"; WHICH
+ *     face is reported depends on the order the form meets the faces in (the brute-force form: the lowest index; the grid form: the
+ *     first in walk order) -- a function of the inputs all the same;
+ *   - grid_workspace NULL selects the BRUTE-FORCE form: the faces staged through LDS in tiles of 256, every ray against every face.
+ *     One launch.  It is the on-device cross-check and the right form for small meshes;
+ *   - grid_workspace: a workspace gpnerf_mesh_grid_build has filled FOR THE SAME vertices, faces and n_faces.  Two launches: the
+ *     faces' largest cell span per axis (below; written into the first three words of each row of the workspace's partial boxes,
+ *     which the build has finished with -- the only thing the call writes there), then THE WALK, one ray per lane.  A grid whose
+ *     status is not OK makes every t NaN (face -1, bary NaN) and is neither read nor written;
+ *   - t, face and bary of the two forms are EQUAL BIT FOR BIT (NEAREST);
+ *   - GPNERF_E_ARG, before any device call: n_rays < 0, n_vertices < 0, n_faces < 1 or >= 2^31, null vertices or faces, a mode that is
+ *     neither of the two, and (with n_rays > 0) null rays, t or face.  n_rays == 0 is a no-op.
+ *
+ * THE WALK.  Notation: u = 2^-24; lo, size, n: the grid's; r_k(x) = (x - lo_k) / size_k, a coordinate in cells; rho_k(s) = r_k(o_k + s
+ * d_k), the ray in cells; z = kz, the axis of the largest |d|, x and y the other two; zeta(s) = rho_z(s) where d_z > 0 and n_z - rho_z(s)
+ * where d_z < 0, which grows with s; slab j is the layer of cells with index j on z counted in the direction of travel.  R = max over
+ * the axes of |o_k - lo_k| + 1.001 n_k size_k, which bounds |v_k - o_k| for every valid vertex v (all lie in the grid's box).
+ * pad_k = 2^-20 R / size_k + 2^-11, in cells.  span_z = the largest cell(max corner) - cell(min corner) on z over the valid faces.
+ * The walk's own arithmetic is float64 (its rounding, 2^-52 of quantities no larger than R / size_k, vanishes in the pads).
+ *   1. [b0, b1] = the parameters at which the ray is inside the box padded by pad_k on every axis (an axis with d_k = 0 either
+ *      contains the ray or ends the walk).  Empty: no hit.
+ *   2. The slabs j = first .. last in order, first = max(floor(zeta(b0) - pad_z), floor(zeta(tmin) - pad_z) - span_z, 0), last =
+ *      min(floor(zeta(b1) + pad_z), n_z - 1).
+ *   3. Before slab j: stop if j > floor(zeta(min(tmax, best)) + pad_z) + span_z, best = the smallest t accepted so far (+inf: none).
+ *   4. In slab j, of cell index c on z: sa, sb = the parameters at which rho_z = c - 2^-11 and c + 1 + 2^-11; on x the cells
+ *      clamp(floor(min(rho_x(sa), rho_x(sb)) - pad_x)) .. clamp(floor(max(..) + pad_x)), the same on y; every face entered in every
+ *      cell of that rectangle is tested with THE INTERSECTION and the tie rule.  No "the hit lies in this cell" test: the minimum is
+ *      idempotent, a face met twice is harmless.
+ * Cost: a ray whose direction lies along a cell diagonal covers two cells per axis in a slab, four cells where an exact 3-D DDA
+ * (Amanatides and Woo) would visit about three in all, and span_z more slabs at the end.  That is the price of the proof.
+ *
+ * THE BOUND: no face the walk has not tested is accepted with t <= the result.  Proof, for a valid face F that THE INTERSECTION accepts
+ * with computed t_F; M <= R bounds its |vertex - o|; barring underflow.
+ *   (a) Sideways.  By watertightness the origin of the sheared plane lies in the closed exact triangle of F's float32 sheared
+ *       vertices, with exact weights w >= 0, sum 1.  A computed sheared coordinate differs from the exact one of the exact vertex by
+ *       at most 6 u M (u M in A[kx], 3 u M in Sx A[kz], 2 u M in the difference).  So P = sum w_i v_i, a point OF F, has exact
+ *       sheared coordinates within 6 u M of 0: with s = (P_z - o_z) / d_z, the ray's point o + s d equals P on z and is within
+ *       6 u M of it on x and y.
+ *   (b) Where P is filed.  P lies in F's bounding box, and cell() is monotone, so on every axis cell(P_k) lies in F's range of cells:
+ *       F is entered in the cell (cell(P_x), cell(P_y), cell(P_z)).  cell()'s argument as computed is r_k (1 + e), |e| <= 3 u, of
+ *       magnitude at most 1025: within 2^-12 of r_k(P_k) (4.10's argument).  Hence rho_z(s) = r_z(P_z) lies in [c - 2^-12, c + 1 +
+ *       2^-12], c = cell(P_z): s lies between step 4's sa and sb for that slab; and the value cell(P_x) floors lies within
+ *       6 u M / size_x + 2^-12 < pad_x of rho_x(s), which lies between rho_x(sa) and rho_x(sb): cell(P_x) is in step 4's range,
+ *       the clamps being the same on both sides.  The same on y.  So F IS TESTED WHEN THE WALK VISITS THE SLAB OF P.  That slab is
+ *       within first .. last as far as the box goes: P is in the box, so the ray is in the padded box at s, b0 <= s <= b1.
+ *   (c) Along the ray.  t_F is NOT s: with U, V, W of one sign, t_F = sum w'_i Z_i (1 + e_i), |e_i| <= 6 u, for the COMPUTED weights w'
+ *       (>= 0, sum 1), Z_i = the computed Az, Bz, Cz = (v_i - o)_z / d_z (1 + 3 u).  The computed weights of a small or thin triangle
+ *       far from the origin can be far from w (the edge functions cancel), so all that holds is: zeta(t_F) lies within 10 u M /
+ *       size_z < pad_z of the interval F's vertices span on zeta.  The slab of P lies in the same interval, at most span_z slabs
+ *       long.  So  floor(zeta(t_F) - pad_z) - span_z  <=  slab of P  <=  floor(zeta(t_F) + pad_z) + span_z.
+ *   (d) tmin <= t_F gives slab of P >= floor(zeta(tmin) - pad_z) - span_z: P's slab is not in front of `first`.  If F is untested when
+ *       the walk stops before slab j (step 3), or at `last` with j = last + 1, the slab of P is >= j (all earlier ones were visited),
+ *       so floor(zeta(t_F) + pad_z) >= j - span_z > floor(zeta(min(tmax, best)) + pad_z): zeta(t_F) > zeta(min(tmax, best)), and
+ *       zeta grows with the parameter: t_F > tmax (not accepted after all) or t_F > best -- it neither beats nor ties.  Past `last`
+ *       there is no P.  Hence t and face equal the brute-force form's bit for bit, and an ANY ray is occluded in one form iff in
+ *       the other.
+ *
+ * gpnerf_pixel_rays(cams, n_views, H, W, z_near, rays, stream): the rays through the pixel centres of calibrated cameras, rays: device
+ * float [n_views][H][W][8].  cams: HOST double [n_views][21] = K 3x3 row-major, then RT 3x4 row-major, gpnerf_mesh_rasterize's layout
+ * and pixel convention (the centre of pixel (column i, row j) projects to (i, j)); n_views: 1 to 8; H, W: 1 to 16384.  Float64, unfused,
+ * rounded once to float32:
+ *   - on the host, inv(M) of a 3x3 M = (m0 .. m8, row-major) = adj / det with adj = (m4 m8 - m5 m7, m2 m7 - m1 m8, m1 m5 - m2 m4;
+ *     m5 m6 - m3 m8, m0 m8 - m2 m6, m2 m3 - m0 m5;  m3 m7 - m4 m6, m1 m6 - m0 m7, m0 m4 - m1 m3) and det = (m0 adj0 + m1 adj3) + m2 adj6;
+ *     Ki = inv(K), Ri = inv(R), R = RT's left 3x3, T its last column;  o_a = -((Ri[a][0] T0 + Ri[a][1] T1) + Ri[a][2] T2);
+ *   - per pixel, one lane each: c_r = (Ki[r][0] i + Ki[r][1] j) + Ki[r][2];  u = c0 / c2, v = c1 / c2;  d_a = (Ri[a][0] u + Ri[a][1] v)
+ *     + Ri[a][2];  the row is (float(o), float(d), float(z_near), +inf).
+ * The direction's camera-z component is 1, so t is camera z: gpnerf_mesh_rasterize's depth.  One launch.  GPNERF_E_ARG, before any
+ * device call: null cams or rays, n_views outside 1..8, H or W outside 1..16384, a z_near that is not > 0 and finite, a K or R whose
+ * det is 0 or not finite. */
+#define GPNERF_RAYCAST_NEAREST 0
+#define GPNERF_RAYCAST_ANY 1
+#define GPNERF_RAYCAST_MAX_VIEWS 8
+int gpnerf_mesh_raycast(const float* rays, int64_t n_rays, const float* vertices, int64_t n_vertices, const int32_t* faces, int64_t n_faces,
+                        void* grid_workspace, int32_t mode, float* t, int32_t* face, float* bary, void* stream);
+int gpnerf_pixel_rays(const double* cams, int32_t n_views, int32_t H, int32_t W, double z_near, float* rays, void* stream);
+
 /* ---- per-frame sparse convolution pyramid (gpnerf_volume.hip), replacing the external spconv v1.2.1 calls of
  * libs/nerfheads/networks/SparseConvNet.py:22-111 (SubMConv3d / SparseConv3d + BatchNorm1d + ReLU, .dense()).
  * A sparse tensor is: features [M][C] fp32, coords [M][3] int32 (d,h,w), and a dense int32 index grid [D][H][W]
