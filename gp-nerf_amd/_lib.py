@@ -187,6 +187,14 @@ SDF_MAX_BAND_STEPS = 1024
 RAYCAST_NEAREST, RAYCAST_ANY = range(2)
 RAYCAST_MODES = {"nearest": RAYCAST_NEAREST, "any": RAYCAST_ANY}
 RAYCAST_MAX_VIEWS = 8
+# gpnerf_texture_points' modes, the fates of a (point, view) pair -- the columns of its stats -- and its limits (include/gpnerf_hip.h
+# GPNERF_TEXTURE_*)
+TEXTURE_BLEND, TEXTURE_BEST = range(2)
+TEXTURE_MODES = {"blend": TEXTURE_BLEND, "best": TEXTURE_BEST}
+TEXTURE_STATS = ("used", "behind", "outside", "masked", "backfacing", "occluded")
+TEXTURE_USED, TEXTURE_BEHIND, TEXTURE_OUTSIDE, TEXTURE_MASKED, TEXTURE_BACKFACING, TEXTURE_OCCLUDED, TEXTURE_FATES = range(7)
+TEXTURE_TOTALS = ("seen", "unseen")
+TEXTURE_MAX_VIEWS, TEXTURE_MAX_SHARPNESS, TEXTURE_MAX_CHANNELS = 8, 4, 4
 # gpnerf_conv_variant's row and its kernel families (include/gpnerf_hip.h GPNERF_CONV_*)
 CONV_VARIANT = ("family", "cot", "rw", "ksplit", "cat", "tiles", "tile_h", "tile_w")
 CONV_FAMILIES = ("REFUSED", "DIRECT_1X1", "DIRECT_NARROW3", "TILED_S1", "TILED_S2", "STEM")
@@ -347,6 +355,11 @@ SYMBOLS = {
     "gpnerf_mesh_raycast": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p,
                                       C.c_void_p, C.c_void_p, C.c_void_p]),
     "gpnerf_pixel_rays": (C.c_int, [DP, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_void_p, C.c_void_p]),
+    "gpnerf_texture_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int32]),
+    "gpnerf_texture_points": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, DP, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
+                                        C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_double, C.c_double, C.c_int32, C.c_float,
+                                        C.c_int32, C.c_void_p, FP, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_void_p]),
     "gpnerf_head_layout": (C.c_int, [C.POINTER(C.c_int32)]),
     "gpnerf_strerror": (C.c_char_p, [C.c_int]),
     "gpnerf_rays_per_tile": (C.c_int32, []),

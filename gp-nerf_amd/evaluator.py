@@ -301,13 +301,24 @@ class MeshEvaluator:
     (camera depth, the meshes' unit, over the pixels where both are hit; means over the frames, the max over them),
     `visible_hit_disagreement` (the share of the pixels hit by exactly one mesh among those hit by either), their per-frame lists,
     and saves `<result_path>/visible_metrics.npy`.  A `gt_mesh` with an output that has no `axes`, or a batch without one of the
-    three keys, raises a GpnerfError naming the key.  Off, nothing changes."""
+    three keys, raises a GpnerfError naming the key.  Off, nothing changes.
+    texture (off by default; the photometric score of a mesh, the colour counterpart of the silhouette IoU): it needs `axes` in the
+    output, the `hull_masks` / `hull_Ks` / `hull_RTs` keys and `hull_imgs` [1,n,h,w,3] float32 in [0,1], the cameras' images.
+    `evaluate` puts the frame's mesh into the cameras' frame (`to_lattice_frame`), colours its vertices from the hull views whose
+    index is not a multiple of `texture_holdout` (the first 8 of them; frame.texture_mesh, masked, hidden by the mesh itself), draws
+    the coloured mesh into the held-out views (frame.rasterize_mesh with the colours as attributes; the first 8), forms the
+    difference to their images on the device -- NaN where no face covers the pixel or the mask is not 1 -- and reduces it with
+    frame.distance_stats into a slot: no host read (the mesh's grid is built unchecked).  `summarize()` reads the slots in one copy
+    and adds `texture_psnr` (-10 log10 of the mean square over the counted pixels' channels; the mean over the frames),
+    `texture_pixels` (counted pixels, summed), `texture_seen_fraction` (the share of the vertices some colouring view saw), their
+    per-frame lists, and saves `<result_path>/texture_metrics.npy`.  A missing key raises a GpnerfError naming it.  Off, nothing
+    changes."""
     PAD = 10                              # if_nerf_mesh.py:20, the np.pad(cube, 10) of BaseRender.py:269
 
     def __init__(self, result_path, mesh_th, export_mesh=False, metric_samples=100000, metric_thresholds=(0.005, 0.01, 0.02),
                  metric_max_dist=float("inf"), metric_device=None, metric_cell_cap=None, metric_entry_cap=None, silhouette=False,
                  topology=False, volume=False, volume_rule="nonzero", components=False, align=None, align_iterations=10,
-                 align_max_dist=float("inf"), signed=False, signed_band=8, visible=False):
+                 align_max_dist=float("inf"), signed=False, signed_band=8, visible=False, texture=False, texture_holdout=4):
         self.mesh_th = mesh_th
         self.export_mesh = bool(export_mesh)
         self.result_path = result_path
@@ -337,6 +348,10 @@ class MeshEvaluator:
         self._signed_slots, self._signed_frames = [], []
         self.visible = bool(visible)
         self._visible_slots, self._visible_frames = [], []
+        self.texture, self.texture_holdout = bool(texture), int(texture_holdout)
+        if self.texture_holdout < 2:
+            raise L.GpnerfError(f"MeshEvaluator: texture_holdout is at least 2 (every texture_holdout-th view is held out), got {texture_holdout!r}")
+        self._texture_slots, self._texture_totals, self._texture_frames = [], [], []
 
     SILHOUETTE_KEYS = ("hull_masks", "hull_Ks", "hull_RTs")
 
@@ -345,7 +360,7 @@ class MeshEvaluator:
         """True once a frame with `gt_mesh` (or, with silhouette on, with masks and cameras; or any frame with topology or components on) has been evaluated and not yet summarized
         (evaluate_loop asks)"""
         return (bool(self._slots) or bool(self._sil_slots) or bool(self._topo_slots) or bool(self._vol_slots) or bool(self._comp_slots) or
-                bool(self._signed_slots) or bool(self._visible_slots))
+                bool(self._signed_slots) or bool(self._visible_slots) or bool(self._texture_slots))
 
     def _padded_lattice(self, axes):
         """(lo, step, dims) of the frame's padded cube lattice in the axes' frame: to_lattice_frame's steps, PAD points around"""
@@ -433,6 +448,67 @@ class MeshEvaluator:
         np.save(os.path.join(self.result_path, "visible_metrics.npy"), table)       # a structured array: one row per frame
         print(f"visible_depth_mean: {metrics['visible_depth_mean']} (hit disagreement {metrics['visible_hit_disagreement']})")
         self._visible_slots, self._visible_frames = [], []
+        return metrics, per_frame
+
+    TEXTURE_KEYS = SILHOUETTE_KEYS + ("hull_imgs",)
+
+    def _enqueue_texture(self, output, batch):
+        from . import frame as F
+        if "axes" not in output:
+            raise L.GpnerfError("MeshEvaluator(texture=True): the output has no 'axes', so its mesh cannot be put into the cameras' frame "
+                                "(the inference renderer's render_mesh; the dense renderer's geometry mode returns axes)")
+        missing = [k for k in self.TEXTURE_KEYS if k not in batch]
+        if missing:
+            raise L.GpnerfError(f"MeshEvaluator(texture=True): the batch has no {', '.join(repr(k) for k in missing)} (the cameras, masks and "
+                                "images of the hull views: hull_masks [1,n,h,w], hull_Ks [1,n,3,3], hull_RTs [1,n,3,4], hull_imgs [1,n,h,w,3])")
+        masks, imgs = torch.as_tensor(batch["hull_masks"][0]), torch.as_tensor(batch["hull_imgs"][0])
+        if not masks.is_cuda or not imgs.is_cuda:
+            raise L.GpnerfError(f"MeshEvaluator(texture=True): hull_masks and hull_imgs must live on the GPU (got {masks.device}, {imgs.device}); "
+                                "no CPU fallback")
+        if masks.dtype != torch.uint8 or masks.dim() != 3:
+            raise L.GpnerfError(f"MeshEvaluator(texture=True): hull_masks must be uint8 [1,n,h,w] (0, 1, border 100), got {masks.dtype} "
+                                f"{tuple(batch['hull_masks'].shape)}")
+        if imgs.dtype != torch.float32 or tuple(imgs.shape) != tuple(masks.shape) + (3,):
+            raise L.GpnerfError(f"MeshEvaluator(texture=True): hull_imgs must be float32 [1,n,h,w,3] beside hull_masks {tuple(batch['hull_masks'].shape)}, "
+                                f"got {imgs.dtype} {tuple(batch['hull_imgs'].shape)}")
+        n, h, w = (int(x) for x in masks.shape)
+        held = [i for i in range(n) if i % self.texture_holdout == 0][:L.RASTER_MAX_VIEWS]
+        source = [i for i in range(n) if i % self.texture_holdout != 0][:L.TEXTURE_MAX_VIEWS]
+        if not source:
+            raise L.GpnerfError(f"MeshEvaluator(texture=True): {n} hull view(s) leave none to colour from (texture_holdout {self.texture_holdout})")
+        Ks, RTs = F.fetch_host(batch["hull_Ks"][0], batch["hull_RTs"][0])
+        v, f = F.mesh_to_device(output["mesh"].to_lattice_frame(output["axes"], self.PAD), masks.device)
+        grid = F.build_mesh_grid(v, f, cell_cap=self.metric_cell_cap, entry_cap=self.metric_entry_cap, check=False)
+        tex = F.texture_mesh(v, f, Ks[source], RTs[source], imgs[source].contiguous(), grid=grid, masks=masks[source].contiguous(),
+                             want=("color",))
+        drawn = F.rasterize_mesh(v, f, Ks[held], RTs[held], h, w, want=("face_id",), attributes=tex["color"])
+        counted = (drawn["face_id"] >= 0) & (masks[held] == 1)
+        diff = torch.where(counted[..., None], drawn["image"] - imgs[held], torch.full((), float("nan"), device=masks.device))
+        self._texture_slots.append(F.distance_stats(diff.contiguous().reshape(-1)))
+        self._texture_totals.append(tex["totals"])
+        self._texture_frames.append(self._scalar(batch["frame_index"]))
+
+    def _summarize_texture(self):
+        """the texture slots -> (means, per-frame lists), texture_metrics.npy written; resets them"""
+        host = torch.stack(self._texture_slots).cpu().numpy()   # the two reads
+        totals = torch.stack(self._texture_totals).cpu().numpy().astype(np.float64)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            psnr = -10.0 * np.log10(host[:, L.DIST_MEAN_SQ])
+            seen = totals[:, 0] / totals.sum(axis=1)
+        pixels = (host[:, L.DIST_FINITE] // 3).astype(np.int64)
+        per_frame = {"texture_psnr": [float(x) for x in psnr], "texture_pixels": [int(x) for x in pixels],
+                     "texture_seen_fraction": [float(x) for x in seen]}
+        metrics = {"texture_psnr": float(np.mean(psnr)), "texture_pixels": int(pixels.sum()), "texture_seen_fraction": float(np.mean(seen))}
+        per_frame["texture_frame_index"] = list(self._texture_frames)
+        table = np.zeros(len(host), dtype=[("frame_index", "i8"), ("pixels", "i8"), ("mean_square", "f8"), ("psnr", "f8"), ("max_abs", "f8"),
+                                           ("vertices_seen", "i8"), ("vertices_unseen", "i8")])
+        table["frame_index"], table["pixels"], table["mean_square"], table["psnr"] = self._texture_frames, pixels, host[:, L.DIST_MEAN_SQ], psnr
+        table["max_abs"] = np.maximum(host[:, L.DIST_MAX], 0.0)
+        table["vertices_seen"], table["vertices_unseen"] = totals[:, 0], totals[:, 1]
+        os.makedirs(self.result_path, exist_ok=True)
+        np.save(os.path.join(self.result_path, "texture_metrics.npy"), table)       # a structured array: one row per frame
+        print(f"texture_psnr: {metrics['texture_psnr']} ({metrics['texture_pixels']} pixels, seen fraction {metrics['texture_seen_fraction']})")
+        self._texture_slots, self._texture_totals, self._texture_frames = [], [], []
         return metrics, per_frame
 
     def _enqueue_volume(self, output, batch):
@@ -546,6 +622,8 @@ class MeshEvaluator:
                 self._enqueue_visible(output, batch)
         if self.silhouette and all(k in batch for k in self.SILHOUETTE_KEYS):
             self._enqueue_silhouette(output, batch)
+        if self.texture:
+            self._enqueue_texture(output, batch)
         if self.topology:
             from . import frame as F
             v, f = F.mesh_to_device(output["mesh"], torch.device(self.metric_device if self.metric_device is not None else "cuda:0"))
@@ -637,10 +715,12 @@ class MeshEvaluator:
         return metrics, per_frame
 
     def summarize(self):
-        if self._sil_slots or self._topo_slots or self._vol_slots or self._comp_slots or self._signed_slots or self._visible_slots:
+        if (self._sil_slots or self._topo_slots or self._vol_slots or self._comp_slots or self._signed_slots or self._visible_slots or
+                self._texture_slots):
             parts = (([self._summarize_silhouettes()] if self._sil_slots else []) + ([self._summarize_topology()] if self._topo_slots else []) +
                      ([self._summarize_volumes()] if self._vol_slots else []) + ([self._summarize_components()] if self._comp_slots else []) +
-                     ([self._summarize_signed()] if self._signed_slots else []) + ([self._summarize_visible()] if self._visible_slots else []))
+                     ([self._summarize_signed()] if self._signed_slots else []) + ([self._summarize_visible()] if self._visible_slots else []) +
+                     ([self._summarize_texture()] if self._texture_slots else []))
             metrics = self._summarize_mesh_metrics() if self._slots else {"per_frame": {}}
             per_frame = metrics.pop("per_frame")
             for means, frames in parts:

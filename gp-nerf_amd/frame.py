@@ -2178,3 +2178,123 @@ def mesh_visibility(points, eyes, vertices=None, faces=None, grid=None, eps=1e-4
     rows[..., 7] = 1.0
     t = raycast_mesh(rows, vertices, faces, grid=grid, mode="any")["t"]
     return (t > 0).to(torch.uint8)
+
+
+# ---- colouring points from calibrated views (csrc/gpnerf_texture.hip)
+
+TEXTURE_WANT = ("color", "weight", "views")
+
+
+def face_vertex_normals(vertices, faces):
+    """Area-weighted vertex normals of a device mesh -> float32 [n,3], not normalised: every face's cross product (b - a) x (c - a) in
+    float64, added to its three vertices by index_add_ in face order.  A vertex no face names gets the zero vector."""
+    nv, _ = _mesh_tensors(vertices, faces, "face_vertex_normals")
+    v, f = vertices.to(torch.float64), faces.to(torch.int64)
+    a, b, c = v[f[:, 0]], v[f[:, 1]], v[f[:, 2]]
+    fn = torch.cross(b - a, c - a, dim=1)
+    out = torch.zeros((nv, 3), device=vertices.device, dtype=torch.float64)
+    for k in range(3):
+        out.index_add_(0, f[:, k], fn)
+    return out.to(torch.float32).contiguous()
+
+
+def texture_points(points, Ks, RTs, images, normals=None, masks=None, vertices=None, faces=None, grid=None, mode="blend", sharpness=2,
+                   cos_min=0.2, eps=1e-4, z_near=1e-6, fallback=None, background=0.0, want=TEXTURE_WANT):
+    """gpnerf_texture_points: the colour the views give each of the device float32 points [n,3].  Ks [m,3,3], RTs [m,3,4]: host arrays,
+    used in float64, rasterize_mesh's cameras (1 to 8); images: device float32 [m,H,W,C], channels last, C <= 4 (Frame.imgs as it is).
+    include/gpnerf_hip.h states what a point receives: per view it is left out when it is behind the camera, outside the image, off
+    the mask (masks: device uint8 [m,H,W], 1 = foreground), facing away (normals: device float32 [n,3], any length; the cosine to the
+    eye must reach cos_min) or hidden by the mesh (grid: a MeshGrid, or vertices and faces for the brute-force form; neither: no
+    occlusion test; eps: mesh_visibility's); the views that remain are sampled bilinearly and blended with the weights cosine^(2
+    sharpness) (mode "blend"), or the one of the largest weight is taken (mode "best").  A point no view sees gets its row of
+    fallback (device float32 [n,C]) or background (a number or C numbers).
+    Returns a dict of device tensors: "color" float32 [n,C], "weight" float32 [n] and "views" uint8 [n] (bit v: view v was used) as
+    `want` names them, "stats" int64 [m,6] (_lib.TEXTURE_STATS: the points of each view under their fate) and "totals" int64 [2]
+    (points some view saw, points none did).  Nothing is read back."""
+    lib = L.lib()
+    if mode not in L.TEXTURE_MODES:
+        raise L.GpnerfError(f"texture_points: mode is 'blend' or 'best', got {mode!r}")
+    unknown = set(want) - set(TEXTURE_WANT)
+    if unknown:
+        raise L.GpnerfError(f"texture_points: want names {sorted(unknown)}; color, weight and views are what there is")
+    if not isinstance(points, torch.Tensor) or not isinstance(images, torch.Tensor):
+        raise L.GpnerfError("texture_points: points and images must be device tensors")
+    points = _points(points, "texture_points: points")
+    dev, n = points.device, int(points.shape[0])
+    cams = _raster_cams(Ks, RTs, "texture_points")
+    m = cams.shape[0]
+    _require_gpu(images, "texture_points: images")
+    if images.dtype != torch.float32 or images.dim() != 4 or images.shape[0] != m or not images.is_contiguous() or images.device != dev:
+        raise L.GpnerfError(f"texture_points: expected contiguous float32 images [{m},H,W,C] on {dev}, got {images.dtype} {tuple(images.shape)}")
+    H, W, c = (int(s) for s in images.shape[1:])
+    if not 1 <= c <= L.TEXTURE_MAX_CHANNELS:
+        raise L.GpnerfError(f"texture_points: 1 to {L.TEXTURE_MAX_CHANNELS} channels, got {c}")
+    if normals is not None:
+        normals = _points(normals, "texture_points: normals", like=points)
+    if masks is not None:
+        if not isinstance(masks, torch.Tensor) or not masks.is_cuda or masks.dtype != torch.uint8 or tuple(masks.shape) != (m, H, W) \
+                or not masks.is_contiguous():
+            raise L.GpnerfError(f"texture_points: expected contiguous uint8 masks [{m},{H},{W}] on the GPU")
+    if fallback is not None:
+        if not isinstance(fallback, torch.Tensor) or not fallback.is_cuda or fallback.dtype != torch.float32 \
+                or tuple(fallback.shape) != (n, c) or not fallback.is_contiguous():
+            raise L.GpnerfError(f"texture_points: expected a contiguous float32 fallback [{n},{c}] on the GPU")
+    for t, name in ((normals, "normals"), (masks, "masks"), (fallback, "fallback")):
+        if t is not None and t.device != dev:
+            raise L.GpnerfError(f"texture_points: points and {name} are on different devices")
+    nv = nf = 0
+    if grid is not None:
+        if not isinstance(grid, MeshGrid):
+            raise L.GpnerfError("texture_points: grid must be a MeshGrid (build_mesh_grid)")
+        vertices, faces = grid.vertices, grid.faces
+    if vertices is not None or faces is not None:
+        nv, nf = _mesh_tensors(vertices, faces, "texture_points")
+        if vertices.device != dev:
+            raise L.GpnerfError("texture_points: points and mesh are on different devices")
+    nbytes = int(lib.gpnerf_texture_workspace_bytes(n, m))
+    if nbytes <= 0 and n > 0:
+        raise L.GpnerfError(f"texture_points: refused ({n} points, {m} views)")
+    ws = _workspace(dev, max(nbytes, 256))
+    res = {"stats": torch.empty((m, L.TEXTURE_FATES), device=dev, dtype=torch.int64), "totals": torch.empty((2,), device=dev, dtype=torch.int64)}
+    if "color" in want:
+        res["color"] = torch.empty((n, c), device=dev, dtype=torch.float32)
+    if "weight" in want:
+        res["weight"] = torch.empty((n,), device=dev, dtype=torch.float32)
+    if "views" in want:
+        res["views"] = torch.empty((n,), device=dev, dtype=torch.uint8)
+    bg = np.broadcast_to(np.asarray(background, dtype=np.float32), (c,))
+    ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None
+    L.check(lib.gpnerf_texture_points(ptr(points), n, ptr(normals), cams.ctypes.data_as(L.DP), m, images.data_ptr(), H, W, c, ptr(masks),
+                                      (vertices.data_ptr() or faces.data_ptr()) if nf else None, nv, faces.data_ptr() if nf else None, nf,
+                                      grid.workspace.data_ptr() if grid is not None else None, float(z_near), float(cos_min), int(sharpness),
+                                      float(eps), L.TEXTURE_MODES[mode], ptr(fallback), (C.c_float * c)(*[float(b) for b in bg]),
+                                      ws.data_ptr(), ws.numel(), ptr(res.get("color")), ptr(res.get("weight")), ptr(res.get("views")),
+                                      res["stats"].data_ptr(), res["totals"].data_ptr(), _stream_ptr(dev)), "gpnerf_texture_points")
+    return res
+
+
+def texture_mesh(vertices, faces, Ks, RTs, images, normals=None, grid=None, **kw):
+    """texture_points on a device mesh's own vertices, hidden by the mesh itself: the grid is built when none is given (build_mesh_grid,
+    whose check is the call's one host read; pass a grid to read nothing), and without normals the area-weighted vertex normals of the
+    faces are used (face_vertex_normals).  The keywords are texture_points'."""
+    _mesh_tensors(vertices, faces, "texture_mesh")
+    if grid is None:
+        grid = build_mesh_grid(vertices, faces)
+    elif not isinstance(grid, MeshGrid):
+        raise L.GpnerfError("texture_mesh: grid must be a MeshGrid (build_mesh_grid)")
+    if normals is None:
+        normals = face_vertex_normals(vertices, faces)
+    return texture_points(vertices, Ks, RTs, images, normals=normals, grid=grid, **kw)
+
+
+def read_texture_stats(stats, totals):
+    """texture_points' counts on the host (arrays or tensors; the one read, at the end) -> {"per_view": {name: [...]} for _lib.TEXTURE_STATS,
+    "used_fraction": [...] per view, "seen", "unseen", "seen_fraction"}; a fraction of nothing is 0."""
+    host = lambda a: np.asarray(a.detach().cpu() if isinstance(a, torch.Tensor) else a).astype(np.int64)
+    s, t = host(stats).reshape(-1, L.TEXTURE_FATES), host(totals).reshape(2)
+    n = int(t.sum())
+    res = {"per_view": {name: [int(v) for v in s[:, k]] for k, name in enumerate(L.TEXTURE_STATS)}}
+    res["used_fraction"] = [float(u) / n if n else 0.0 for u in s[:, L.TEXTURE_USED]]
+    res["seen"], res["unseen"] = int(t[0]), int(t[1])
+    res["seen_fraction"] = float(t[0]) / n if n else 0.0
+    return res

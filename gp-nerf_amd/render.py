@@ -53,12 +53,22 @@ def parse_mesh_clean(value):
     return int(value) or None
 
 
+def parse_mesh_texture(value):
+    """Renderer(mesh_texture=...) / GPNERF_MESH_TEXTURE -> None (off) or "views": off is None, False, 0, "0" or ""; anything else is
+    refused."""
+    if value is None or value is False or value == 0 or (isinstance(value, str) and value.strip() in ("", "0")):
+        return None
+    if isinstance(value, str) and value.strip() == "views":
+        return "views"
+    raise L.GpnerfError(f"mesh_texture / GPNERF_MESH_TEXTURE: expected 0 or 'views', got {value!r}")
+
+
 class Renderer(nn.Module):
     def __init__(self, encoder, nerfhead, is_train=False, neg_ray_train=False, neg_ray_val=False, n_rays=1024,
                  n_samples=64, voxel_size=(0.005, 0.005, 0.005), chunk=64, mesh_th=-1, early_term=None, term_eps=1e-5,
                  progressive=False, split_f16=None, sharded_outputs="all", shard_group=None, encoder_graph=None, fold_levels=None, reserve_cus=None,
                  mesh_colors=None, mesh_clean=None, mesh_normals=None, mesh_simplify=None, mesh_smooth=None, mesh_topology=None,
-                 mesh_components=None):
+                 mesh_components=None, mesh_texture=None):
         super().__init__()
         self.encoder = encoder
         self.nerfhead = nerfhead
@@ -138,6 +148,11 @@ class Renderer(nn.Module):
         # nine counts of _lib.COMPONENT_STATS as mesh_<name>.  Off by default.
         self.mesh_components = F_.parse_components(os.environ.get("GPNERF_MESH_COMPONENTS", "0") if mesh_components is None else mesh_components,
                                                    "mesh_components / GPNERF_MESH_COMPONENTS")
+        # mesh_texture (GPNERF_MESH_TEXTURE = unset / 0 (off) or views): the final mesh's vertices take their colours from the frame's
+        # source views (frame.texture_mesh: projected, culled by facing and by the mesh itself, sampled and blended); a vertex no view
+        # sees keeps the field's rgb, the colour mesh_colors gives.  `mesh_stats` gains the per-view counts as texture_<name> (lists,
+        # _lib.TEXTURE_STATS) and texture_seen / texture_unseen.  Off by default.
+        self.mesh_texture = parse_mesh_texture(os.environ.get("GPNERF_MESH_TEXTURE", "0") if mesh_texture is None else mesh_texture)
 
     # ---- helpers the reference exposes as methods (stage entry points) ----------------------------
     def _neg_ray(self, batch):
@@ -333,6 +348,34 @@ class Renderer(nn.Module):
                 stats = {**(stats or {}), **dict(zip(names, m[key].cpu().tolist()))}
         return stats
 
+    def _mesh_colours(self, frame, m, consts, neg):
+        """(colours device float32 [nv,3] or None, texture counts or None) of extract_mesh's result: the field's rgb at the vertices
+        with mesh_colors; with mesh_texture the source views' colours (frame.texture_mesh), the field's rgb where no view sees the
+        vertex.  The lattice lives in the world frame -- the frame src_poses map from: query_points projects these very points with
+        K P --, so the cameras are the batch's as they are; under neg_ray, where a point in front of a view has h_z < 0, the pose is
+        negated on the host (K (-P) p = -h: the same pixel, z > 0; the eye -R^T T is unchanged)."""
+        if not self.mesh_colors and self.mesh_texture is None:
+            return None, None
+        field = F_.query_points(frame, m["vertices"], neg_ray=neg, want=("rgb",), lattice=m["lattice"])
+        if self.mesh_texture is None or int(m["faces"].shape[0]) == 0:        # (an empty mesh has nothing to colour or to hide behind)
+            return field["rgb"], None
+        lo, step, pad = m["lattice"]
+        dev = m["vertices"].device
+        lo_t, step_t = torch.tensor(lo, dtype=torch.float64, device=dev), torch.tensor(step, dtype=torch.float64, device=dev)
+        world = (lo_t + (m["vertices"].to(torch.float64) - float(pad)) * step_t).to(torch.float32).contiguous()   # query_points' formula
+        Ks, poses = np.asarray(consts[0], np.float64).reshape(-1, 3, 3), np.asarray(consts[1], np.float64).reshape(-1, 3, 4)
+        tex = F_.texture_mesh(world, m["faces"], Ks, -poses if neg else poses, frame.imgs, normals=m["normals"], fallback=field["raw"])
+        return tex["color"][:, :3], (tex["stats"], tex["totals"])
+
+    @staticmethod
+    def _texture_stats(stats, counts):
+        """mesh_stats with the texture's counts: texture_<name> per view (_lib.TEXTURE_STATS), texture_seen, texture_unseen"""
+        if counts is None:
+            return stats
+        per, tot = counts[0].cpu().tolist(), counts[1].cpu().tolist()
+        return {**(stats or {}), **{f"texture_{n}": [row[k] for row in per] for k, n in enumerate(L.TEXTURE_STATS)},
+                **{f"texture_{n}": tot[k] for k, n in enumerate(L.TEXTURE_TOTALS)}}
+
     def render_mesh(self, batch):
         """The inference renderer's geometry mode (demo_render.py:166-175, 249-311, 366-376, use_rgbhead False) on the device: returns
         `mesh` (mesh.Mesh: vertices in index units of the padded cube, as mcubes gives them), `cube` (the padded alpha cube,
@@ -351,8 +394,11 @@ class Renderer(nn.Module):
         and with it or mesh_topology `mesh_stats` gains the ten counts of _lib.TOPOLOGY_STATS.  With mesh_components ("largest" or N) only
         the connected components kept stay in the mesh (frame.filter_components, behind the simplification and in front of smoothing,
         topology, normals and colours: one more host read, the two sizes), and `mesh_stats` gains the nine counts of
-        _lib.COMPONENT_STATS as mesh_<name> (of the mesh before the filter, and what was kept).  With all of them off, extract_mesh
-        enqueues exactly the launches it did before there were these options."""
+        _lib.COMPONENT_STATS as mesh_<name> (of the mesh before the filter, and what was kept).  With mesh_texture ("views") the final
+        mesh's vertex_colors come from the frame's source views (frame.texture_mesh on the vertices in the lattice's frame, the cube's
+        geometric normals, hidden by the mesh itself: one more host read, the grid's status), the field's rgb where no view sees a
+        vertex, and `mesh_stats` gains texture_<name> per view (_lib.TEXTURE_STATS) and texture_seen / texture_unseen.  With all of
+        them off, extract_mesh enqueues exactly the launches it did before there were these options."""
         dev = batch["src_imgs"].device
         torch.cuda.synchronize(dev)
         te = time.time()
@@ -369,17 +415,15 @@ class Renderer(nn.Module):
         frame.build_occupancy()
         ev[2].record()
         m = F_.extract_mesh(frame, self.voxel_size, batch["bounds"][0, 0], batch["Rh"][0], batch["Th"][0], neg_ray=self._neg_ray(batch),
-                            iso=M_.ISO_REFERENCE, host=box_host, clean=self.mesh_clean, normals=self.mesh_normals,
+                            iso=M_.ISO_REFERENCE, host=box_host, clean=self.mesh_clean, normals=self.mesh_normals or self.mesh_texture is not None,
                             simplify=self.mesh_simplify, smooth=self.mesh_smooth, topology=self.mesh_topology,
                             components=self.mesh_components)
-        colours = None
-        if self.mesh_colors:
-            colours = F_.query_points(frame, m["vertices"], neg_ray=self._neg_ray(batch), want=("rgb",), lattice=m["lattice"])["rgb"]
+        colours, texture = self._mesh_colours(frame, m, consts, self._neg_ray(batch))
         ev[3].record()
         cube = m["cube"].cpu().numpy()
         mesh = M_.Mesh(m["vertices"].cpu().numpy(), m["faces"].cpu().numpy(), colours.cpu().numpy() if colours is not None else None,
-                       m["normals"].cpu().numpy() if "normals" in m else None)
-        stats = self._mesh_stats(m)
+                       m["normals"].cpu().numpy() if self.mesh_normals else None)
+        stats = self._texture_stats(self._mesh_stats(m), texture)
         t4 = time.time()
         etime = ev[0].elapsed_time(ev[1]) * 1e-3
         t_frame, t_mesh = ev[1].elapsed_time(ev[2]) * 1e-3, ev[2].elapsed_time(ev[3]) * 1e-3
@@ -404,7 +448,7 @@ class Renderer(nn.Module):
               loader neither builds the 12 B/point `pts` array nor carves.
         Returns `cube` (the padded alpha cube, float32 numpy), `mesh` (mesh.Mesh, vertices in index units of the padded cube), `axes`
         (three host float32 arrays), `n_inside` (kept points), `time_slots`, `etime`, `rtime`, and `mesh_stats` with mesh_clean,
-        mesh_simplify, mesh_smooth, mesh_topology or mesh_components.  mesh_clean / mesh_normals / mesh_colors / mesh_simplify / mesh_smooth / mesh_topology / mesh_components act as in render_mesh.  Host reads: the constants (with the axes or the cameras) before
+        mesh_simplify, mesh_smooth, mesh_topology, mesh_components or mesh_texture.  mesh_clean / mesh_normals / mesh_colors / mesh_simplify / mesh_smooth / mesh_topology / mesh_components / mesh_texture act as in render_mesh.  Host reads: the constants (with the axes or the cameras) before
         the encoder, the mesh counts, and the results."""
         dev = batch["src_imgs"].device
         have_a = "pts" in batch and "inside" in batch
@@ -449,16 +493,15 @@ class Renderer(nn.Module):
         neg = self._neg_ray(batch)
         cube, n_kept = F_.density_lattice(frame, axes, neg_ray=neg, pad=F_.MESH_PAD, inside=inside)
         m = F_.extract_mesh(frame, self.voxel_size, None, None, None, neg_ray=neg, iso=self.mesh_th, host=[vs_host], clean=self.mesh_clean,
-                            normals=self.mesh_normals, lattice=(cube, axes, n_kept), simplify=self.mesh_simplify, smooth=self.mesh_smooth,
+                            normals=self.mesh_normals or self.mesh_texture is not None, lattice=(cube, axes, n_kept),
+                            simplify=self.mesh_simplify, smooth=self.mesh_smooth,
                             topology=self.mesh_topology, components=self.mesh_components)
-        colours = None
-        if self.mesh_colors:
-            colours = F_.query_points(frame, m["vertices"], neg_ray=neg, want=("rgb",), lattice=m["lattice"])["rgb"]
+        colours, texture = self._mesh_colours(frame, m, consts, neg)
         ev[4].record()
         cube_np = m["cube"].cpu().numpy()
         mesh = M_.Mesh(m["vertices"].cpu().numpy(), m["faces"].cpu().numpy(), colours.cpu().numpy() if colours is not None else None,
-                       m["normals"].cpu().numpy() if "normals" in m else None)
-        stats = self._mesh_stats(m)
+                       m["normals"].cpu().numpy() if self.mesh_normals else None)
+        stats = self._texture_stats(self._mesh_stats(m), texture)
         n_inside = int(n_kept.cpu().item())
         t4 = time.time()
         etime = ev[0].elapsed_time(ev[1]) * 1e-3

@@ -1415,6 +1415,83 @@ int gpnerf_mesh_raycast(const float* rays, int64_t n_rays, const float* vertices
                         void* grid_workspace, int32_t mode, float* t, int32_t* face, float* bary, void* stream);
 int gpnerf_pixel_rays(const double* cams, int32_t n_views, int32_t H, int32_t W, double z_near, float* rays, void* stream);
 
+/* ---- colouring points from calibrated views (gpnerf_texture.hip): the colour the photographs give a mesh's vertices (or any list of
+ * points), with the views in which a point is behind the camera, outside the image, off the mask, facing away or hidden by the mesh
+ * left out.  Kernel launches only, on the caller's stream; nothing allocated, nothing waited for; every launch sized from the arguments
+ * alone; no float atomic (integer sums for the counts, one add per wavefront and counter); the call captures into a HIP graph and
+ * replays with the same bytes; the result is a function of the inputs alone.
+ *
+ * gpnerf_texture_points(points, n_points, normals, cams, n_views, images, H, W, C, masks, vertices, n_vertices, faces, n_faces,
+ * grid_workspace, z_near, cos_min, sharpness, eps, mode, fallback, background, workspace, workspace_bytes, color, weight, views, stats,
+ * totals, stream):
+ *   points: device float [n_points][3];  normals: device float [n_points][3] or NULL, need not be unit length;  cams: HOST double
+ *   [n_views][21] = K 3x3 row-major, then RT 3x4 row-major, gpnerf_mesh_rasterize's layout; n_views: 1 to 8;  images: device float
+ *   [n_views][H][W][C], channels last, C in 1..4 (GpnerfFrame.imgs as it is, C = 4; 16-byte aligned when C = 4), H, W: 1 to 16384;
+ *   masks: device uint8 [n_views][H][W] (get_mask: 0, 1 and the border band's 100) or NULL;  the mesh that occludes: vertices, faces and
+ *   grid_workspace as gpnerf_mesh_raycast takes them (a NULL grid selects its brute-force form), n_faces == 0: no occlusion test (a
+ *   grid is then refused);  fallback: device float [n_points][C] or NULL;  background: HOST float [C].
+ *
+ * THE DEFINITION.  All arithmetic float64, multiply then add, unfused, in the order written, rounded to float32 once at the end.
+ * Per (point p, view): the FIRST rule that applies names the pair's fate; every pair has exactly one.
+ *   1. BEHIND.  gpnerf_mesh_rasterize's projection of a vertex: the float32 point widened to float64, c = p0 RT[:,0] + p1 RT[:,1] + p2
+ *      RT[:,2] + RT[:,3], h = c0 K[:,0] + c1 K[:,1] + c2 K[:,2], z = h2, x = h0 / h2, y = h1 / h2.  BEHIND unless x, y and z are
+ *      finite and z >= z_near.
+ *   2. OUTSIDE unless 0 <= x <= W - 1 and 0 <= y <= H - 1: pixel centres are at integer coordinates (the rasteriser's convention,
+ *      grid_sample's align_corners=True), so the image's frame is the hull of its pixel centres.
+ *   3. MASKED (masks given) unless the mask at row rint(y), column rint(x) (half to even) is exactly 1.
+ *   4. BACKFACING (normals given).  e = the view's eye, e_a = -((RT[0][a] RT[0][3] + RT[1][a] RT[1][3]) + RT[2][a] RT[2][3]) (-R^T T)
+ *      in float64 on the host, rounded to float32.  v = e - p in float32 (one rounding per component), widened.  a = (n0 v0 + n1 v1)
+ *      + n2 v2, nn = (n0 n0 + n1 n1) + n2 n2, vv likewise.  BACKFACING unless nn is finite, a > 0 and a a >= ((cos_min cos_min) nn) vv
+ *      (cos_min cos_min formed on the host): a zero or non-finite normal is BACKFACING.  The weight: r = (a a) / (nn vv), w = r
+ *      multiplied by r (sharpness - 1) times; sharpness 0: w = 1.  Without normals there is no facing test and w = 1.
+ *   5. OCCLUDED (n_faces > 0).  The row (o = p, d = v, tmin = eps, tmax = 1) -- mesh_visibility's row for this point and eye -- goes
+ *      through gpnerf_mesh_raycast in GPNERF_RAYCAST_ANY mode; OCCLUDED unless its t > 0 (t = 0: a face lies between; t = NaN: a row
+ *      that is not a ray, e.g. a v that overflowed, or a grid that is not OK -- mesh_visibility's answer in every case).
+ *   6. USED.  The colour is the bilinear sample: i0 = floor(x), i1 = min(i0 + 1, W - 1), fx = x - i0, the same for j0, j1, fy from y;
+ *      with cab = image[view][row jb][column ia], per channel top = c00 (1 - fx) + c10 fx, bottom = c01 (1 - fx) + c11 fx,
+ *      colour = top (1 - fy) + bottom fy.
+ * Per point:
+ *   - GPNERF_TEXTURE_BLEND: S = 0, D = 0; over the USED views in ascending index S = S + w colour (per channel), D = D + w;
+ *     color = float(S / D), weight = float(D), views = the USED views' bits;
+ *   - GPNERF_TEXTURE_BEST: the USED view of the largest w, the lowest index among equal w; color = float(its colour), weight =
+ *     float(its w), views = its bit alone;
+ *   - no USED view: color = the point's fallback row, or background without one; weight = 0, views = 0.
+ * Outputs, each optional (NULL): color device float [n_points][C]; weight device float [n_points]; views device uint8 [n_points], bit
+ * v set iff view v was USED (BEST: the chosen one);  stats device int64 [n_views][GPNERF_TEXTURE_FATES], the pairs of each view under
+ * their fate (GPNERF_TEXTURE_USED ... _OCCLUDED; a row sums to n_points; BEST counts every USED pair, chosen or not);  totals device
+ * int64 [2]: the points with at least one USED view, and those with none.  The call sets stats and totals.
+ * Launches: (a) prepare, one lane per point, the views in a loop: rules 1-4, the pair's fate, weight and row into the workspace -- a
+ * pair that is already decided gets the row (0, 0, 0; 0, 0, 1; tmin 1, tmax 0), which gpnerf_mesh_raycast rejects as "not a ray"
+ * without a walk; block 0 zeroes stats and totals;  (b) with n_faces > 0, gpnerf_mesh_raycast itself over the [n_points][n_views] rows
+ * (its one or two launches);  (c) blend, one lane per point: the cast's answer, the taps (C = 4: one 16-byte load each), the blend,
+ * the outputs and the counts.  n_points == 0: (a) alone.
+ * workspace: gpnerf_texture_workspace_bytes(n_points, n_views) bytes (host arithmetic only; 0 for what the call refuses), 16-byte
+ * aligned, = align256(32 P) + align256(4 P) + align256(4 P) + align256(8 P) + align256(P), P = n_points n_views: the rows, the
+ * cast's t and face, the weights (float64), the fates.  It carries nothing from call to call.
+ * GPNERF_E_ARG, before anything is launched: null cams, images, background or workspace; null points with n_points > 0; n_points
+ * negative or >= 2^31; n_views outside 1..8; H or W outside 1..16384; C outside 1..4; images not 16-byte aligned with C = 4; a z_near
+ * that is not > 0 and finite; cos_min outside [0, 1) or NaN; sharpness outside 0..4; eps outside [0, 1] or NaN; a mode that is
+ * neither of the two; n_faces negative or >= 2^31; n_faces > 0 with null vertices or faces or n_vertices < 0; a grid with n_faces ==
+ * 0; a workspace under the formula or not 16-byte aligned. */
+#define GPNERF_TEXTURE_BLEND 0
+#define GPNERF_TEXTURE_BEST 1
+#define GPNERF_TEXTURE_USED 0
+#define GPNERF_TEXTURE_BEHIND 1
+#define GPNERF_TEXTURE_OUTSIDE 2
+#define GPNERF_TEXTURE_MASKED 3
+#define GPNERF_TEXTURE_BACKFACING 4
+#define GPNERF_TEXTURE_OCCLUDED 5
+#define GPNERF_TEXTURE_FATES 6
+#define GPNERF_TEXTURE_MAX_VIEWS 8
+#define GPNERF_TEXTURE_MAX_SHARPNESS 4
+size_t gpnerf_texture_workspace_bytes(int64_t n_points, int32_t n_views);
+int gpnerf_texture_points(const float* points, int64_t n_points, const float* normals, const double* cams, int32_t n_views,
+                          const float* images, int32_t H, int32_t W, int32_t C, const uint8_t* masks, const float* vertices,
+                          int64_t n_vertices, const int32_t* faces, int64_t n_faces, void* grid_workspace, double z_near, double cos_min,
+                          int32_t sharpness, float eps, int32_t mode, const float* fallback, const float* background, void* workspace,
+                          size_t workspace_bytes, float* color, float* weight, uint8_t* views, int64_t* stats, int64_t* totals,
+                          void* stream);
+
 /* ---- per-frame sparse convolution pyramid (gpnerf_volume.hip), replacing the external spconv v1.2.1 calls of
  * libs/nerfheads/networks/SparseConvNet.py:22-111 (SubMConv3d / SparseConv3d + BatchNorm1d + ReLU, .dense()).
  * A sparse tensor is: features [M][C] fp32, coords [M][3] int32 (d,h,w), and a dense int32 index grid [D][H][W]
