@@ -195,6 +195,14 @@ TEXTURE_STATS = ("used", "behind", "outside", "masked", "backfacing", "occluded"
 TEXTURE_USED, TEXTURE_BEHIND, TEXTURE_OUTSIDE, TEXTURE_MASKED, TEXTURE_BACKFACING, TEXTURE_OCCLUDED, TEXTURE_FATES = range(7)
 TEXTURE_TOTALS = ("seen", "unseen")
 TEXTURE_MAX_VIEWS, TEXTURE_MAX_SHARPNESS, TEXTURE_MAX_CHANNELS = 8, 4, 4
+# gpnerf_fusion_integrate's fates of a (lattice point, view) pair -- the columns of its stats --, finalise's totals, the bits of a
+# point's flag byte and the limit on the views of one call (include/gpnerf_hip.h GPNERF_FUSION_*)
+FUSION_FATES = ("behind", "outside", "nodata", "empty", "hidden", "near")
+FUSION_BEHIND, FUSION_OUTSIDE, FUSION_NODATA, FUSION_EMPTY, FUSION_HIDDEN, FUSION_NEAR, FUSION_N_FATES = range(7)
+FUSION_TOTALS = ("seen", "surface", "interior", "unknown")
+FUSION_SEEN, FUSION_SURFACE, FUSION_INTERIOR, FUSION_UNKNOWN, FUSION_N_TOTALS = range(5)
+FUSION_FLAG_HIDDEN, FUSION_FLAG_NEAR = 1, 2
+FUSION_MAX_VIEWS = 8
 # gpnerf_conv_variant's row and its kernel families (include/gpnerf_hip.h GPNERF_CONV_*)
 CONV_VARIANT = ("family", "cot", "rw", "ksplit", "cat", "tiles", "tile_h", "tile_w")
 CONV_FAMILIES = ("REFUSED", "DIRECT_1X1", "DIRECT_NARROW3", "TILED_S1", "TILED_S2", "STEM")
@@ -360,6 +368,13 @@ SYMBOLS = {
                                         C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_double, C.c_double, C.c_int32, C.c_float,
                                         C.c_int32, C.c_void_p, FP, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                         C.c_void_p, C.c_void_p]),
+    "gpnerf_fusion_reset": (C.c_int, [C.POINTER(C.c_int32), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gpnerf_fusion_integrate": (C.c_int, [C.c_void_p, C.c_void_p, DP, C.c_int32, C.c_int32, C.c_int32, DP, C.POINTER(C.c_int32), C.c_float,
+                                          C.c_double, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gpnerf_fusion_finalise": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_float, C.c_void_p, C.c_void_p,
+                                         C.c_void_p]),
+    "gpnerf_fusion_oneshot": (C.c_int, [C.c_void_p, C.c_void_p, DP, C.c_int32, C.c_int32, C.c_int32, DP, C.POINTER(C.c_int32), C.c_float,
+                                        C.c_double, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gpnerf_head_layout": (C.c_int, [C.POINTER(C.c_int32)]),
     "gpnerf_strerror": (C.c_char_p, [C.c_int]),
     "gpnerf_rays_per_tile": (C.c_int32, []),

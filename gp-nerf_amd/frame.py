@@ -2298,3 +2298,130 @@ def read_texture_stats(stats, totals):
     res["seen"], res["unseen"] = int(t[0]), int(t[1])
     res["seen_fraction"] = float(t[0]) / n if n else 0.0
     return res
+
+
+# ---- fusing depth maps into a truncated signed distance field (csrc/gpnerf_fusion.hip)
+
+def _fusion_band(band, lat, what):
+    band32 = float(np.float32(band))
+    if not (np.isfinite(band32) and 0.0 < band32 <= L.SDF_MAX_BAND_STEPS * float(lat[3:].min())):
+        raise L.GpnerfError(f"{what}: band {band} refused (finite, > 0, at most {L.SDF_MAX_BAND_STEPS} x the smallest step {float(lat[3:].min())})")
+    return band32
+
+
+def _fusion_views(depth, Ks, RTs, weights, z_near, what, dev=None):
+    """the checked (depth, weights, cams, n_views, H, W, z_near) of a fusion call"""
+    if not isinstance(depth, torch.Tensor):
+        raise L.GpnerfError(f"{what}: depth must be a device tensor")
+    _require_gpu(depth, f"{what}: depth")
+    cams = _raster_cams(Ks, RTs, what)
+    m = cams.shape[0]
+    if depth.dtype != torch.float32 or depth.dim() != 3 or depth.shape[0] != m or not depth.is_contiguous() or 0 in depth.shape:
+        raise L.GpnerfError(f"{what}: expected contiguous float32 depth [{m},H,W], got {depth.dtype} {tuple(depth.shape)}")
+    if dev is not None and depth.device != dev:
+        raise L.GpnerfError(f"{what}: depth on {depth.device}, the lattice's state on {dev}")
+    H, W = int(depth.shape[1]), int(depth.shape[2])
+    if not (1 <= H <= 16384 and 1 <= W <= 16384):
+        raise L.GpnerfError(f"{what}: refused ({m} views, {H} x {W})")
+    if weights is not None:
+        if not isinstance(weights, torch.Tensor) or not weights.is_cuda or weights.dtype != torch.float32 \
+                or tuple(weights.shape) != (m, H, W) or not weights.is_contiguous() or weights.device != depth.device:
+            got = f"{weights.dtype} {tuple(weights.shape)}" if isinstance(weights, torch.Tensor) else type(weights).__name__
+            raise L.GpnerfError(f"{what}: expected contiguous float32 weights [{m},{H},{W}] on {depth.device}, got {got}")
+    z_near = float(z_near)
+    if not (np.isfinite(z_near) and z_near > 0.0):
+        raise L.GpnerfError(f"{what}: z_near {z_near} refused (> 0 and finite)")
+    return depth, weights, cams, m, H, W, z_near
+
+
+class DepthFusion:
+    """The running state of a depth-map fusion (gpnerf_fusion_integrate; include/gpnerf_hip.h states THE DEFINITION) on the lattice of
+    dims = (nx, ny, nz) POINTS at lo + (i, j, k) * step: `sum` and `weight` device float64 [nx,ny,nz], `flags` device uint8 (bit 0:
+    some view saw the point behind its surface; bit 1: some view saw it within the band of one).  band: metric, > 0, at most 1024 x the
+    smallest step.  integrate() continues the sums, so any number of views goes through in groups of at most eight; grid() is the field
+    so far.  17 bytes per lattice point; nothing is read back."""
+
+    def __init__(self, lo, step, dims, band, device):
+        self.dims = _voxel_dims(dims, "DepthFusion")
+        lat = _voxel_lattice(lo, step, "DepthFusion")
+        self.lo, self.step, self._lat = lat[:3].copy(), lat[3:].copy(), lat
+        self.band = _fusion_band(band, lat, "DepthFusion")
+        dev = torch.device(device)
+        if dev.type != "cuda":
+            raise L.GpnerfError(f"DepthFusion: the state must live on the GPU (got {dev}); the HIP path has no CPU fallback")
+        self.device = dev
+        self.sum = torch.empty(self.dims, device=dev, dtype=torch.float64)
+        self.weight = torch.empty(self.dims, device=dev, dtype=torch.float64)
+        self.flags = torch.empty(self.dims, device=dev, dtype=torch.uint8)
+        self.reset()
+
+    def _c_dims(self):
+        return (C.c_int32 * 3)(*self.dims)
+
+    def reset(self):
+        """gpnerf_fusion_reset: the state back to no view at all"""
+        L.check(L.lib().gpnerf_fusion_reset(self._c_dims(), self.sum.data_ptr(), self.weight.data_ptr(), self.flags.data_ptr(),
+                                            _stream_ptr(self.device)), "gpnerf_fusion_reset")
+        return self
+
+    def integrate(self, depth, Ks, RTs, weights=None, z_near=1e-6, carve=True):
+        """gpnerf_fusion_integrate: 1 to 8 more views into the state.  depth: device float32 [m,H,W], CAMERA Z (rasterize_mesh's
+        depth; raycast_mesh's t along pixel_rays), +inf where the pixel sees nothing -- with carve, such a pixel empties the space
+        along its ray; without, it says nothing.  NaN, 0 and negative depths say nothing.  Ks [m,3,3], RTs [m,3,4]: host arrays, used
+        in float64, rasterize_mesh's cameras; weights: device float32 [m,H,W] or None (1).  Returns the call's device int64 [m,6]
+        counts (_lib.FUSION_FATES: the lattice points of each view under their fate)."""
+        depth, weights, cams, m, H, W, z_near = _fusion_views(depth, Ks, RTs, weights, z_near, "DepthFusion.integrate", self.device)
+        stats = torch.empty((m, L.FUSION_N_FATES), device=self.device, dtype=torch.int64)
+        L.check(L.lib().gpnerf_fusion_integrate(depth.data_ptr(), weights.data_ptr() if weights is not None else None, cams.ctypes.data_as(L.DP),
+                                                m, H, W, self._lat.ctypes.data_as(L.DP), self._c_dims(), self.band, z_near, int(bool(carve)),
+                                                self.sum.data_ptr(), self.weight.data_ptr(), self.flags.data_ptr(), stats.data_ptr(),
+                                                _stream_ptr(self.device)), "gpnerf_fusion_integrate")
+        return stats
+
+    def grid(self):
+        """gpnerf_fusion_finalise: the field so far as an SdfGrid (face None, voxels None) whose stats are the device int64 [4] totals
+        (_lib.FUSION_TOTALS): sum / weight clamped to the band where a view weighed in, -band where none did and some view saw the
+        point behind its surface, +band elsewhere.  offset_mesh(0) is the fused surface."""
+        values = torch.empty(self.dims, device=self.device, dtype=torch.float32)
+        totals = torch.empty((L.FUSION_N_TOTALS,), device=self.device, dtype=torch.int64)
+        L.check(L.lib().gpnerf_fusion_finalise(self.sum.data_ptr(), self.weight.data_ptr(), self.flags.data_ptr(), self._c_dims(), self.band,
+                                               values.data_ptr(), totals.data_ptr(), _stream_ptr(self.device)), "gpnerf_fusion_finalise")
+        return SdfGrid(values, None, None, self.lo, self.step, self.dims, self.band, totals)
+
+
+def fuse_depth(depth, Ks, RTs, lo, step, dims, band, weights=None, z_near=1e-6, carve=True, want_flags=False):
+    """gpnerf_fusion_oneshot: at most eight depth maps fused into a truncated signed distance field in one pass -- what a fresh
+    DepthFusion's integrate() and grid() give, bit for bit, with the sums in registers: 4 bytes written per lattice point instead of
+    17 + 17 + 4 moved.  The arguments are DepthFusion's and integrate's.  Returns an SdfGrid (face None, voxels None, stats = the
+    totals) with .fusion_stats (device int64 [m,6], _lib.FUSION_FATES), .fusion_totals (device int64 [4], _lib.FUSION_TOTALS) and, with
+    want_flags, .flags (device uint8 [nx,ny,nz]) attached.  Nothing is read back."""
+    d = _voxel_dims(dims, "fuse_depth")
+    lat = _voxel_lattice(lo, step, "fuse_depth")
+    band32 = _fusion_band(band, lat, "fuse_depth")
+    depth, weights, cams, m, H, W, z_near = _fusion_views(depth, Ks, RTs, weights, z_near, "fuse_depth")
+    dev = depth.device
+    values = torch.empty(d, device=dev, dtype=torch.float32)
+    flags = torch.empty(d, device=dev, dtype=torch.uint8) if want_flags else None
+    stats = torch.empty((m, L.FUSION_N_FATES), device=dev, dtype=torch.int64)
+    totals = torch.empty((L.FUSION_N_TOTALS,), device=dev, dtype=torch.int64)
+    L.check(L.lib().gpnerf_fusion_oneshot(depth.data_ptr(), weights.data_ptr() if weights is not None else None, cams.ctypes.data_as(L.DP), m, H,
+                                          W, lat.ctypes.data_as(L.DP), (C.c_int32 * 3)(*d), band32, z_near, int(bool(carve)), values.data_ptr(),
+                                          flags.data_ptr() if flags is not None else None, stats.data_ptr(), totals.data_ptr(),
+                                          _stream_ptr(dev)), "gpnerf_fusion_oneshot")
+    grid = SdfGrid(values, None, None, lat[:3], lat[3:], d, band32, totals)
+    grid.fusion_stats, grid.fusion_totals = stats, totals
+    if want_flags:
+        grid.flags = flags
+    return grid
+
+
+def read_fusion_stats(stats, totals):
+    """fusion counts on the host (arrays or tensors; the one read, at the end) -> {"per_view": {name: [...]} for _lib.FUSION_FATES,
+    **{name: count for _lib.FUSION_TOTALS}, "seen_fraction"}; stats may be several calls' rows stacked.  A fraction of nothing is 0."""
+    host = lambda a: np.asarray(a.detach().cpu() if isinstance(a, torch.Tensor) else a).astype(np.int64)
+    s, t = host(stats).reshape(-1, L.FUSION_N_FATES), host(totals).reshape(L.FUSION_N_TOTALS)
+    res = {"per_view": {name: [int(v) for v in s[:, k]] for k, name in enumerate(L.FUSION_FATES)}}
+    res.update({name: int(t[k]) for k, name in enumerate(L.FUSION_TOTALS)})
+    n = int(t[L.FUSION_SEEN] + t[L.FUSION_INTERIOR] + t[L.FUSION_UNKNOWN])
+    res["seen_fraction"] = float(t[L.FUSION_SEEN]) / n if n else 0.0
+    return res

@@ -509,6 +509,82 @@ class Renderer(nn.Module):
         return {"cube": cube_np, "mesh": mesh, "axes": axes, "n_inside": n_inside, **({"mesh_stats": stats} if stats is not None else {}),
                 "time_slots": {"frame": t_frame, "hull": t_hull, "mesh": t_mesh}, "etime": etime, "rtime": max(0.0, (t4 - te) - etime)}
 
+    def render_fusion(self, batch, n_samples=None, band_steps=4, acc_min=0.5):
+        """A surface from the field's own RENDERS instead of its density lattice: the frame is produced as render_geometry produces it,
+        every hull camera's h x w pixels are rendered (frame.select_rays(compact=False) for the rays, frame.render_fused for `depth`
+        and `acc` -- the progressive renderer's launch, occupancy-culled), the depth maps are fused into a truncated signed distance
+        field over frame.dataset_lattice_axes(can_bounds, voxel_size) (frame.DepthFusion, groups of 8 views) and its zero set is
+        meshed.  No density threshold enters: a cross-check on the 1 / mesh_th iso of render_geometry.
+        Needs the batch keys of HULL_KEYS (`hull_masks` for h and w only).  A pixel's depth is depth / acc where acc >= acc_min and
+        +inf where the ray misses the box or acc < acc_min, which carves.  THE DEPTH IS CAMERA Z: select_rays' directions are R^T
+        inv(K) (i, j, 1), whose camera-z component is 1 for a K whose last row is (0, 0, 1) -- any other K is refused --, and
+        render_fused's depth is the weighted sum of the samples' parameters along that direction.  Under neg_ray the parameters run
+        through negative values and the sum is no camera z: refused.  The rays are made from the cameras rounded to float32, as the
+        progressive renderer makes them; the fusion projects with the cameras as given (float64).
+        band = band_steps x the largest voxel step.  Returns `mesh` (mesh.Mesh in the WORLD frame, sdf.offset_mesh(0)), `sdf` (the
+        SdfGrid, on the device), `depth_maps` (device float32 [n,h,w]), `fusion_stats` (frame.read_fusion_stats of every view's counts
+        and the totals), `time_slots`, `etime`, `rtime`."""
+        missing = [k for k in self.HULL_KEYS if k not in batch]
+        if missing:
+            raise L.GpnerfError("render_fusion needs the batch keys " + ", ".join(repr(k) for k in self.HULL_KEYS) + "; missing: " +
+                                ", ".join(repr(k) for k in missing) + f"; the batch has {sorted(batch.keys())}")
+        neg = self._neg_ray(batch)
+        if neg:
+            raise L.GpnerfError("render_fusion: the renderer runs this batch under neg_ray (neg_ray_train / neg_ray_val), where "
+                                "render_fused's depth is not camera z; no conversion is defined")
+        if not (float(acc_min) > 0.0 and float(band_steps) > 0.0):
+            raise L.GpnerfError(f"render_fusion: acc_min {acc_min} and band_steps {band_steps} must be > 0")
+        dev = batch["src_imgs"].device
+        S = int(n_samples) if n_samples is not None else self.n_samples
+        n, h, w = (int(s) for s in batch["hull_masks"].shape[1:4])
+        torch.cuda.synchronize(dev)
+        te = time.time()
+        fetched = F_.fetch_host(batch["src_Ks"][0], batch["src_poses"][0], batch["Rh"][0], batch["Th"][0], batch["bounds"][0, 0],
+                                self.voxel_size, batch["out_sh"][0], self.voxel_size, batch["can_bounds"][0], batch["hull_Ks"][0],
+                                batch["hull_RTs"][0])
+        consts, vs_host, box, Ks, RTs = fetched[:7], fetched[7], fetched[8], fetched[9].reshape(-1, 3, 3), fetched[10].reshape(-1, 3, 4)
+        if Ks.shape[0] != n or RTs.shape[0] != n:
+            raise L.GpnerfError(f"render_fusion: {n} hull_masks, {Ks.shape[0]} hull_Ks, {RTs.shape[0]} hull_RTs")
+        if not np.array_equal(Ks[:, 2], np.tile([0.0, 0.0, 1.0], (n, 1))):
+            raise L.GpnerfError("render_fusion: a hull_K whose last row is not (0, 0, 1): the rendered depth would not be camera z")
+        prepared = self.prepare_builder_inputs(batch, consts)
+        self.nerfhead.head_blob(dev)
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(5)]
+        ev[0].record()
+        featmaps = self.encode(batch)
+        ev[1].record()
+        frame = self.build_frame(batch, featmaps, consts, prepared)
+        frame.build_occupancy()
+        ev[2].record()
+        depth_maps = torch.empty((n, h, w), device=dev, dtype=torch.float32)
+        inf = torch.full((), float("inf"), device=dev)
+        for v in range(n):
+            rays, mask = F_.select_rays(frame, None, None, h, w, None, None, None, None, neg_ray=False, compact=False,
+                                        host=[Ks[v], RTs[v], vs_host, consts[4], consts[2], consts[3]])
+            idx = torch.nonzero(mask).squeeze(1)
+            if idx.numel():
+                o = F_.render_fused(frame, rays, S, neg_ray=False, early_term=self.early_term, term_eps=self.term_eps, occ_cull=True,
+                                    want=(), split_f16=self.split_f16, ray_order=F_.patch_order_of(idx, w), subset=True)
+                depth_maps[v] = torch.where(o["acc_map"] >= float(acc_min), o["depth_map"] / o["acc_map"], inf).view(h, w)
+            else:
+                depth_maps[v] = inf
+        ev[3].record()
+        axes = F_.dataset_lattice_axes(box, vs_host)
+        step = np.asarray(vs_host, np.float64).ravel()[:3]
+        fusion = F_.DepthFusion([np.float64(a[0]) for a in axes], step, [len(a) for a in axes], float(band_steps) * float(step.max()), dev)
+        stats = [fusion.integrate(depth_maps[g:g + L.FUSION_MAX_VIEWS], Ks[g:g + L.FUSION_MAX_VIEWS], RTs[g:g + L.FUSION_MAX_VIEWS])
+                 for g in range(0, n, L.FUSION_MAX_VIEWS)]
+        sdf = fusion.grid()
+        vertices, faces = sdf.offset_mesh(0.0)
+        ev[4].record()
+        mesh = M_.Mesh(vertices.cpu().numpy(), faces.cpu().numpy())
+        fusion_stats = F_.read_fusion_stats(torch.cat(stats), sdf.stats)
+        t4 = time.time()
+        etime = ev[0].elapsed_time(ev[1]) * 1e-3
+        t_frame, t_render, t_fuse = (ev[i].elapsed_time(ev[i + 1]) * 1e-3 for i in (1, 2, 3))
+        return {"mesh": mesh, "sdf": sdf, "depth_maps": depth_maps, "fusion_stats": fusion_stats,
+                "time_slots": {"frame": t_frame, "render": t_render, "fusion": t_fuse}, "etime": etime, "rtime": max(0.0, (t4 - te) - etime)}
+
     def query_points(self, batch, pts, want=("rgb", "sigma"), occ_cull=False):
         """The frame's radiance field at world points pts [n,3] (device float32): the producers as render_mesh runs them (encoder,
         volumes, frame, occupancy), then frame.query_points under the batch's neg_ray.  Returns its dict of device tensors

@@ -1492,6 +1492,81 @@ int gpnerf_texture_points(const float* points, int64_t n_points, const float* no
                           size_t workspace_bytes, float* color, float* weight, uint8_t* views, int64_t* stats, int64_t* totals,
                           void* stream);
 
+/* ---- fusing depth maps into a truncated signed distance field (gpnerf_fusion.hip): Curless and Levoy's volumetric integration of
+ * calibrated depth maps -- a radiance field's rendered depth, gpnerf_mesh_rasterize's, a sensor's -- on a lattice.  Marching cubes at
+ * the field's zero is the fused surface.  Kernel launches only, on the caller's stream; nothing allocated, nothing waited for; every
+ * launch sized from the arguments alone; no float atomic (integer sums for the counts, into counters a kernel of the library's own
+ * zeroes: no memset node); every call captures into a HIP graph and replays with the same
+ * bytes; the result is a function of the inputs alone.
+ *
+ * The lattice: dims = (nx, ny, nz) POINTS at lo + (i, j, k) * step, lattice HOST double [6] = lo, step: gpnerf_mesh_sdf's layout and
+ * limits (each dims entry >= 1, the product <= 2^28), z fastest in memory.  cams: HOST double [n_views][21] = K 3x3 row-major, then RT
+ * 3x4 row-major, gpnerf_mesh_rasterize's layout; n_views: 1 to 8.  depth: device float [n_views][H][W], CAMERA Z -- gpnerf_mesh_rasterize's
+ * depth, and gpnerf_mesh_raycast's t along gpnerf_pixel_rays' rays; H, W: 1 to 16384.  weights: device float [n_views][H][W], or NULL:
+ * every weight 1.  band: float, finite, > 0, at most 1024 x the smallest step (gpnerf_mesh_sdf's rule).  z_near: > 0 and finite.
+ * carve: 0 or 1.
+ *
+ * THE DEFINITION (gpnerf_fusion_integrate).  All arithmetic float64, multiply then add, unfused, in the order written.
+ * Per (lattice point p, view): the FIRST rule that applies names the pair's fate; every pair has exactly one.
+ *   1. BEHIND.  p_a = float32(lo_a + double(i_a) * step_a) (product and sum in float64, one rounding), widened to float64;
+ *      gpnerf_mesh_rasterize's projection of a vertex (gpnerf_texture_points, rule 1): c = p0 RT[:,0] + p1 RT[:,1] + p2 RT[:,2] +
+ *      RT[:,3], h = c0 K[:,0] + c1 K[:,1] + c2 K[:,2], z = h2, x = h0 / h2, y = h1 / h2.  BEHIND unless x, y and z are finite and z >=
+ *      z_near.
+ *   2. OUTSIDE unless 0 <= x <= W - 1 and 0 <= y <= H - 1 (pixel centres at integer coordinates).
+ *   3. NODATA.  d = depth[view][row rint(y)][column rint(x)] (half to even) and w = the weight there (1 without weights): the NEAREST
+ *      pixel, never a bilinear tap -- a tap across a silhouette would mix +inf into a surface.  NODATA if d is NaN, -inf or <= 0; if w
+ *      is not finite or not > 0; if d = +inf with carve = 0.
+ *   4. EMPTY (background): d = +inf with carve = 1 -- the pixel sees past everything; t = band.
+ *   5. HIDDEN.  s = d - z (d widened).  HIDDEN if s < -band: the pair contributes nothing; bit 0 (GPNERF_FUSION_FLAG_HIDDEN) of the
+ *      point's flag byte is set.
+ *   6. EMPTY (in front): s >= band; t = band.
+ *   7. NEAR otherwise; t = s; bit 1 (GPNERF_FUSION_FLAG_NEAR) of the flag byte is set.
+ * The EMPTY and NEAR pairs of a point contribute in ascending view index: sum = sum + w t, then weight = weight + w.
+ * State, [nx][ny][nz] each: sum and weight device double, flags device uint8.  gpnerf_fusion_reset zeroes it; an integrate call
+ * CONTINUES the sums it is handed, so views 0..7 in one call and views 0..3 then 4..7 in two leave the same bits: that is how more
+ * than eight views are fused.
+ * Finalise (gpnerf_fusion_finalise), per point: weight > 0: value = float32(sum / weight), clamped to [-band, band]; otherwise, bit 0
+ * of the flags set: value = -band (unseen, and behind a surface in some view: interior); otherwise value = +band (unknown reads as
+ * empty).  gpnerf_mesh_sdf's convention: negative inside, +-band where flat.
+ * Counts.  stats: device int64 [n_views][GPNERF_FUSION_FATES], the pairs of each view of THE CALL under their fate (a row sums to
+ * nx ny nz); integrate and oneshot set it.  totals: device int64 [GPNERF_FUSION_TOTALS], set by finalise and oneshot: the points with
+ * weight > 0 (SEEN), with the NEAR bit (SURFACE), interior-filled (INTERIOR), unknown (UNKNOWN); SEEN + INTERIOR + UNKNOWN = nx ny nz.
+ * gpnerf_fusion_oneshot is reset + integrate + finalise of at most eight views in one pass, the sums in registers: sdf, flags (or
+ * NULL), stats and totals EQUAL those three calls' bit for bit; the state is never written.
+ * Launches: reset: one; integrate: the counters' clear (one wavefront) and a sweep over the lattice by at most 768 blocks of 512 lanes,
+ * one lattice point per lane and step, consecutive lanes consecutive k, the views in a loop inside the lane, the cameras in the kernel
+ * argument (scalar loads): one load and one store of the 17-byte state per point; finalise: the clear and the same sweep; oneshot: the
+ * clear and the integrate kernel's other instantiation.  The counts: one integer add per wavefront and counter into the block's LDS,
+ * one per block and counter into memory when the block has swept its share.
+ * GPNERF_E_ARG, before anything is launched: a null depth, cams, lattice, dims, sum, weight, flags (oneshot: flags may be NULL), sdf,
+ * stats or totals where the call takes it; a dims entry < 1 or a product > 2^28; n_views outside 1..8; H or W outside 1..16384; a band
+ * that is NaN, infinite, <= 0 or above 1024 x the smallest step (finalise, which has no lattice: NaN, infinite or <= 0); a z_near
+ * that is not > 0 and finite; carve neither 0 nor 1; a lattice entry that is not finite or a step that is not > 0. */
+#define GPNERF_FUSION_BEHIND 0
+#define GPNERF_FUSION_OUTSIDE 1
+#define GPNERF_FUSION_NODATA 2
+#define GPNERF_FUSION_EMPTY 3
+#define GPNERF_FUSION_HIDDEN 4
+#define GPNERF_FUSION_NEAR 5
+#define GPNERF_FUSION_FATES 6
+#define GPNERF_FUSION_SEEN 0
+#define GPNERF_FUSION_SURFACE 1
+#define GPNERF_FUSION_INTERIOR 2
+#define GPNERF_FUSION_UNKNOWN 3
+#define GPNERF_FUSION_TOTALS 4
+#define GPNERF_FUSION_FLAG_HIDDEN 1
+#define GPNERF_FUSION_FLAG_NEAR 2
+#define GPNERF_FUSION_MAX_VIEWS 8
+int gpnerf_fusion_reset(const int32_t* dims, double* sum, double* weight, uint8_t* flags, void* stream);
+int gpnerf_fusion_integrate(const float* depth, const float* weights, const double* cams, int32_t n_views, int32_t H, int32_t W,
+                            const double* lattice, const int32_t* dims, float band, double z_near, int32_t carve, double* sum,
+                            double* weight, uint8_t* flags, int64_t* stats, void* stream);
+int gpnerf_fusion_finalise(const double* sum, const double* weight, const uint8_t* flags, const int32_t* dims, float band, float* sdf,
+                           int64_t* totals, void* stream);
+int gpnerf_fusion_oneshot(const float* depth, const float* weights, const double* cams, int32_t n_views, int32_t H, int32_t W,
+                          const double* lattice, const int32_t* dims, float band, double z_near, int32_t carve, float* sdf, uint8_t* flags,
+                          int64_t* stats, int64_t* totals, void* stream);
+
 /* ---- per-frame sparse convolution pyramid (gpnerf_volume.hip), replacing the external spconv v1.2.1 calls of
  * libs/nerfheads/networks/SparseConvNet.py:22-111 (SubMConv3d / SparseConv3d + BatchNorm1d + ReLU, .dense()).
  * A sparse tensor is: features [M][C] fp32, coords [M][3] int32 (d,h,w), and a dense int32 index grid [D][H][W]
