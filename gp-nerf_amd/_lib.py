@@ -195,6 +195,13 @@ TEXTURE_STATS = ("used", "behind", "outside", "masked", "backfacing", "occluded"
 TEXTURE_USED, TEXTURE_BEHIND, TEXTURE_OUTSIDE, TEXTURE_MASKED, TEXTURE_BACKFACING, TEXTURE_OCCLUDED, TEXTURE_FATES = range(7)
 TEXTURE_TOTALS = ("seen", "unseen")
 TEXTURE_MAX_VIEWS, TEXTURE_MAX_SHARPNESS, TEXTURE_MAX_CHANNELS = 8, 4, 4
+# gpnerf_atlas_layout's row, gpnerf_atlas_pack's coverage values, gpnerf_atlas_shade's filters and the limits on res (include/gpnerf_hip.h
+# GPNERF_ATLAS_*)
+ATLAS_LAYOUT = ("cells_x", "cells_y", "width", "height", "texels_per_face", "n_texels")
+ATLAS_UNOWNED, ATLAS_SEEN, ATLAS_FALLBACK, ATLAS_GUTTER = range(4)
+ATLAS_SIMPLEX, ATLAS_NEAREST = range(2)
+ATLAS_FILTERS = {"simplex": ATLAS_SIMPLEX, "nearest": ATLAS_NEAREST}
+ATLAS_MIN_RES, ATLAS_MAX_RES = 2, 64
 # gpnerf_fusion_integrate's fates of a (lattice point, view) pair -- the columns of its stats --, finalise's totals, the bits of a
 # point's flag byte and the limit on the views of one call (include/gpnerf_hip.h GPNERF_FUSION_*)
 FUSION_FATES = ("behind", "outside", "nodata", "empty", "hidden", "near")
@@ -368,6 +375,12 @@ SYMBOLS = {
                                         C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_double, C.c_double, C.c_int32, C.c_float,
                                         C.c_int32, C.c_void_p, FP, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                         C.c_void_p, C.c_void_p]),
+    "gpnerf_atlas_layout": (C.c_int, [C.c_int64, C.c_int32, C.POINTER(C.c_int64)]),
+    "gpnerf_atlas_texels": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64,
+                                      C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gpnerf_atlas_pack": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, FP, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gpnerf_atlas_shade": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, DP, C.c_int32, C.c_int32, C.c_int32, C.c_double,
+                                     C.c_void_p, C.c_int32, C.c_int32, C.c_int32, FP, C.c_void_p, C.c_void_p]),
     "gpnerf_fusion_reset": (C.c_int, [C.POINTER(C.c_int32), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gpnerf_fusion_integrate": (C.c_int, [C.c_void_p, C.c_void_p, DP, C.c_int32, C.c_int32, C.c_int32, DP, C.POINTER(C.c_int32), C.c_float,
                                           C.c_double, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -28,16 +28,14 @@ namespace {
 #include "gpnerf_diag.h"       // the lab's hook points, empty in the product (csrc/nodiag/)
 #include "gpnerf_util.h"       // align256, S_, launch_status, blocks_for, sweep_blocks, mesh_ok; wave_count, wave_sum, stat_add
 #include "gpnerf_tri2d.h"      // Mesh, Snapped, Setup, Edges, setup_face, count_states, large_append, lane_walk, wave_walk; LARGE_*
+#include "gpnerf_rasterface.h" // Cams, Setup8, project_vertex, raster_setup, covers, Persp, persp_of, cams_of; RASTER_VIEWS
 
-constexpr int MAX_VIEWS = 8, THREADS = 256, MAX_SIDE = 16384, MAX_ATTRS = 4;
+constexpr int MAX_VIEWS = RASTER_VIEWS, THREADS = 256, MAX_SIDE = 16384, MAX_ATTRS = 4;
 constexpr int COUNT_BLOCKS_MAX = 256;                    // per view, of the silhouette count
-constexpr int SNAP_SHIFT = 8;                            // 256 sub-pixel units per pixel
-constexpr double GUARD = 1048576.0;                      // 2^20 pixels
 constexpr unsigned long long EMPTY = ~0ull;
 
 static_assert(GPNERF_RASTER_DRAWN == FACE_OK && GPNERF_RASTER_SKIPPED_VERTEX == FACE_BAD_VERTEX && GPNERF_RASTER_SKIPPED_AREA == FACE_NO_AREA,
               "count_states adds a face under its state");
-using Setup8 = Setup<SNAP_SHIFT>;
 
 struct Layout { size_t hdr, keys, list, total; };
 
@@ -53,51 +51,6 @@ Layout layout_of(int64_t n_faces, int n_views, int H, int W) {
 
 bool sizes_ok(int64_t n_faces, int n_views, int H, int W) {
     return n_faces >= 0 && n_faces <= INT32_MAX && n_views >= 1 && n_views <= MAX_VIEWS && H >= 1 && W >= 1 && H <= MAX_SIDE && W <= MAX_SIDE;
-}
-
-struct Cams { double cam[MAX_VIEWS][21]; };              // K 3x3 row-major, RT 3x4 row-major: gpnerf_visual_hull's layout
-
-// one vertex in one view: the hull's projection (float64, multiply then add, unfused), the usable test, the snap to 1/256 pixel
-DEV bool project_vertex(const double* __restrict__ cam, const float* __restrict__ p, double z_near, Snapped& s) {
-    const double* K = cam;
-    const double* RT = cam + 9;
-    const double p0 = (double)p[0], p1 = (double)p[1], p2 = (double)p[2];
-    const double c0 = ((p0 * RT[0] + p1 * RT[1]) + p2 * RT[2]) + RT[3];
-    const double c1 = ((p0 * RT[4] + p1 * RT[5]) + p2 * RT[6]) + RT[7];
-    const double c2 = ((p0 * RT[8] + p1 * RT[9]) + p2 * RT[10]) + RT[11];
-    const double h0 = (c0 * K[0] + c1 * K[1]) + c2 * K[2];
-    const double h1 = (c0 * K[3] + c1 * K[4]) + c2 * K[5];
-    const double h2 = (c0 * K[6] + c1 * K[7]) + c2 * K[8];
-    const double x = h0 / h2, y = h1 / h2;
-    // (every comparison is false for a NaN; an infinite x or y fails the guard band, an infinite z is named)
-    if (!(h2 >= z_near) || !(h2 < (double)INFINITY) || !(fabs(x) <= GUARD) || !(fabs(y) <= GUARD)) return false;
-    s.X = (int64_t)rint(256.0 * x);
-    s.Y = (int64_t)rint(256.0 * y);
-    s.z = h2;
-    return true;
-}
-
-// face f in the view of `cam`: its corners projected, A and the pixel box clipped to the image
-DEV FaceState raster_setup(const Mesh& m, const double* __restrict__ cam, double z_near, long f, int H, int W, Setup8& s) {
-    return setup_face(m, f, W, H, [&](const float* p, Snapped& v) { return project_vertex(cam, p, z_near, v); }, s);
-}
-
-// the edge functions each multiplied by sign(A): covered iff none is negative (a pixel exactly on an edge is covered)
-DEV bool covers(const Setup8& s, const Edges& e) {
-    return s.A > 0 ? (e.ea >= 0 && e.eb >= 0 && e.ec >= 0) : (e.ea <= 0 && e.eb <= 0 && e.ec <= 0);
-}
-
-// perspective-correct depth terms of a covered pixel: wk = Ek / A, q = (wa / za + wb / zb) + wc / zc
-struct Persp { double ta, tb, tc, q; };                 // tk = wk / zk
-
-DEV Persp persp_of(const Setup8& s, const Edges& e) {
-    const double A = (double)s.A;
-    Persp p;
-    p.ta = ((double)e.ea / A) / s.a.z;
-    p.tb = ((double)e.eb / A) / s.b.z;
-    p.tc = ((double)e.ec / A) / s.c.z;
-    p.q = (p.ta + p.tb) + p.tc;
-    return p;
 }
 
 DEV unsigned long long key_of(const Setup8& s, const Edges& e, long f) {
@@ -241,11 +194,6 @@ __global__ __launch_bounds__(THREADS) void silhouette_count_kernel(const int32_t
         const int v = wave_sum(cnt[k]);
         if ((threadIdx.x & 63) == 0) stat_add(out + GPNERF_SILHOUETTE_COUNTS * view, k, v);
     }
-}
-
-void cams_of(const double* cams, int n_views, Cams& c) {
-    for (int v = 0; v < MAX_VIEWS; ++v)
-        for (int e = 0; e < 21; ++e) c.cam[v][e] = v < n_views ? cams[v * 21 + e] : 0.0;
 }
 
 }  // namespace

@@ -312,13 +312,17 @@ class MeshEvaluator:
     and adds `texture_psnr` (-10 log10 of the mean square over the counted pixels' channels; the mean over the frames),
     `texture_pixels` (counted pixels, summed), `texture_seen_fraction` (the share of the vertices some colouring view saw), their
     per-frame lists, and saves `<result_path>/texture_metrics.npy`.  A missing key raises a GpnerfError naming it.  Off, nothing
-    changes."""
+    changes.  texture="atlas" runs the same protocol -- the same views, slots, keys and table -- with a per-face texture atlas of
+    `texture_res` texels per face edge in place of the vertex colours: frame.texture_atlas bakes it from the colouring views (the
+    faces' own normals), TextureAtlas.shade draws the held-out views, and `texture_seen_fraction` is the seen share of the owned
+    texels (the table's vertices_seen / vertices_unseen then count texels)."""
     PAD = 10                              # if_nerf_mesh.py:20, the np.pad(cube, 10) of BaseRender.py:269
 
     def __init__(self, result_path, mesh_th, export_mesh=False, metric_samples=100000, metric_thresholds=(0.005, 0.01, 0.02),
                  metric_max_dist=float("inf"), metric_device=None, metric_cell_cap=None, metric_entry_cap=None, silhouette=False,
                  topology=False, volume=False, volume_rule="nonzero", components=False, align=None, align_iterations=10,
-                 align_max_dist=float("inf"), signed=False, signed_band=8, visible=False, texture=False, texture_holdout=4):
+                 align_max_dist=float("inf"), signed=False, signed_band=8, visible=False, texture=False, texture_holdout=4,
+                 texture_res=8):
         self.mesh_th = mesh_th
         self.export_mesh = bool(export_mesh)
         self.result_path = result_path
@@ -348,7 +352,12 @@ class MeshEvaluator:
         self._signed_slots, self._signed_frames = [], []
         self.visible = bool(visible)
         self._visible_slots, self._visible_frames = [], []
+        if texture not in (False, True, None, 0, 1, "atlas"):
+            raise L.GpnerfError(f"MeshEvaluator: texture is False, True (vertex colours) or 'atlas', got {texture!r}")
         self.texture, self.texture_holdout = bool(texture), int(texture_holdout)
+        self.texture_atlas, self.texture_res = texture == "atlas", int(texture_res)
+        if self.texture_atlas and not L.ATLAS_MIN_RES <= self.texture_res <= L.ATLAS_MAX_RES:
+            raise L.GpnerfError(f"MeshEvaluator: texture_res is {L.ATLAS_MIN_RES} to {L.ATLAS_MAX_RES} texels per face edge, got {texture_res!r}")
         if self.texture_holdout < 2:
             raise L.GpnerfError(f"MeshEvaluator: texture_holdout is at least 2 (every texture_holdout-th view is held out), got {texture_holdout!r}")
         self._texture_slots, self._texture_totals, self._texture_frames = [], [], []
@@ -479,13 +488,20 @@ class MeshEvaluator:
         Ks, RTs = F.fetch_host(batch["hull_Ks"][0], batch["hull_RTs"][0])
         v, f = F.mesh_to_device(output["mesh"].to_lattice_frame(output["axes"], self.PAD), masks.device)
         grid = F.build_mesh_grid(v, f, cell_cap=self.metric_cell_cap, entry_cap=self.metric_entry_cap, check=False)
-        tex = F.texture_mesh(v, f, Ks[source], RTs[source], imgs[source].contiguous(), grid=grid, masks=masks[source].contiguous(),
-                             want=("color",))
-        drawn = F.rasterize_mesh(v, f, Ks[held], RTs[held], h, w, want=("face_id",), attributes=tex["color"])
+        if self.texture_atlas:
+            atlas = F.texture_atlas(v, f, Ks[source], RTs[source], imgs[source].contiguous(), res=self.texture_res, grid=grid,
+                                    masks=masks[source].contiguous())
+            drawn = F.rasterize_mesh(v, f, Ks[held], RTs[held], h, w, want=("face_id",))
+            image, totals = atlas.shade(drawn["face_id"], v, f, Ks[held], RTs[held]), atlas.totals
+        else:
+            tex = F.texture_mesh(v, f, Ks[source], RTs[source], imgs[source].contiguous(), grid=grid, masks=masks[source].contiguous(),
+                                 want=("color",))
+            drawn = F.rasterize_mesh(v, f, Ks[held], RTs[held], h, w, want=("face_id",), attributes=tex["color"])
+            image, totals = drawn["image"], tex["totals"]
         counted = (drawn["face_id"] >= 0) & (masks[held] == 1)
-        diff = torch.where(counted[..., None], drawn["image"] - imgs[held], torch.full((), float("nan"), device=masks.device))
+        diff = torch.where(counted[..., None], image - imgs[held], torch.full((), float("nan"), device=masks.device))
         self._texture_slots.append(F.distance_stats(diff.contiguous().reshape(-1)))
-        self._texture_totals.append(tex["totals"])
+        self._texture_totals.append(totals)
         self._texture_frames.append(self._scalar(batch["frame_index"]))
 
     def _summarize_texture(self):

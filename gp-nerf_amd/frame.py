@@ -2300,6 +2300,197 @@ def read_texture_stats(stats, totals):
     return res
 
 
+# ---- a per-face texture atlas (csrc/gpnerf_atlas.hip)
+
+def atlas_layout(n_faces, res):
+    """gpnerf_atlas_layout (host arithmetic only) -> {name: int} for _lib.ATLAS_LAYOUT: the cells across and down, the image's width and
+    height, the texels per face and in all.  Raises for what the atlas calls refuse (res outside 2..64, an image side above 16384,
+    2^31 texels or more)."""
+    row = (C.c_int64 * len(L.ATLAS_LAYOUT))()
+    lib = L.lib()
+    try:
+        code = lib.gpnerf_atlas_layout(int(n_faces), int(res), row)
+    except (C.ArgumentError, OverflowError, TypeError, ValueError):
+        code = -1
+    if code != 0:
+        raise L.GpnerfError(f"atlas_layout: refused ({n_faces} faces, res {res}; res is {L.ATLAS_MIN_RES} to {L.ATLAS_MAX_RES}, the image at most "
+                            "16384 x 16384, fewer than 2^31 texels)")
+    return dict(zip(L.ATLAS_LAYOUT, (int(v) for v in row)))
+
+
+def _vertex_rows(t, nv, dev, what, channels=None):
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32 or t.dim() != 2 or t.shape[0] != nv or not t.is_contiguous() \
+            or t.device != dev or (channels is not None and t.shape[1] != channels):
+        raise L.GpnerfError(f"{what}: expected a contiguous float32 [{nv},{channels or 'C'}] tensor on {dev}")
+    return t
+
+
+def atlas_texels(vertices, faces, res, normals=None, attrs=None, first_face=0, count=None, want=("points", "normals")):
+    """gpnerf_atlas_texels: the surface points of the atlas's texels for the faces first_face .. first_face + count - 1 (default: to the
+    last) of a device mesh, in global texel order.  Returns a dict of device float32 tensors: "points" [T,3] and "normals" [T,3] as
+    `want` names them -- the corners' `normals` (device float32 [nv,3]) combined with the texel's weights, or without them the face's
+    cross product, not normalised --, and "attrs" [T,C] when per-vertex `attrs` (device float32 [nv,C], C <= 4) are given.  A face with
+    an index out of range gives NaN rows.  Nothing is read back."""
+    lib = L.lib()
+    vertices, faces = _raster_mesh(vertices, faces, "atlas_texels")
+    unknown = set(want) - {"points", "normals"}
+    if unknown:
+        raise L.GpnerfError(f"atlas_texels: want names {sorted(unknown)}; points and normals are what there is (attrs come with `attrs`)")
+    nv, nf, dev = int(vertices.shape[0]), int(faces.shape[0]), vertices.device
+    lay = atlas_layout(nf, res)
+    first_face = int(first_face)
+    count = nf - first_face if count is None else int(count)
+    if first_face < 0 or count < 0 or first_face + count > nf:
+        raise L.GpnerfError(f"atlas_texels: faces {first_face} .. {first_face + count - 1} of {nf}")
+    if normals is not None:
+        _vertex_rows(normals, nv, dev, "atlas_texels: normals", 3)
+    c = 1
+    if attrs is not None:
+        _vertex_rows(attrs, nv, dev, "atlas_texels: attrs")
+        c = int(attrs.shape[1])
+        if not 1 <= c <= L.TEXTURE_MAX_CHANNELS:
+            raise L.GpnerfError(f"atlas_texels: 1 to {L.TEXTURE_MAX_CHANNELS} attribute channels, got {c}")
+    n = count * lay["texels_per_face"]
+    res_ = {}
+    if "points" in want:
+        res_["points"] = torch.empty((n, 3), device=dev, dtype=torch.float32)
+    if "normals" in want:
+        res_["normals"] = torch.empty((n, 3), device=dev, dtype=torch.float32)
+    if attrs is not None:
+        res_["attrs"] = torch.empty((n, c), device=dev, dtype=torch.float32)
+    ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None
+    L.check(lib.gpnerf_atlas_texels(ptr(vertices), nv, ptr(faces), nf, ptr(normals), ptr(attrs), c, int(res), first_face, count,
+                                    ptr(res_.get("points")), ptr(res_.get("normals")), ptr(res_.get("attrs")), _stream_ptr(dev)),
+            "gpnerf_atlas_texels")
+    return res_
+
+
+class TextureAtlas:
+    """texture_atlas' result, device tensors throughout: `image` float32 [Ht,Wt,C] and `coverage` uint8 [Ht,Wt] (_lib.ATLAS_UNOWNED, _SEEN,
+    _FALLBACK, _GUTTER), the lists in global texel order `colors` [T,C], `weight` [T] and `views` uint8 [T] (texture_points' outputs
+    for the texels), `stats` int64 [m,6] and `totals` int64 [2] counted over TEXELS (read_texture_stats reads them as they are), `res`,
+    `n_faces` and `layout` (atlas_layout's dict)."""
+
+    def __init__(self, image, coverage, colors, weight, views, stats, totals, res, n_faces, layout):
+        self.image, self.coverage, self.colors, self.weight, self.views = image, coverage, colors, weight, views
+        self.stats, self.totals, self.res, self.n_faces, self.layout = stats, totals, int(res), int(n_faces), layout
+
+    def face_uvs(self):
+        """host float64 [n_faces,3,2]: the (u, v) of every face's corner texels a, b, c -- texel centres of the image, OBJ's v up"""
+        return atlas_face_uvs(self.n_faces, self.res)
+
+    def shade(self, face_id, vertices, faces, Ks, RTs, filter="simplex", background=0.0, z_near=1e-6):
+        """gpnerf_atlas_shade: the mesh drawn from this atlas over rasterize_mesh's `face_id` (device int32 [n,H,W], same mesh, cameras
+        and z_near) -> device float32 [n,H,W,C]; a pixel no face of its own covers takes `background` (a number or C numbers).
+        filter: "simplex" (barycentric on the face's texel lattice) or "nearest".  Only the face's own texels are read."""
+        lib = L.lib()
+        if filter not in L.ATLAS_FILTERS:
+            raise L.GpnerfError(f"TextureAtlas.shade: filter is 'simplex' or 'nearest', got {filter!r}")
+        vertices, faces = _raster_mesh(vertices, faces, "TextureAtlas.shade")
+        nv, nf, dev = int(vertices.shape[0]), int(faces.shape[0]), vertices.device
+        if nf != self.n_faces or self.image.device != dev:
+            raise L.GpnerfError(f"TextureAtlas.shade: the atlas was baked for {self.n_faces} faces on {self.image.device}, got {nf} on {dev}")
+        cams = _raster_cams(Ks, RTs, "TextureAtlas.shade")
+        n = cams.shape[0]
+        if not isinstance(face_id, torch.Tensor) or not face_id.is_cuda or face_id.dtype != torch.int32 or face_id.dim() != 3 \
+                or face_id.shape[0] != n or not face_id.is_contiguous() or face_id.device != dev:
+            raise L.GpnerfError(f"TextureAtlas.shade: expected a contiguous int32 face_id [{n},H,W] on {dev}")
+        H, W = int(face_id.shape[1]), int(face_id.shape[2])
+        c = int(self.image.shape[2])
+        bg = np.broadcast_to(np.asarray(background, dtype=np.float32), (c,))
+        out = torch.empty((n, H, W, c), device=dev, dtype=torch.float32)
+        ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None
+        L.check(lib.gpnerf_atlas_shade(face_id.data_ptr(), ptr(vertices), nv, ptr(faces), nf, cams.ctypes.data_as(L.DP), n, H, W, float(z_near),
+                                       ptr(self.image), self.res, c, L.ATLAS_FILTERS[filter], (C.c_float * c)(*[float(b) for b in bg]),
+                                       out.data_ptr(), _stream_ptr(dev)), "gpnerf_atlas_shade")
+        return out
+
+
+def atlas_face_uvs(n_faces, res):
+    """host float64 [n_faces,3,2]: (u, v) of the corner texels a = (0, 0), b = (res - 1, 0), c = (0, res - 1) of every face under the
+    packing of include/gpnerf_hip.h: u = (X + 0.5) / Wt, v = 1 - (Y + 0.5) / Ht"""
+    lay = atlas_layout(n_faces, res)
+    R = int(res)
+    f = np.arange(int(n_faces), dtype=np.int64)
+    q, odd = f // 2, (f % 2).astype(bool)
+    i, j = np.array([0, R - 1, 0], np.int64), np.array([0, 0, R - 1], np.int64)
+    x = np.where(odd[:, None], R + 1 - i[None], i[None])
+    y = np.where(odd[:, None], R - 1 - j[None], j[None])
+    cx = max(lay["cells_x"], 1)
+    X, Y = (q % cx)[:, None] * (R + 2) + x, (q // cx)[:, None] * R + y
+    return np.stack([(X + 0.5) / max(lay["width"], 1), 1.0 - (Y + 0.5) / max(lay["height"], 1)], axis=-1)
+
+
+def atlas_pack(colors, views, n_faces, res, background=0.0):
+    """gpnerf_atlas_pack: the colour list (device float32 [T,C], global texel order) into the image -> (image float32 [Ht,Wt,C],
+    coverage uint8 [Ht,Wt]).  views: device uint8 [T] (a texel whose bits are 0 is on its fallback) or None.  A gather: every image
+    texel reads its owner's row; a gutter texel takes the mean of its owned neighbours, an unowned one `background`."""
+    lib = L.lib()
+    lay = atlas_layout(n_faces, res)
+    t = lay["n_texels"]
+    if not isinstance(colors, torch.Tensor) or not colors.is_cuda or colors.dtype != torch.float32 or colors.dim() != 2 or colors.shape[0] != t \
+            or not colors.is_contiguous() or not 1 <= colors.shape[1] <= L.TEXTURE_MAX_CHANNELS:
+        raise L.GpnerfError(f"atlas_pack: expected contiguous float32 colors [{t},C] on the GPU, C <= {L.TEXTURE_MAX_CHANNELS}")
+    dev, c = colors.device, int(colors.shape[1])
+    if views is not None and (not isinstance(views, torch.Tensor) or views.dtype != torch.uint8 or tuple(views.shape) != (t,)
+                              or not views.is_contiguous() or views.device != dev):
+        raise L.GpnerfError(f"atlas_pack: expected contiguous uint8 views [{t}] on {dev}")
+    bg = np.broadcast_to(np.asarray(background, dtype=np.float32), (c,))
+    image = torch.empty((lay["height"], lay["width"], c), device=dev, dtype=torch.float32)
+    coverage = torch.empty((lay["height"], lay["width"]), device=dev, dtype=torch.uint8)
+    ptr = lambda a: a.data_ptr() if a is not None and a.numel() else None
+    L.check(lib.gpnerf_atlas_pack(ptr(colors), ptr(views), int(n_faces), int(res), c, (C.c_float * c)(*[float(b) for b in bg]), ptr(image),
+                                  ptr(coverage), _stream_ptr(dev)), "gpnerf_atlas_pack")
+    return image, coverage
+
+
+def texture_atlas(vertices, faces, Ks, RTs, images, res=8, normals=None, masks=None, grid=None, fallback=None, chunk_texels=1 << 20,
+                  background=0.0, **kw):
+    """A per-face texture atlas of a device mesh baked from calibrated views -> TextureAtlas.  The faces are walked in chunks of at
+    most chunk_texels texels (at least one face): atlas_texels gives the chunk's surface points and normals (the corners' `normals`,
+    device float32 [nv,3], combined; without them the faces' own), texture_points colours them -- UNCHANGED: Ks, RTs, images, masks and
+    the keywords mode, sharpness, cos_min, eps, z_near are its, the mesh hides its own texels through `grid` (built when none is
+    given, as texture_mesh does: build_mesh_grid's check is then the call's one host read) -- into slices of one colour, weight and
+    view-bits list, the counts are added on the device, and atlas_pack makes the image.  fallback: per-VERTEX colours, device float32
+    [nv,C], spread over the texels by atlas_texels: what a texel no view sees keeps (without it: background).  A chunked bake equals
+    an unchunked one bit for bit; the chunk bounds texture_points' workspace (49 bytes per texel and view)."""
+    nv, nf = _mesh_tensors(vertices, faces, "texture_atlas")
+    dev = vertices.device
+    for name in ("vertices", "faces", "want", "points"):
+        if name in kw:
+            raise L.GpnerfError(f"texture_atlas: {name} is not a keyword of the bake")
+    lay = atlas_layout(nf, res)
+    tpf, t = lay["texels_per_face"], lay["n_texels"]
+    if int(chunk_texels) < 1:
+        raise L.GpnerfError(f"texture_atlas: chunk_texels must be at least 1, got {chunk_texels}")
+    if grid is None:
+        grid = build_mesh_grid(vertices, faces)
+    elif not isinstance(grid, MeshGrid):
+        raise L.GpnerfError("texture_atlas: grid must be a MeshGrid (build_mesh_grid)")
+    if not isinstance(images, torch.Tensor) or images.dim() != 4:
+        raise L.GpnerfError("texture_atlas: images must be a device tensor [m,H,W,C]")
+    m, c = int(images.shape[0]), int(images.shape[3])
+    if fallback is not None:
+        _vertex_rows(fallback, nv, dev, "texture_atlas: fallback", c)
+    colors = torch.empty((t, c), device=dev, dtype=torch.float32)
+    weight = torch.empty((t,), device=dev, dtype=torch.float32)
+    views = torch.empty((t,), device=dev, dtype=torch.uint8)
+    stats = torch.zeros((m, L.TEXTURE_FATES), device=dev, dtype=torch.int64)
+    totals = torch.zeros((2,), device=dev, dtype=torch.int64)
+    per = max(1, int(chunk_texels) // tpf)
+    for first in range(0, nf, per):
+        count = min(per, nf - first)
+        tex = atlas_texels(vertices, faces, res, normals=normals, attrs=fallback, first_face=first, count=count)
+        got = texture_points(tex["points"], Ks, RTs, images, normals=tex["normals"], masks=masks, grid=grid, fallback=tex.get("attrs"),
+                             background=background, **kw)
+        rows = slice(first * tpf, (first + count) * tpf)
+        colors[rows], weight[rows], views[rows] = got["color"], got["weight"], got["views"]
+        stats += got["stats"]
+        totals += got["totals"]
+    image, coverage = atlas_pack(colors, views, nf, res, background=background)
+    return TextureAtlas(image, coverage, colors, weight, views, stats, totals, res, nf, lay)
+
+
 # ---- fusing depth maps into a truncated signed distance field (csrc/gpnerf_fusion.hip)
 
 def _fusion_band(band, lat, what):

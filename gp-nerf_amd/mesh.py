@@ -17,6 +17,10 @@ cube, as mcubes returns them), `.faces` (int64 [nf,3]) and `.export(path)`, the 
     i.e. toward lower values.
 These are NOT the published triangle lists: those cannot be compared with here, and neither can PyMCubes' tie rule.
 """
+import os
+import struct
+import zlib
+
 import numpy as np
 
 # corner c -> (dx, dy, dz)
@@ -89,12 +93,14 @@ def case_tables():
 
 class Mesh:
     """vertices float64 [nv,3], faces int64 [nf,3] (trimesh's names), vertex_colors float32 [nv,3] in [0, 1] or None, vertex_normals
-    float32 [nv,3] or None; export() writes a binary little-endian PLY.  The vertices are marching cubes' (one per crossed lattice edge)
+    float32 [nv,3] or None, texture float32 [Ht,Wt,3] in [0, 1] with face_uvs float64 [nf,3,2] (a texture atlas: frame.texture_atlas'
+    image and its face_uvs(); both or neither); export() writes a binary little-endian PLY, or a Wavefront OBJ with its material and
+    the texture as a PNG.  The vertices are marching cubes' (one per crossed lattice edge)
     or, with the renderer's mesh_simplify, one per occupied cell of the clustering grid (frame.simplify_mesh), still in index units of
     the cube, and with mesh_smooth moved by Taubin's filter (frame.smooth_mesh); colours and normals belong to whichever vertices the
     mesh carries."""
 
-    def __init__(self, vertices, faces, vertex_colors=None, vertex_normals=None):
+    def __init__(self, vertices, faces, vertex_colors=None, vertex_normals=None, texture=None, face_uvs=None):
         self.vertices = np.ascontiguousarray(vertices, dtype=np.float64).reshape(-1, 3)
         self.faces = np.ascontiguousarray(faces, dtype=np.int64).reshape(-1, 3)
         self.vertex_colors = None
@@ -107,18 +113,34 @@ class Mesh:
             self.vertex_normals = np.ascontiguousarray(vertex_normals, dtype=np.float32).reshape(-1, 3)
             if len(self.vertex_normals) != len(self.vertices):
                 raise ValueError(f"{len(self.vertex_normals)} vertex normals for {len(self.vertices)} vertices")
+        self.texture = self.face_uvs = None
+        if (texture is None) != (face_uvs is None):
+            raise ValueError("a texture comes with the faces' UVs, and UVs with a texture")
+        if texture is not None:
+            self.texture = np.ascontiguousarray(texture, dtype=np.float32)
+            if self.texture.ndim != 3 or self.texture.shape[2] != 3:
+                raise ValueError(f"texture: expected [height, width, 3], got {self.texture.shape}")
+            self.face_uvs = np.ascontiguousarray(face_uvs, dtype=np.float64).reshape(-1, 3, 2)
+            if len(self.face_uvs) != len(self.faces):
+                raise ValueError(f"{len(self.face_uvs)} faces' UVs for {len(self.faces)} faces")
 
     def __repr__(self):
         c = "" if self.vertex_colors is None else ", coloured"
         n = "" if self.vertex_normals is None else ", normals"
-        return f"Mesh(vertices={len(self.vertices)}, faces={len(self.faces)}{c}{n})"
+        t = "" if self.texture is None else f", texture {self.texture.shape[1]} x {self.texture.shape[0]}"
+        return f"Mesh(vertices={len(self.vertices)}, faces={len(self.faces)}{c}{n}{t})"
 
     def export(self, file_obj, file_type="ply"):
         """Binary little-endian PLY: float64 x y z per vertex (the array as it is) -- followed, when the mesh has vertex normals, by
         float32 nx ny nz and, when it has vertex colours, by uchar red green blue = clip(rint(255 c), 0, 255) -- and one
-        uint8-counted int32 index list per face."""
+        uint8-counted int32 index list per face.
+        file_type="obj" (a path, not a file object): a Wavefront OBJ -- `v` lines with 17 significant digits, and for a textured mesh
+        three `vt` lines per face and `f v/vt` items -- with, for a textured mesh, `<stem>.mtl` and `<stem>.png` next to it: the
+        texture as 8-bit RGB through colour_bytes (write_png).  A mesh without a texture is written as `v` and `f` lines alone."""
+        if file_type == "obj":
+            return self._export_obj(file_obj)
         if file_type != "ply":
-            raise ValueError("only PLY is written (trimesh is not a dependency)")
+            raise ValueError("PLY and OBJ are written (trimesh is not a dependency)")
         if len(self.faces) and (self.faces.min() < 0 or self.faces.max() >= len(self.vertices) or len(self.vertices) >= 2 ** 31):
             raise ValueError("face indices out of range for a PLY int32 list")
         normal = ("property float nx\nproperty float ny\nproperty float nz\n" if self.vertex_normals is not None else "")
@@ -150,10 +172,33 @@ class Mesh:
                 f.write(head + body)
 
 
+    def _export_obj(self, path):
+        if hasattr(path, "write"):
+            raise ValueError("an OBJ is written to a path: its material and texture go next to it")
+        if len(self.faces) and (self.faces.min() < 0 or self.faces.max() >= len(self.vertices)):
+            raise ValueError("face indices out of range")
+        stem = os.path.splitext(os.path.basename(path))[0]
+        folder = os.path.dirname(os.path.abspath(path))
+        lines = ["# gp-nerf_amd mesh"]
+        if self.texture is not None:
+            lines += [f"mtllib {stem}.mtl", "usemtl atlas"]
+        lines += ["v %.17g %.17g %.17g" % tuple(v) for v in self.vertices]
+        if self.texture is not None:
+            lines += ["vt %.17g %.17g" % tuple(uv) for uv in self.face_uvs.reshape(-1, 2)]
+            lines += ["f %d/%d %d/%d %d/%d" % (f[0] + 1, 3 * k + 1, f[1] + 1, 3 * k + 2, f[2] + 1, 3 * k + 3) for k, f in enumerate(self.faces)]
+        else:
+            lines += ["f %d %d %d" % (f[0] + 1, f[1] + 1, f[2] + 1) for f in self.faces]
+        with open(path, "w") as fh:
+            fh.write("\n".join(lines) + "\n")
+        if self.texture is not None:
+            with open(os.path.join(folder, stem + ".mtl"), "w") as fh:
+                fh.write(f"newmtl atlas\nKa 1 1 1\nKd 1 1 1\nKs 0 0 0\nillum 1\nmap_Kd {stem}.png\n")
+            write_png(os.path.join(folder, stem + ".png"), colour_bytes(self.texture))
+
     def to_lattice_frame(self, axes, pad):
         """The mesh in the coordinates of the lattice axes (the frame a scan is given in) from marching-cubes vertices in index units of
         the padded cube: per axis axes[a][0] + (v[a] - pad) * step[a], step[a] = (axes[a][-1] - axes[a][0]) / (len(axes[a]) - 1), all
-        in float64 on the host (an axis of one point has step 1).  A new Mesh: faces and colours carried over, normals -- gradients,
+        in float64 on the host (an axis of one point has step 1).  A new Mesh: faces, colours, texture and UVs carried over, normals -- gradients,
         which scale with the inverse step -- divided by the step and renormalised (a zero normal stays zero)."""
         ax = [np.asarray(a.detach().cpu() if hasattr(a, "detach") else a, dtype=np.float64).reshape(-1) for a in axes]
         if len(ax) != 3 or any(len(a) < 1 for a in ax):
@@ -166,12 +211,27 @@ class Mesh:
             n = self.vertex_normals.astype(np.float64) / step
             length = np.sqrt((n * n).sum(axis=1, keepdims=True))
             normals = np.where(length > 0, n / np.where(length > 0, length, 1.0), 0.0).astype(np.float32)
-        return Mesh(verts, self.faces.copy(), None if self.vertex_colors is None else self.vertex_colors.copy(), normals)
+        return Mesh(verts, self.faces.copy(), None if self.vertex_colors is None else self.vertex_colors.copy(), normals,
+                    None if self.texture is None else self.texture.copy(), None if self.face_uvs is None else self.face_uvs.copy())
 
 
 def colour_bytes(c):
     """float colours in [0, 1] -> uint8: clip(rint(255 c), 0, 255), in float32"""
     return np.clip(np.rint(np.float32(255) * np.asarray(c, dtype=np.float32)), 0, 255).astype(np.uint8)
+
+
+def write_png(path, rgb_uint8):
+    """An 8-bit RGB PNG of uint8 [height, width, 3], row 0 at the top: IHDR, one IDAT holding one zlib stream of the rows, each behind
+    filter byte 0, and IEND.  The standard library only."""
+    rgb = np.ascontiguousarray(rgb_uint8)
+    if rgb.dtype != np.uint8 or rgb.ndim != 3 or rgb.shape[2] != 3 or rgb.shape[0] < 1 or rgb.shape[1] < 1:
+        raise ValueError(f"write_png: expected uint8 [height, width, 3] with at least one pixel, got {rgb.dtype} {rgb.shape}")
+    h, w = rgb.shape[:2]
+    rows = np.concatenate([np.zeros((h, 1), np.uint8), rgb.reshape(h, 3 * w)], axis=1).tobytes()
+    chunk = lambda kind, data: struct.pack(">I", len(data)) + kind + data + struct.pack(">I", zlib.crc32(kind + data) & 0xFFFFFFFF)
+    with open(path, "wb") as fh:
+        fh.write(b"\x89PNG\r\n\x1a\n" + chunk(b"IHDR", struct.pack(">IIBBBBB", w, h, 8, 2, 0, 0, 0)) + chunk(b"IDAT", zlib.compress(rows, 6))
+                 + chunk(b"IEND", b""))
 
 
 _PLY_TYPES = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short": "<i2", "int16": "<i2", "ushort": "<u2", "uint16": "<u2",

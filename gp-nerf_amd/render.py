@@ -54,13 +54,26 @@ def parse_mesh_clean(value):
 
 
 def parse_mesh_texture(value):
-    """Renderer(mesh_texture=...) / GPNERF_MESH_TEXTURE -> None (off) or "views": off is None, False, 0, "0" or ""; anything else is
-    refused."""
+    """Renderer(mesh_texture=...) / GPNERF_MESH_TEXTURE -> None (off), "views" or "atlas": off is None, False, 0, "0" or ""; anything
+    else is refused."""
     if value is None or value is False or value == 0 or (isinstance(value, str) and value.strip() in ("", "0")):
         return None
-    if isinstance(value, str) and value.strip() == "views":
-        return "views"
-    raise L.GpnerfError(f"mesh_texture / GPNERF_MESH_TEXTURE: expected 0 or 'views', got {value!r}")
+    if isinstance(value, str) and value.strip() in ("views", "atlas"):
+        return value.strip()
+    raise L.GpnerfError(f"mesh_texture / GPNERF_MESH_TEXTURE: expected 0, 'views' or 'atlas', got {value!r}")
+
+
+def parse_mesh_texture_res(value):
+    """Renderer(mesh_texture_res=...) / GPNERF_MESH_TEXTURE_RES -> the atlas's texels along a face edge, 2 to 64"""
+    try:
+        res = int(str(value).strip()) if isinstance(value, str) else int(value)
+        ok = not isinstance(value, bool) and res == (float(value) if not isinstance(value, str) else res)
+    except (TypeError, ValueError):
+        ok, res = False, 0
+    if not ok or not L.ATLAS_MIN_RES <= res <= L.ATLAS_MAX_RES:
+        raise L.GpnerfError(f"mesh_texture_res / GPNERF_MESH_TEXTURE_RES: expected {L.ATLAS_MIN_RES} to {L.ATLAS_MAX_RES} texels per face edge, "
+                            f"got {value!r}")
+    return res
 
 
 class Renderer(nn.Module):
@@ -68,7 +81,7 @@ class Renderer(nn.Module):
                  n_samples=64, voxel_size=(0.005, 0.005, 0.005), chunk=64, mesh_th=-1, early_term=None, term_eps=1e-5,
                  progressive=False, split_f16=None, sharded_outputs="all", shard_group=None, encoder_graph=None, fold_levels=None, reserve_cus=None,
                  mesh_colors=None, mesh_clean=None, mesh_normals=None, mesh_simplify=None, mesh_smooth=None, mesh_topology=None,
-                 mesh_components=None, mesh_texture=None):
+                 mesh_components=None, mesh_texture=None, mesh_texture_res=None):
         super().__init__()
         self.encoder = encoder
         self.nerfhead = nerfhead
@@ -148,11 +161,17 @@ class Renderer(nn.Module):
         # nine counts of _lib.COMPONENT_STATS as mesh_<name>.  Off by default.
         self.mesh_components = F_.parse_components(os.environ.get("GPNERF_MESH_COMPONENTS", "0") if mesh_components is None else mesh_components,
                                                    "mesh_components / GPNERF_MESH_COMPONENTS")
-        # mesh_texture (GPNERF_MESH_TEXTURE = unset / 0 (off) or views): the final mesh's vertices take their colours from the frame's
+        # mesh_texture (GPNERF_MESH_TEXTURE = unset / 0 (off), views or atlas).  views: the final mesh's vertices take their colours from the frame's
         # source views (frame.texture_mesh: projected, culled by facing and by the mesh itself, sampled and blended); a vertex no view
         # sees keeps the field's rgb, the colour mesh_colors gives.  `mesh_stats` gains the per-view counts as texture_<name> (lists,
         # _lib.TEXTURE_STATS) and texture_seen / texture_unseen.  Off by default.
+        # "atlas": instead, the mesh gains `texture` (float32 [Ht,Wt,3]) and `face_uvs`: a per-face atlas of mesh_texture_res
+        # (GPNERF_MESH_TEXTURE_RES, default 8) texels per face edge baked from the source views (frame.texture_atlas), the field's
+        # rgb at the vertices spread over the texels no view sees; the texture_* counts are then over TEXELS.  Mesh.export(path,
+        # file_type="obj") writes it with its material and PNG.
         self.mesh_texture = parse_mesh_texture(os.environ.get("GPNERF_MESH_TEXTURE", "0") if mesh_texture is None else mesh_texture)
+        self.mesh_texture_res = parse_mesh_texture_res(os.environ.get("GPNERF_MESH_TEXTURE_RES", "8") if mesh_texture_res is None
+                                                       else mesh_texture_res)
 
     # ---- helpers the reference exposes as methods (stage entry points) ----------------------------
     def _neg_ray(self, batch):
@@ -349,23 +368,35 @@ class Renderer(nn.Module):
         return stats
 
     def _mesh_colours(self, frame, m, consts, neg):
-        """(colours device float32 [nv,3] or None, texture counts or None) of extract_mesh's result: the field's rgb at the vertices
-        with mesh_colors; with mesh_texture the source views' colours (frame.texture_mesh), the field's rgb where no view sees the
-        vertex.  The lattice lives in the world frame -- the frame src_poses map from: query_points projects these very points with
+        """(colours device float32 [nv,3] or None, texture counts or None, TextureAtlas or None) of extract_mesh's result: the field's
+        rgb at the vertices with mesh_colors; with mesh_texture "views" the source views' colours (frame.texture_mesh), the field's rgb
+        where no view sees the vertex; with "atlas" the vertices keep what mesh_colors gives them and the atlas is baked from the same
+        views with the same cameras and normals (frame.texture_atlas), the field's raw colours at the vertices as its fallback.  The lattice lives in the world frame -- the frame src_poses map from: query_points projects these very points with
         K P --, so the cameras are the batch's as they are; under neg_ray, where a point in front of a view has h_z < 0, the pose is
         negated on the host (K (-P) p = -h: the same pixel, z > 0; the eye -R^T T is unchanged)."""
         if not self.mesh_colors and self.mesh_texture is None:
-            return None, None
+            return None, None, None
         field = F_.query_points(frame, m["vertices"], neg_ray=neg, want=("rgb",), lattice=m["lattice"])
         if self.mesh_texture is None or int(m["faces"].shape[0]) == 0:        # (an empty mesh has nothing to colour or to hide behind)
-            return field["rgb"], None
+            return field["rgb"], None, None
         lo, step, pad = m["lattice"]
         dev = m["vertices"].device
         lo_t, step_t = torch.tensor(lo, dtype=torch.float64, device=dev), torch.tensor(step, dtype=torch.float64, device=dev)
         world = (lo_t + (m["vertices"].to(torch.float64) - float(pad)) * step_t).to(torch.float32).contiguous()   # query_points' formula
         Ks, poses = np.asarray(consts[0], np.float64).reshape(-1, 3, 3), np.asarray(consts[1], np.float64).reshape(-1, 3, 4)
+        if self.mesh_texture == "atlas":
+            atlas = F_.texture_atlas(world, m["faces"], Ks, -poses if neg else poses, frame.imgs, res=self.mesh_texture_res, normals=m["normals"],
+                                     fallback=field["raw"])
+            return field["rgb"] if self.mesh_colors else None, (atlas.stats, atlas.totals), atlas
         tex = F_.texture_mesh(world, m["faces"], Ks, -poses if neg else poses, frame.imgs, normals=m["normals"], fallback=field["raw"])
-        return tex["color"][:, :3], (tex["stats"], tex["totals"])
+        return tex["color"][:, :3], (tex["stats"], tex["totals"]), None
+
+    @staticmethod
+    def _mesh_atlas(atlas):
+        """Mesh's texture keywords from a baked atlas (the image's first three channels, on the host), or none"""
+        if atlas is None:
+            return {}
+        return {"texture": atlas.image[:, :, :3].cpu().numpy(), "face_uvs": atlas.face_uvs()}
 
     @staticmethod
     def _texture_stats(stats, counts):
@@ -397,7 +428,10 @@ class Renderer(nn.Module):
         _lib.COMPONENT_STATS as mesh_<name> (of the mesh before the filter, and what was kept).  With mesh_texture ("views") the final
         mesh's vertex_colors come from the frame's source views (frame.texture_mesh on the vertices in the lattice's frame, the cube's
         geometric normals, hidden by the mesh itself: one more host read, the grid's status), the field's rgb where no view sees a
-        vertex, and `mesh_stats` gains texture_<name> per view (_lib.TEXTURE_STATS) and texture_seen / texture_unseen.  With all of
+        vertex, and `mesh_stats` gains texture_<name> per view (_lib.TEXTURE_STATS) and texture_seen / texture_unseen.  With mesh_texture
+        "atlas" the mesh carries `texture` and `face_uvs` instead -- a per-face atlas of mesh_texture_res texels per face edge baked from
+        the same views (frame.texture_atlas), the field's raw colours where no view sees a texel -- and the texture_* counts are over
+        texels.  With all of
         them off, extract_mesh enqueues exactly the launches it did before there were these options."""
         dev = batch["src_imgs"].device
         torch.cuda.synchronize(dev)
@@ -418,11 +452,11 @@ class Renderer(nn.Module):
                             iso=M_.ISO_REFERENCE, host=box_host, clean=self.mesh_clean, normals=self.mesh_normals or self.mesh_texture is not None,
                             simplify=self.mesh_simplify, smooth=self.mesh_smooth, topology=self.mesh_topology,
                             components=self.mesh_components)
-        colours, texture = self._mesh_colours(frame, m, consts, self._neg_ray(batch))
+        colours, texture, atlas = self._mesh_colours(frame, m, consts, self._neg_ray(batch))
         ev[3].record()
         cube = m["cube"].cpu().numpy()
         mesh = M_.Mesh(m["vertices"].cpu().numpy(), m["faces"].cpu().numpy(), colours.cpu().numpy() if colours is not None else None,
-                       m["normals"].cpu().numpy() if self.mesh_normals else None)
+                       m["normals"].cpu().numpy() if self.mesh_normals else None, **self._mesh_atlas(atlas))
         stats = self._texture_stats(self._mesh_stats(m), texture)
         t4 = time.time()
         etime = ev[0].elapsed_time(ev[1]) * 1e-3
@@ -496,11 +530,11 @@ class Renderer(nn.Module):
                             normals=self.mesh_normals or self.mesh_texture is not None, lattice=(cube, axes, n_kept),
                             simplify=self.mesh_simplify, smooth=self.mesh_smooth,
                             topology=self.mesh_topology, components=self.mesh_components)
-        colours, texture = self._mesh_colours(frame, m, consts, neg)
+        colours, texture, atlas = self._mesh_colours(frame, m, consts, neg)
         ev[4].record()
         cube_np = m["cube"].cpu().numpy()
         mesh = M_.Mesh(m["vertices"].cpu().numpy(), m["faces"].cpu().numpy(), colours.cpu().numpy() if colours is not None else None,
-                       m["normals"].cpu().numpy() if self.mesh_normals else None)
+                       m["normals"].cpu().numpy() if self.mesh_normals else None, **self._mesh_atlas(atlas))
         stats = self._texture_stats(self._mesh_stats(m), texture)
         n_inside = int(n_kept.cpu().item())
         t4 = time.time()

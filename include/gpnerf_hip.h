@@ -1492,6 +1492,100 @@ int gpnerf_texture_points(const float* points, int64_t n_points, const float* no
                           size_t workspace_bytes, float* color, float* weight, uint8_t* views, int64_t* stats, int64_t* totals,
                           void* stream);
 
+/* ---- a per-face texture atlas (gpnerf_atlas.hip): every face owns a triangular lattice of texels on its own surface, two faces share
+ * a rectangular cell of the atlas image.  There is no unwrap: the parameterisation is host arithmetic on the face index.  The texels'
+ * surface points go through gpnerf_texture_points UNCHANGED -- a texel's colour, weight, view bits and fate are by definition what that
+ * call gives its point and normal --, the colour list is packed into the image, and the mesh is drawn from the image over
+ * gpnerf_mesh_rasterize's face ids.  All device entry points: kernel launches only, on the caller's stream; nothing allocated, nothing
+ * waited for; every launch sized from the arguments alone; no atomic, no host read; every call captures into a HIP graph and replays
+ * with the same bytes; the result is a function of the inputs alone.  All arithmetic float64, multiply then add, unfused, in the order
+ * written, rounded to float32 once.
+ *
+ * THE DEFINITION, 1: the parameterisation.  R = res, the texels along a face edge, 2 <= R <= 64.
+ *   - face f with corners (a, b, c) owns the texels (i, j), i >= 0, j >= 0, i + j <= R - 1: tpf = R (R + 1) / 2 of them; texel (i, j)
+ *     has the index t = j R - j (j - 1) / 2 + i within its face (rows of j, i ascending) and the global number f tpf + t;
+ *   - its weights are wb = double(i) / double(R - 1), wc = double(j) / double(R - 1), wa = double(R - 1 - i - j) / double(R - 1): corner a
+ *     is texel (0, 0), b is (R - 1, 0), c is (0, R - 1), so the corner texels are the vertices bit for bit;
+ *   - packing: faces 2q and 2q + 1 share cell q, R + 2 texels wide and R high.  Face 2q's texel (i, j) sits at cell-local (x, y) =
+ *     (i, j) (x + y <= R - 1), face 2q + 1's at (R + 1 - i, R - 1 - j) (x + y >= R + 1); the diagonal x + y = R is the GUTTER between
+ *     the two hypotenuses.  P = ceil(n_faces / 2) cells, Cx = the smallest integer with Cx Cx >= P, Cy = ceil(P / Cx) (0 cells: 0 by
+ *     0); cell q sits at column q % Cx and row q / Cx.  The image is Wt = Cx (R + 2) wide and Ht = Cy R high, row 0 at the top;
+ *   - the UV of the texel at image column X, row Y is u = (X + 0.5) / Wt, v = 1 - (Y + 0.5) / Ht (OBJ's v points up).  A bilinear
+ *     sampler that stays inside a face's UV triangle reads other data only on the gutter along the hypotenuse.
+ * gpnerf_atlas_layout(n_faces, res, layout): HOST only.  layout: HOST int64 [GPNERF_ATLAS_LAYOUT_INTS] = Cx, Cy, Wt, Ht, tpf and
+ * n_faces tpf (GPNERF_ATLAS_CELLS_X ... _N_TEXELS).  GPNERF_E_ARG: a null layout, res outside 2..64, n_faces negative or >= 2^31, Wt
+ * or Ht above 16384, 2^31 texels or more.  Every call below refuses what this one refuses, before anything is launched.
+ *
+ * THE DEFINITION, 2: gpnerf_atlas_texels(vertices, n_vertices, faces, n_faces, normals, attrs, C, res, first_face, n_faces_here,
+ * points, out_normals, out_attrs, stream): the texels of the faces first_face .. first_face + n_faces_here - 1, T = n_faces_here tpf
+ * rows in global texel order.  normals: device float [n_vertices][3] or NULL; attrs: device float [n_vertices][C], C in 1..4, or NULL.
+ * Outputs, each optional (NULL):
+ *   - points device float [T][3] = float((wa a + wb b) + wc c) per component, the float32 corners widened;
+ *   - out_normals device float [T][3]: the same combination of the corners' normals; without normals the face's (b - a) x (c - a) --
+ *     u = b - a, v = c - a, (u1 v2 - u2 v1, u2 v0 - u0 v2, u0 v1 - u1 v0) in float64, rounded, not normalised (what rule 4 of
+ *     gpnerf_texture_points accepts) -- for every texel of the face;
+ *   - out_attrs device float [T][C]: the same combination of the corners' attributes.
+ * A face that names a vertex outside [0, n_vertices) gives NaN in every output row of its texels (gpnerf_texture_points files a NaN
+ * point as BEHIND in every view).  One launch, a lane per texel; T == 0 or no output: none.  GPNERF_E_ARG: the layout's refusals; null
+ * vertices with n_vertices > 0 or faces with n_faces > 0, n_vertices negative or >= 2^31; first_face or n_faces_here negative or
+ * first_face + n_faces_here > n_faces; C outside 1..4 with attrs or out_attrs; out_attrs without attrs (n_vertices > 0).
+ *
+ * THE DEFINITION, 4: gpnerf_atlas_pack(colors, views, n_faces, res, C, background, atlas, coverage, stream): colors: device float
+ * [n_faces tpf][C], the colour list in global texel order; views: device uint8 [n_faces tpf] (gpnerf_texture_points' view bits) or
+ * NULL (every texel counts as seen); background: HOST float [C].  Outputs, each optional: atlas device float [Ht][Wt][C], coverage
+ * device uint8 [Ht][Wt].  Every image texel inverts the packing: with q = (Y / R) Cx + X / (R + 2), x = X % (R + 2), y = Y % R,
+ *   - q >= P: GPNERF_ATLAS_UNOWNED (0), the texel takes background;
+ *   - x + y == R: GPNERF_ATLAS_GUTTER (3).  It takes the float64 sum of its left, upper, right and lower neighbours' colours, in that
+ *     order, over those that lie in the image and are owned, divided by double(their number); background when there are none (no
+ *     neighbour of a gutter texel is a gutter texel);
+ *   - otherwise the face is 2q (x + y < R, (i, j) = (x, y)) or 2q + 1 ((i, j) = (R + 1 - x, R - 1 - y)); a face >= n_faces (the absent
+ *     odd face): UNOWNED; else the texel takes its row of colors, coverage GPNERF_ATLAS_SEEN (1) where its view bits are not 0 and
+ *     GPNERF_ATLAS_FALLBACK (2) where they are.
+ * One launch, a lane per image texel: a gather, no clear pass and no scatter.  GPNERF_E_ARG: the layout's refusals; a null background;
+ * null colors with texels; C outside 1..4.
+ *
+ * THE DEFINITION, 5: gpnerf_atlas_shade(face_id, vertices, n_vertices, faces, n_faces, cams, n_views, H, W, z_near, atlas, res, C,
+ * filter, background, out, stream): face_id, the mesh, cams, n_views, H, W, z_near and background as gpnerf_mesh_interpolate takes
+ * them; atlas: device float [Ht][Wt][C] for (n_faces, res); out: device float [n_views][H][W][C].  A pixel is shaded where its face_id
+ * names a face that is drawn in that view and covers it -- gpnerf_mesh_interpolate's condition, its Ek, wk, zk, q and uk recomputed
+ * exactly as there --; every other pixel takes background.  With clamp(v, lo, hi) = (v > lo ? v : lo) then (v < hi ? v : hi):
+ *   s = clamp(ub (R - 1), 0, R - 1), t = clamp(uc (R - 1), 0, (R - 1) - s), i0 = min(int(floor(s)), R - 1), j0 = min(int(floor(t)),
+ *   R - 1 - i0), fs = s - i0, ft = t - j0.
+ *   - GPNERF_ATLAS_SIMPLEX: in the lower half-cell (fs + ft <= 1, or i0 + j0 >= R - 2) the taps are (i0, j0) with weight (1 - fs) - ft,
+ *     (i0 + 1, j0) with fs and (i0, j0 + 1) with ft; otherwise (i0 + 1, j0) with 1 - ft, (i0, j0 + 1) with 1 - fs and (i0 + 1, j0 + 1)
+ *     with (fs + ft) - 1.  A tap with i + j > R - 1 is NOT READ and its weight is dropped.  S = 0, D = 0; over the read taps in the
+ *     order (0,0), (1,0), (0,1), (1,1) of (i - i0, j - j0): S = S + w colour (per channel), D = D + w; out = float(S / D);
+ *   - GPNERF_ATLAS_NEAREST: the colour of the read tap of the largest weight, the first in that order among equal weights.
+ * The texel (i, j) of face f is read at its image position (the packing above): only the face's own texels, never a neighbour cell,
+ * never the gutter.  One launch, a lane per pixel and view.  GPNERF_E_ARG: the layout's refusals; what gpnerf_mesh_interpolate refuses
+ * of the arguments they share; a null atlas with n_faces > 0; C outside 1..4; a filter that is neither of the two.
+ * Known limit: the texel density is uniform per FACE, not per area -- right for marching-cubes and vertex-clustered meshes, whose
+ * faces are near-uniform in size, wasteful for arbitrary scans. */
+#define GPNERF_ATLAS_CELLS_X 0
+#define GPNERF_ATLAS_CELLS_Y 1
+#define GPNERF_ATLAS_WIDTH 2
+#define GPNERF_ATLAS_HEIGHT 3
+#define GPNERF_ATLAS_TEXELS_PER_FACE 4
+#define GPNERF_ATLAS_N_TEXELS 5
+#define GPNERF_ATLAS_LAYOUT_INTS 6
+#define GPNERF_ATLAS_UNOWNED 0
+#define GPNERF_ATLAS_SEEN 1
+#define GPNERF_ATLAS_FALLBACK 2
+#define GPNERF_ATLAS_GUTTER 3
+#define GPNERF_ATLAS_SIMPLEX 0
+#define GPNERF_ATLAS_NEAREST 1
+#define GPNERF_ATLAS_MIN_RES 2
+#define GPNERF_ATLAS_MAX_RES 64
+int gpnerf_atlas_layout(int64_t n_faces, int32_t res, int64_t* layout);
+int gpnerf_atlas_texels(const float* vertices, int64_t n_vertices, const int32_t* faces, int64_t n_faces, const float* normals,
+                        const float* attrs, int32_t C, int32_t res, int64_t first_face, int64_t n_faces_here, float* points,
+                        float* out_normals, float* out_attrs, void* stream);
+int gpnerf_atlas_pack(const float* colors, const uint8_t* views, int64_t n_faces, int32_t res, int32_t C, const float* background,
+                      float* atlas, uint8_t* coverage, void* stream);
+int gpnerf_atlas_shade(const int32_t* face_id, const float* vertices, int64_t n_vertices, const int32_t* faces, int64_t n_faces,
+                       const double* cams, int32_t n_views, int32_t H, int32_t W, double z_near, const float* atlas, int32_t res, int32_t C,
+                       int32_t filter, const float* background, float* out, void* stream);
+
 /* ---- fusing depth maps into a truncated signed distance field (gpnerf_fusion.hip): Curless and Levoy's volumetric integration of
  * calibrated depth maps -- a radiance field's rendered depth, gpnerf_mesh_rasterize's, a sensor's -- on a lattice.  Marching cubes at
  * the field's zero is the fused surface.  Kernel launches only, on the caller's stream; nothing allocated, nothing waited for; every
