@@ -173,6 +173,15 @@ COMPONENTS_KEEP_ALL, COMPONENTS_KEEP_LARGEST, COMPONENTS_KEEP_MIN_FACES = range(
 COMPONENTS_LABEL, COMPONENTS_VERTEX_COMPONENT, COMPONENTS_FACE_COMPONENT, COMPONENTS_TABLE = range(4)
 COMPONENTS_HDR_STATUS = 3
 COMPONENTS_COUNTING, COMPONENTS_COUNTED, COMPONENTS_EMITTED, COMPONENTS_MISMATCH, COMPONENTS_NO_ADJACENCY = 1, 2, 3, 4, 5
+# gpnerf_mesh_repair's flags, face fates, stats, the workspace's status word and its values (include/gpnerf_hip.h GPNERF_REPAIR_*)
+REPAIR_WELD, REPAIR_DROP_DUPLICATES, REPAIR_ORIENT, REPAIR_OUTWARD = 1, 2, 4, 8
+REPAIR_FATES = ("kept", "kept_flipped", "invalid", "unkeyable", "collapsed", "duplicate")
+REPAIR_STATS = ("vertices_out", "faces_out", "vertices_welded", "vertices_unkeyable", "vertices_unreferenced", "faces_invalid", "faces_unkeyable",
+                "faces_collapsed", "faces_duplicate", "faces_flipped", "edges_nonmanifold", "patches", "patches_closed", "patches_unorientable",
+                "patches_inverted", "patches_undecided")
+REPAIR_HDR_STATUS = 3
+REPAIR_COUNTING, REPAIR_COUNTED, REPAIR_EMITTED, REPAIR_MISMATCH, REPAIR_NO_COUNT = 1, 2, 3, 4, 5
+REPAIR_MAX_VERTICES = 1 << 30
 # gpnerf_mesh_voxelize's rules and stats, gpnerf_voxel_stats' row (include/gpnerf_hip.h GPNERF_VOXEL_*)
 VOXEL_PARITY, VOXEL_NONZERO = range(2)
 VOXEL_RULES = {"parity": VOXEL_PARITY, "nonzero": VOXEL_NONZERO}
@@ -356,6 +365,11 @@ SYMBOLS = {
                                          C.c_void_p, C.c_void_p]),
     "gpnerf_mesh_components_emit": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_size_t, C.c_int64, C.c_int64,
                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gpnerf_mesh_repair_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64]),
+    "gpnerf_mesh_repair": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_double, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p,
+                                     C.c_void_p]),
+    "gpnerf_mesh_repair_emit": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int64, C.c_void_p,
+                                          C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gpnerf_mesh_voxelize_workspace_bytes": (C.c_size_t, [C.c_int64, C.POINTER(C.c_int32), C.c_int32]),
     "gpnerf_mesh_voxelize": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, DP, C.POINTER(C.c_int32), C.c_int32, C.c_void_p, C.c_size_t,
                                        C.c_void_p, C.c_void_p, C.c_void_p]),

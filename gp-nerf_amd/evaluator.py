@@ -315,15 +315,26 @@ class MeshEvaluator:
     changes.  texture="atlas" runs the same protocol -- the same views, slots, keys and table -- with a per-face texture atlas of
     `texture_res` texels per face edge in place of the vertex colours: frame.texture_atlas bakes it from the colouring views (the
     faces' own normals), TextureAtlas.shade draws the held-out views, and `texture_seen_fraction` is the seen share of the owned
-    texels (the table's vertices_seen / vertices_unseen then count texels)."""
+    texels (the table's vertices_seen / vertices_unseen then count texels).
+    repair_gt (off by default; repair_tol, 0.0 by default, is its weld tolerance): a batch's `gt_mesh` goes through frame.repair_mesh
+    once per frame -- welded, repeated and unusable faces dropped, every patch wound outward -- before any metric above sees it: a
+    scanner's triangle soup or a merged export otherwise makes the signed metrics, the volume IoU and the normal consistency wrong
+    without saying so.  One host read per frame (the repaired mesh's two sizes).  `summarize()` adds `gt_repaired_frames` (frames whose
+    scan the repair changed), the per-frame lists `gt_repair_<name>` (_lib.REPAIR_STATS and `changed`) and `gt_repair_frame_index`,
+    and saves `<result_path>/repair_metrics.npy` (a structured array: frame_index, the sixteen counts, changed).  Off, no launch is
+    added, no key appears and every output is what it is without the keyword."""
     PAD = 10                              # if_nerf_mesh.py:20, the np.pad(cube, 10) of BaseRender.py:269
 
     def __init__(self, result_path, mesh_th, export_mesh=False, metric_samples=100000, metric_thresholds=(0.005, 0.01, 0.02),
                  metric_max_dist=float("inf"), metric_device=None, metric_cell_cap=None, metric_entry_cap=None, silhouette=False,
                  topology=False, volume=False, volume_rule="nonzero", components=False, align=None, align_iterations=10,
                  align_max_dist=float("inf"), signed=False, signed_band=8, visible=False, texture=False, texture_holdout=4,
-                 texture_res=8):
+                 texture_res=8, repair_gt=False, repair_tol=0.0):
         self.mesh_th = mesh_th
+        self.repair_gt, self.repair_tol = bool(repair_gt), float(repair_tol)
+        if not 0.0 <= self.repair_tol < float("inf"):
+            raise L.GpnerfError(f"MeshEvaluator: repair_tol must be finite and >= 0, got {repair_tol!r}")
+        self._repair_slots, self._repair_frames = [], []
         self.export_mesh = bool(export_mesh)
         self.result_path = result_path
         self.vis_result_dir = os.path.join(result_path, "mesh")
@@ -615,6 +626,14 @@ class MeshEvaluator:
         np.save(os.path.join(self.pts_result_dir, f"{self._scalar(batch['frame_index'])}.npy"), pts)
         if self.export_mesh:
             self.visualize(output, batch)
+        if self.repair_gt and batch.get("gt_mesh") is not None:
+            # the scan as every metric below sees it: welded, de-duplicated, wound outward (once per frame; the batch itself is left alone)
+            from . import frame as F
+            gv, gf = F.mesh_to_device(batch["gt_mesh"], torch.device(self.metric_device if self.metric_device is not None else "cuda:0"))
+            gv, gf, stats = F.repair_mesh(gv, gf, tol=self.repair_tol)
+            batch = {**batch, "gt_mesh": (gv, gf)}
+            self._repair_slots.append(stats)
+            self._repair_frames.append(self._scalar(batch["frame_index"]))
         if batch.get("gt_mesh") is not None:
             from . import frame as F
             pred = output["mesh"]
@@ -730,10 +749,29 @@ class MeshEvaluator:
         self._comp_slots, self._comp_frames = [], []
         return metrics, per_frame
 
+    def _summarize_repair(self):
+        """the scan repair's slots -> (means, per-frame lists), repair_metrics.npy written; resets them"""
+        from . import frame as F
+        host = torch.stack(self._repair_slots).cpu().numpy()   # the one read
+        rows = [F.read_mesh_repair(h) for h in host]
+        per_frame = {f"gt_repair_{k}": [r[k] for r in rows] for k in L.REPAIR_STATS + ("changed",)}
+        per_frame["gt_repair_frame_index"] = list(self._repair_frames)
+        metrics = {"gt_repaired_frames": int(sum(r["changed"] for r in rows))}
+        table = np.zeros(len(rows), dtype=[("frame_index", "i8")] + [(k, "i8") for k in L.REPAIR_STATS] + [("changed", "?")])
+        table["frame_index"] = self._repair_frames
+        for k in table.dtype.names[1:]:
+            table[k] = [r[k] for r in rows]
+        os.makedirs(self.result_path, exist_ok=True)
+        np.save(os.path.join(self.result_path, "repair_metrics.npy"), table)        # a structured array: one row per frame
+        print(f"gt_repaired_frames: {metrics['gt_repaired_frames']} of {len(rows)}")
+        self._repair_slots, self._repair_frames = [], []
+        return metrics, per_frame
+
     def summarize(self):
         if (self._sil_slots or self._topo_slots or self._vol_slots or self._comp_slots or self._signed_slots or self._visible_slots or
-                self._texture_slots):
-            parts = (([self._summarize_silhouettes()] if self._sil_slots else []) + ([self._summarize_topology()] if self._topo_slots else []) +
+                self._texture_slots or self._repair_slots):
+            parts = (([self._summarize_repair()] if self._repair_slots else []) +
+                     ([self._summarize_silhouettes()] if self._sil_slots else []) + ([self._summarize_topology()] if self._topo_slots else []) +
                      ([self._summarize_volumes()] if self._vol_slots else []) + ([self._summarize_components()] if self._comp_slots else []) +
                      ([self._summarize_signed()] if self._signed_slots else []) + ([self._summarize_visible()] if self._visible_slots else []) +
                      ([self._summarize_texture()] if self._texture_slots else []))

@@ -4,6 +4,7 @@ torch is used for device memory and streams only; all arithmetic of the path run
 the HIP library (include/gpnerf_hip.h).  Nothing here falls back to PyTorch ops.
 """
 import ctypes as C
+from types import SimpleNamespace
 
 import numpy as np
 import torch
@@ -1299,6 +1300,89 @@ def filter_components(vertices, faces, keep="largest", components=None, want_map
     L.check(lib.gpnerf_mesh_components_emit(ptr(vertices), nv, ptr(faces), nf, ws.data_ptr(), ws.numel(), n_out_v, n_out_f, ptr(out_v), ptr(out_f),
                                             ptr(vmap), ptr(kept), _stream_ptr(dev)), "gpnerf_mesh_components_emit")
     return out_v, out_f, components.stats, ((vmap, kept) if want_map else None)
+
+
+def _repair_flags(weld, drop_duplicates, orient, outward):
+    if outward and not orient:
+        raise L.GpnerfError("repair_mesh: outward needs orient (a patch is turned outward as a whole, behind its faces' common winding)")
+    return ((L.REPAIR_WELD if weld else 0) | (L.REPAIR_DROP_DUPLICATES if drop_duplicates else 0) | (L.REPAIR_ORIENT if orient else 0) |
+            (L.REPAIR_OUTWARD if outward else 0))
+
+
+def repair_mesh(vertices, faces, tol=0.0, weld=True, drop_duplicates=True, orient=True, outward=True, want_map=False):
+    """gpnerf_mesh_repair + gpnerf_mesh_repair_emit: a loaded device mesh (vertices float32 [n,3], faces int32 [m,3]: a triangle soup, a
+    merged export with repeated faces and mixed windings, an inside-out scan) made fit for the mesh tools here -> (vertices float32
+    [n',3], faces int32 [m',3], stats int64 [16] (_lib.REPAIR_STATS; read_mesh_repair names them)), all on the device.  include/
+    gpnerf_hip.h states the definition.  weld: the vertices of one key become the lowest index among them -- tol == 0: equal float32
+    coordinates, -0.0 as +0.0; tol > 0: the same cell of the grid of step tol (CELL clustering: two vertices closer than tol either side
+    of a cell wall stay apart); drop_duplicates: of the faces on one set of three vertices the lowest index stays; orient: every
+    edge-connected patch gets one winding (the minority flips); outward: a closed patch is turned to enclose positive volume (each by
+    itself: a cavity's wall ends up facing its own outside -- leave outward off to keep it).  Faces with an index out of range, a
+    non-finite corner or two equal corners and the vertices no face uses are always dropped; a kept vertex keeps its coordinates bit
+    for bit, and vertices and faces stay in their original order.  want_map: a fourth result, a namespace of vertex_map int32 [n]
+    (old -> new, following the weld; -1 dropped), kept_vertices int32 [n'] (new -> old), face_map int32 [m'] (new -> old), face_fate
+    uint8 [m] (_lib.REPAIR_FATES) and face_patch int32 [m'] (the lowest original face index of the face's patch).  One host read: the
+    two output sizes."""
+    lib = L.lib()
+    nv, nf = _mesh_arrays(vertices, faces, "repair_mesh")
+    flags = _repair_flags(weld, drop_duplicates, orient, outward)
+    tol = float(tol)
+    if not (0.0 <= tol < float("inf")):
+        raise L.GpnerfError(f"repair_mesh: tol must be finite and >= 0, got {tol!r}")
+    nbytes = int(lib.gpnerf_mesh_repair_workspace_bytes(nv, nf))
+    if nbytes <= 0:
+        raise L.GpnerfError(f"repair_mesh: sizes refused ({nv} vertices, {nf} faces; at most {L.REPAIR_MAX_VERTICES} vertices and {L.ADJACENCY_MAX_FACES} faces)")
+    dev = vertices.device
+    ws = torch.empty((nbytes,), device=dev, dtype=torch.uint8)
+    stats = torch.empty((len(L.REPAIR_STATS),), device=dev, dtype=torch.int64)
+    ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None
+    L.check(lib.gpnerf_mesh_repair(ptr(vertices), nv, ptr(faces), nf, tol, flags, ws.data_ptr(), ws.numel(), stats.data_ptr(), _stream_ptr(dev)),
+            "gpnerf_mesh_repair")
+    n_out_v, n_out_f = (int(v) for v in stats[:2].cpu().tolist())
+    out_v = torch.empty((n_out_v, 3), device=dev, dtype=torch.float32)
+    out_f = torch.empty((n_out_f, 3), device=dev, dtype=torch.int32)
+    maps = None
+    if want_map:
+        new = lambda n, dt: torch.empty((n,), device=dev, dtype=dt)
+        maps = SimpleNamespace(vertex_map=new(nv, torch.int32), kept_vertices=new(n_out_v, torch.int32), face_map=new(n_out_f, torch.int32),
+                               face_fate=new(nf, torch.uint8), face_patch=new(n_out_f, torch.int32))
+    m = maps if maps is not None else SimpleNamespace(vertex_map=None, kept_vertices=None, face_map=None, face_fate=None, face_patch=None)
+    L.check(lib.gpnerf_mesh_repair_emit(ptr(vertices), nv, ptr(faces), nf, ws.data_ptr(), ws.numel(), ptr(out_v), n_out_v, ptr(out_f), n_out_f,
+                                        ptr(m.vertex_map), ptr(m.kept_vertices), ptr(m.face_map), ptr(m.face_fate), ptr(m.face_patch),
+                                        _stream_ptr(dev)), "gpnerf_mesh_repair_emit")
+    return (out_v, out_f, stats, maps) if want_map else (out_v, out_f, stats)
+
+
+def read_mesh_repair(stats):
+    """repair_mesh's stats on the host (a tensor or array of 16) -> dict of the _lib.REPAIR_STATS names, plus `changed`: True when
+    anything was welded, dropped (a vertex or a face) or flipped -- False says the mesh came out as it went in."""
+    row = np.asarray(stats.detach().cpu() if isinstance(stats, torch.Tensor) else stats).astype(np.int64).reshape(-1)
+    if row.shape != (len(L.REPAIR_STATS),):
+        raise L.GpnerfError(f"read_mesh_repair: expected {len(L.REPAIR_STATS)} counts, got {row.shape}")
+    res = {k: int(v) for k, v in zip(L.REPAIR_STATS, row)}
+    res["changed"] = any(res[k] for k in ("vertices_welded", "vertices_unkeyable", "vertices_unreferenced", "faces_invalid", "faces_unkeyable",
+                                          "faces_collapsed", "faces_duplicate", "faces_flipped"))
+    return res
+
+
+def repair_mesh_object(mesh, device=None, **kw):
+    """repair_mesh on a mesh.Mesh -> (mesh.Mesh, stats dict of read_mesh_repair): the mesh is uploaded (float32 vertices), repaired with
+    repair_mesh's keywords and read back.  vertex_colors are carried through kept_vertices (a welded group keeps its representative's
+    colour); texture and face_uvs through face_map, the UV rows of a flipped face swapped like its corners.  vertex_normals are
+    DROPPED: welding and flipping leave them stale (frame.mesh_normals or a fresh estimate replaces them)."""
+    from .mesh import Mesh
+    dev = torch.device(device if device is not None else "cuda:0")
+    v, f = mesh_to_device(mesh, dev)
+    out_v, out_f, stats, maps = repair_mesh(v, f, want_map=True, **kw)
+    kept, face_map = maps.kept_vertices.cpu().numpy().astype(np.int64), maps.face_map.cpu().numpy().astype(np.int64)
+    colours = None if getattr(mesh, "vertex_colors", None) is None else mesh.vertex_colors[kept]
+    texture = uvs = None
+    if getattr(mesh, "face_uvs", None) is not None:
+        flipped = maps.face_fate.cpu().numpy()[face_map] == L.REPAIR_FATES.index("kept_flipped")
+        uvs = mesh.face_uvs[face_map].copy()
+        uvs[flipped] = uvs[flipped][:, [0, 2, 1]]
+        texture = mesh.texture.copy()
+    return Mesh(out_v.cpu().numpy(), out_f.cpu().numpy(), colours, None, texture, uvs), read_mesh_repair(stats)
 
 
 def _mesh_arrays(vertices, faces, what):

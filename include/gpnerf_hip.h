@@ -1128,6 +1128,137 @@ int gpnerf_mesh_components_emit(const float* vertices, int64_t n_vertices, const
                                 size_t workspace_bytes, int64_t n_out_vertices, int64_t n_out_faces, float* out_vertices, int32_t* out_faces,
                                 int32_t* vertex_map, int32_t* kept_vertices, void* stream);
 
+/* ---- repairing a loaded mesh (gpnerf_meshrepair.hip): weld, de-duplicate, orient outward.  Every other mesh tool here assumes what
+ * marching cubes makes: vertices shared between faces, no face twice, one winding, normals out.  A scanner's triangle soup, a merged
+ * OBJ with repeated faces and mixed windings, an inside-out export break that silently (every edge a boundary edge, one component
+ * per triangle, a wrong sign of the distance field).  This call makes such a mesh fit for them.  Both calls: kernel launches only, on
+ * the caller's stream; nothing allocated, nothing waited for; every launch sized from the arguments alone; every data-dependent length
+ * stays in the workspace; a fixed number of launches for given flags; no device-wide barrier, no cooperative launch, and no lane ever
+ * waits for a value another lane has yet to write; both capture into a HIP graph and replay with the same bits.
+ * vertices: device float [n_vertices][3]; faces: device int32 [n_faces][3]; n_vertices 0 to 2^30; n_faces 0 to 715 827 882 (the
+ * adjacency's limit); either may be NULL where its count is 0.  tol: finite and >= 0.  flags: GPNERF_REPAIR_WELD | _DROP_DUPLICATES |
+ * _ORIENT | _OUTWARD (OUTWARD needs ORIENT).
+ *
+ * THE DEFINITION
+ *   1. KEYS.  A vertex is UNKEYABLE when a coordinate is not finite, or tol > 0 and some |double(x) / tol| >= 2^62.  Otherwise its key
+ *      is, with tol == 0, the three float32 bit patterns with -0.0 taken as +0.0; with tol > 0, the three int64 floor(double(x) / tol).
+ *      The tol > 0 form is CELL CLUSTERING on the grid of step tol through the origin, not distance welding: two vertices closer than
+ *      tol on opposite sides of a cell wall do not weld; two vertices of one cell, up to sqrt(3) tol apart, do.
+ *   2. WELD.  With GPNERF_REPAIR_WELD rep[i] = the smallest index among the keyable vertices with i's key; without it rep[i] = i.  An
+ *      unkeyable vertex has no representative.  A representative keeps its own coordinates bit for bit; nothing is averaged.
+ *   3. FACE FATES, one per ORIGINAL face (a, b, c), the first that applies: GPNERF_REPAIR_INVALID (an index outside [0, n_vertices));
+ *      _UNKEYABLE (a corner is an unkeyable vertex); _COLLAPSED (two of rep[a], rep[b], rep[c] are equal); _DUPLICATE (with
+ *      GPNERF_REPAIR_DROP_DUPLICATES: some face of lower original index that reached this step has the same unordered set {rep[a],
+ *      rep[b], rep[c]}, whatever its winding); _KEPT or _KEPT_FLIPPED for all others: the LIVE faces, in ascending original index.
+ *   4. OUTPUT VERTICES: the representatives a live face references, in ascending original index.  kept_vertices maps new -> old;
+ *      vertex_map[i] = the new index of rep[i], -1 when rep[i] is not kept or i is unkeyable (a welded vertex maps to where it went);
+ *      face_map maps new -> old.  An output face is (new[rep[a]], new[rep[b]], new[rep[c]]), or (a, c, b) of that when it is flipped.
+ *   5. PATCHES (with GPNERF_REPAIR_ORIENT).  An edge is an unordered pair of output vertices, m the number of live half-edges on it.
+ *      Two live faces are JOINED when they share an edge with m == 2; a PATCH is a connected component of the live faces under JOINED.
+ *      This is EDGE connectivity -- non-manifold edges (m >= 3) and boundary edges (m == 1) join nothing -- and NOT the vertex
+ *      connectivity of gpnerf_mesh_components: two sheets that touch in a vertex, or along an edge three faces share, are patches of
+ *      their own, each wound by itself.  The patch's ROOT is its lowest original face index; face_patch[new face] = the root's
+ *      original index (without ORIENT: the face's own original index).  A joined pair has PARITY 1 when its two half-edges run the
+ *      same way, 0 otherwise.  A patch is ORIENTABLE when flips s(f) in {0, 1} exist with s(f) xor s(g) = the parity of every joined
+ *      pair; with s(root) = 0 they are unique.  An unorientable patch (a Moebius strip) has s = 0 everywhere and is counted.  A patch
+ *      is CLOSED when every edge of every one of its faces has m == 2 -- counting, on a non-manifold edge, the half-edges of THE PATCH'S
+ *      OWN faces: two solids that share an edge (m == 4, two half-edges of each) are two closed patches, each with a volume of its own;
+ *      three sheets on one edge are three open ones.
+ *   6. WHICH WAY (orientable patches only).  With GPNERF_REPAIR_OUTWARD, for CLOSED patches: the exact integer signed volume of the
+ *      patch after its flips on a quantised grid.  Per axis a: lo_a, hi_a = the float32 minimum and maximum over the output vertices;
+ *      c_a = (double(lo_a) + double(hi_a)) / 2; ext = max_a (double(hi_a) - double(lo_a)); q_a(x) = int64(rint((double(x) - c_a) *
+ *      (1048574.0 / ext))), every q = 0 where ext == 0; unfused double arithmetic, round half to even.  |q| <= 524 287, so a face's
+ *      det(q(A), q(B), q(C)) is below 2^60 in magnitude; per patch hi = det >> 30 (arithmetic) and lo = det & (2^30 - 1) are summed in
+ *      two int64 words, both below 2^60 at the face limit: the order of the adds cannot matter.  A negative total inverts every s of
+ *      the patch (counted as inverted); a zero total is counted as undecided and treated like an open patch.  Open patches, undecided
+ *      patches and every patch without OUTWARD: when more than half of the patch's faces have s = 1 every s is inverted, so that the
+ *      minority flips; on an exact half the root keeps its winding.  A flipped face (a, b, c) is written as (a, c, b).
+ *      CAVITIES: each closed patch is turned to enclose positive volume BY ITSELF, so the wall of an enclosed cavity ends up facing
+ *      its own outside, like the outer wall.  Voxelising with the parity rule is unchanged by that; the nonzero rule fills the
+ *      cavity.  A caller who wants neither leaves OUTWARD off (the majority rule then leaves a consistently wound wall alone).
+ *   7. the stats, int64 [GPNERF_REPAIR_STATS], every one written by the call: VERTICES_OUT, FACES_OUT; VERTICES_WELDED (keyable and
+ *      not their own representative), VERTICES_UNKEYABLE, VERTICES_UNREFERENCED (representatives no live face references);
+ *      FACES_INVALID, FACES_UNKEYABLE, FACES_COLLAPSED, FACES_DUPLICATE; FACES_FLIPPED; EDGES_NONMANIFOLD (edges with m >= 3);
+ *      PATCHES, PATCHES_CLOSED, PATCHES_UNORIENTABLE, PATCHES_INVERTED, PATCHES_UNDECIDED (the last six are 0 without ORIENT).
+ *      n_faces = FACES_OUT + FACES_INVALID + FACES_UNKEYABLE + FACES_COLLAPSED + FACES_DUPLICATE and n_vertices = VERTICES_OUT +
+ *      VERTICES_WELDED + VERTICES_UNKEYABLE + VERTICES_UNREFERENCED.
+ *   8. every output is a function of the inputs: it does not depend on the launch geometry, the arrival order or the hash function.
+ *      The vertex outputs and all stats do not depend on the order of the faces either, with two exceptions where a tie rule names a
+ *      face index: which duplicate survives, and the exact half of step 6.  Integer atomics only; no float is summed.
+ *
+ * gpnerf_mesh_repair fills the workspace and sets stats (device).  Three open-addressing hash tables live in the workspace, each of
+ * the smallest power of two >= 2 n slots and at least 64 (n = n_vertices, n_faces, 3 n_faces), cleared by a kernel of the library:
+ * vertices (an int32 slot holds a vertex index, its key read through the index), faces (an int32 slot holds a face index, its key
+ * the sorted triple of representatives) and edges (a 64-bit slot holds the packed (lo, hi) itself; beside it an incidence count
+ * and the first two incidences (face, direction)); a fourth, of the edge table's capacity, counts the half-edges per (non-manifold
+ * edge, patch) for step 5's CLOSED.  Insert: probe; CAS the own index into an empty slot; atomicMin it into a slot
+ * whose occupant has an equal key; go on otherwise.  A slot never empties and never changes its key, so a key ends in one slot whatever
+ * the races and that slot ends holding the key's minimum; a second kernel, behind the kernel boundary, looks the answers up.  Launches:
+ * the clear; a lane per vertex (insert, with WELD); a lane per vertex (rep); a lane per face (the first three fates; insert, with
+ * DROP_DUPLICATES); a lane per face (DUPLICATE, the live marks, the half-edges into the edge table); with ORIENT: a lane per vertex
+ * (the bounding box, with OUTWARD), a lane per face (a lock-free union-find over the faces whose word packs (parent << 1) | parity:
+ * find accumulates the parity along the walk, a link hangs the higher root under the lower by CAS with parity p_a xor p_b xor p_edge
+ * and retries from find when the CAS fails, a pair found under one root is CHECKED instead and a mismatch marks the face), a lane per
+ * face (flatten; faces, flipped faces, the open and mismatch marks and the determinant's two words into the root's row, reduced
+ * per wavefront and per workgroup where the lanes agree on the root), two lanes per face with a non-manifold edge (its patch's own
+ * half-edges on it, counted and looked up), a lane per root (the decision), a lane per face (the fate);
+ * two three-launch scans (the new numbers); one lane (stats).
+ * gpnerf_mesh_repair_emit writes out_vertices float [n_out_vertices][3], out_faces int32 [n_out_faces][3] and the maps, each of which
+ * may be NULL: vertex_map int32 [n_vertices], kept_vertices int32 [n_out_vertices], face_map int32 [n_out_faces], face_fate uint8
+ * [n_faces], face_patch int32 [n_out_faces].  The caller reads VERTICES_OUT and FACES_OUT (the one host read) and sizes the outputs;
+ * emit's first launch compares n_vertices, n_faces and the two output sizes with those counted ON THE DEVICE: when they differ
+ * nothing is written and the workspace's 64-bit word GPNERF_REPAIR_HDR_STATUS says GPNERF_REPAIR_MISMATCH; on a workspace with no
+ * finished count nothing is written and it says GPNERF_REPAIR_NO_COUNT; after a good emit GPNERF_REPAIR_EMITTED.
+ * workspace: gpnerf_mesh_repair_workspace_bytes(n_vertices, n_faces) bytes (host arithmetic only, from the worst-case capacities; 0
+ * for what the calls refuse) = 256 + 2 a(4 nv) + a(4 Cv) + 2 a(nf) + 3 a(4 nf) + a(4 Cf) + 2 a(8 Ce) + 3 a(4 Ce) + a(56 nf) +
+ * a(8 ceil(max(nv, nf, 1) / 2048)), with a() rounding up to a multiple of 256 and Cv, Cf, Ce the three capacities: the header; rep and
+ * the new vertex numbers; the vertex table; the fates and the open / mismatch marks; the new face numbers, the union-find's words
+ * and the flattened (root, parity); the face table; the edge table's keys and incidences (8 bytes each), its counts and the per-patch table's slots and counts (4 each); the patches' rows (seven
+ * int64 per face: a root is a face); the scans' block sums.
+ * GPNERF_E_ARG, before anything is launched: a null workspace or stats; null vertices / faces / out_vertices / out_faces whose count
+ * is > 0; a count that is negative or beyond the limits above; a tol that is negative or not finite; unknown flag bits; OUTWARD
+ * without ORIENT; a workspace under its formula; emit: output sizes that are negative or exceed the input's. */
+#define GPNERF_REPAIR_WELD 1u
+#define GPNERF_REPAIR_DROP_DUPLICATES 2u
+#define GPNERF_REPAIR_ORIENT 4u
+#define GPNERF_REPAIR_OUTWARD 8u
+#define GPNERF_REPAIR_KEPT 0
+#define GPNERF_REPAIR_KEPT_FLIPPED 1
+#define GPNERF_REPAIR_INVALID 2
+#define GPNERF_REPAIR_UNKEYABLE 3
+#define GPNERF_REPAIR_COLLAPSED 4
+#define GPNERF_REPAIR_DUPLICATE 5
+#define GPNERF_REPAIR_VERTICES_OUT 0
+#define GPNERF_REPAIR_FACES_OUT 1
+#define GPNERF_REPAIR_VERTICES_WELDED 2
+#define GPNERF_REPAIR_VERTICES_UNKEYABLE 3
+#define GPNERF_REPAIR_VERTICES_UNREFERENCED 4
+#define GPNERF_REPAIR_FACES_INVALID 5
+#define GPNERF_REPAIR_FACES_UNKEYABLE 6
+#define GPNERF_REPAIR_FACES_COLLAPSED 7
+#define GPNERF_REPAIR_FACES_DUPLICATE 8
+#define GPNERF_REPAIR_FACES_FLIPPED 9
+#define GPNERF_REPAIR_EDGES_NONMANIFOLD 10
+#define GPNERF_REPAIR_PATCHES 11
+#define GPNERF_REPAIR_PATCHES_CLOSED 12
+#define GPNERF_REPAIR_PATCHES_UNORIENTABLE 13
+#define GPNERF_REPAIR_PATCHES_INVERTED 14
+#define GPNERF_REPAIR_PATCHES_UNDECIDED 15
+#define GPNERF_REPAIR_STATS 16
+#define GPNERF_REPAIR_HDR_STATUS 3
+#define GPNERF_REPAIR_COUNTING 1
+#define GPNERF_REPAIR_COUNTED 2
+#define GPNERF_REPAIR_EMITTED 3
+#define GPNERF_REPAIR_MISMATCH 4
+#define GPNERF_REPAIR_NO_COUNT 5
+size_t gpnerf_mesh_repair_workspace_bytes(int64_t n_vertices, int64_t n_faces);
+int gpnerf_mesh_repair(const float* vertices, int64_t n_vertices, const int32_t* faces, int64_t n_faces, double tol, uint32_t flags,
+                       void* workspace, size_t workspace_bytes, int64_t* stats, void* stream);
+int gpnerf_mesh_repair_emit(const float* vertices, int64_t n_vertices, const int32_t* faces, int64_t n_faces, void* workspace,
+                            size_t workspace_bytes, float* out_vertices, int64_t n_out_vertices, int32_t* out_faces, int64_t n_out_faces,
+                            int32_t* vertex_map, int32_t* kept_vertices, int32_t* face_map, uint8_t* face_fate, int32_t* face_patch,
+                            void* stream);
+
 /* ---- voxelising a mesh (gpnerf_voxelize.hip): the SOLID occupancy of a triangle mesh on a lattice, packed one bit per lattice point,
  * the counts that give its volume, and the small operations on packed cubes that go with it (from a density cube, back to a float
  * cube, the popcounts of two cubes for a volumetric IoU, containment of points).  It is the one direction mesh -> lattice beside
