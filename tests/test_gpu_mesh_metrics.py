@@ -247,7 +247,7 @@ def test_an_overflowing_grid_says_so_and_writes_no_entry(monkeypatch):
     brute = F.point_mesh_distance(q, tv, tf)
     assert torch.equal(bits(ok["dist"]), bits(brute["dist"])) and torch.equal(ok["face"], brute["face"])
     # the wrapper's one retry, forced by a tiny default
-    monkeypatch.setattr(F, "mesh_grid_caps", lambda n_faces: (cell_cap, 16))
+    monkeypatch.setattr(importlib.import_module(F.build_mesh_grid.__module__), "mesh_grid_caps", lambda n_faces: (cell_cap, 16))
     retried = F.build_mesh_grid(tv, tf)
     assert retried.entry_cap == needed and retried.header()["status"] == L.GRID_OK
     unchecked = F.build_mesh_grid(tv, tf, check=False)
